@@ -9,15 +9,26 @@ generators in gtars_amd/synth.py).  One "step" = one fused
 tokenization pass (CSR u64 offsets + u32 token ids in Bits order) over one
 batch that is already resident in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W] [--queries Q] [--universe U]
+  python bench.py [--gpus N --steps K --warmup W] [--queries Q] [--universe U] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the outputs of the last timed step when
+--dump-outputs is given, and prints the result line.  Everything else below -- the oracle check of the timed output,
+the repetition statistics, the roofline (and its rocprofv3 children), the sorted-input, large-batch, universe-size,
+IGD / LOLA / fragment objects, the all-gather and sharded objects at N > 1 and the CPU baselines -- runs only with
+--full (the --no-* options then leave parts of it out, as before).
+
+--dump-outputs DIR: after the timed steps, DIR/offsets.npy (u64[Q+1]) and DIR/token_ids.npy (u32[H]) of the last
+timed step's batch -- what a caller of the tokenizer receives -- as float64, 64 MB at most (beyond that a sorted,
+fixed-seed sample of each).  The workload is seeded, so the same arguments give the same inputs in every run.
 
 How the number is taken:
   * every step works on a DIFFERENT batch and writes DIFFERENT output buffers: the run rotates through
     --batches (default 32) device-resident batches, 0.7 GB in all, so that neither the 12 MB of queries
     nor the 10 MB of results of a step are still in the 256 MB Infinity Cache when their turn comes again;
-  * a repetition = K back-to-back steps bracketed by barrier + torch.cuda.synchronize() on both sides, MAX
-    over ranks; `value` is the MEDIAN over the repetitions, of which there are as many as it takes to keep
-    the GPU busy for >= --min-seconds (default 0.6 s; never fewer than 11);
+  * the K timed steps run back to back, bracketed by barrier + torch.cuda.synchronize() on both sides, MAX
+    over ranks: `value` = queries of the K steps (all ranks) / that wall time, `ms_per_step` = wall time / K;
+  * --full also repeats the K steps as many times as it takes to keep the GPU busy for >= --min-seconds
+    (default 0.6 s; never fewer than 11 repetitions) and reports their spread under `timing`;
   * roofline.achieved = algorithmic bytes per launch / average kernel duration, the duration measured with
     HIP events on the launch stream around the K launches of the same repetitions (the events see only
     that stream; one step is exactly one k_tok_lds launch);
@@ -39,7 +50,7 @@ universe and user set (config 4) -- is measured at N > 1 in `igd_config3_sharded
 ingests only its chromosomes, counts, and ONE all-reduce of the per-file vector(s) yields the global counts
 (what must be reduced: gtars-lola/src/enrichment.rs:198-221).  `ranks` lists what every rank saw (device, backend).
 
-Rank 0 prints ONE JSON line.  At N = 1 it also carries: larger batches (`roofline_large`), a hit-heavy batch
+Rank 0 prints ONE JSON line.  With --full, at N = 1 it also carries: larger batches (`roofline_large`), a hit-heavy batch
 (`roofline_hit_heavy`: 1 Mbp-wide queries, ~33 ids each; `roofline_hit_heavy_overlapping`: the same on the ChIP-like universe),
 universes of 140k / 200k / 1M regions at 64M queries (`roofline_universe_*`: beyond the LDS key budget of the tokenizer kernel),
 BASELINE config 3
@@ -69,6 +80,26 @@ PROFILE_ROUND = "r06"
 def algorithmic_bytes(nq: int, h: int, nu: int) -> int:
     """12*Nq read (chrom,start,end) + 8*(Nq+1) written offsets + 4*H written ids + 12*Nu index read."""
     return 12 * nq + 8 * (nq + 1) + 4 * h + 12 * nu
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: each array as out_dir/<name>.npy in float64 (exact for u32 ids and for offsets below 2**53).  When they
+    would take more than `limit` bytes, each keeps the same fraction of its elements, at sorted positions drawn with a fixed
+    seed: the same arrays give the same sample in every run.  -> {name: elements written}"""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 8 * sum(int(np.asarray(a).size) for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        if total > limit:
+            keep = a.size * limit // total
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+        written[name] = int(a.size)
+    return written
 
 
 def cpu_baseline(u, q, budget_s: float = 12.0):
@@ -872,9 +903,10 @@ def _lib_host_threads() -> int:
     return _lib.lib.gtars_host_threads(64)
 
 
-def spawn_ranks(n: int) -> int:
+def spawn_ranks(n: int, dump_dir=None) -> int:
     """`python bench.py --gpus N` started plainly: start the N ranks as a child torch.distributed.run (this process has
-    not touched a GPU: torch.cuda.device_count() does not initialise one on this image) and return its exit code."""
+    not touched a GPU: torch.cuda.device_count() does not initialise one on this image) and return its exit code.
+    dump_dir: --dump-outputs as an absolute path (the ranks run in the repository root)."""
     import socket
     import subprocess
 
@@ -890,7 +922,7 @@ def spawn_ranks(n: int) -> int:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:] + (["--dump-outputs", dump_dir] if dump_dir else [])
     return subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, GTARS_BENCH_SPAWNED="1")).returncode
 
 
@@ -1118,26 +1150,33 @@ def bench_fragsplit_sharded(dist, rank, world, max_over_ranks, barrier, files=32
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle check, repetition statistics, roofline, further sizes / configs and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's offsets and token ids to DIR/<name>.npy")
     ap.add_argument("--queries", type=int, default=1_000_000, help="query regions per step per GPU")
     ap.add_argument("--universe", type=int, default=100_000)
     ap.add_argument("--batches", type=int, default=32, help="distinct device-resident batches the steps rotate through")
-    ap.add_argument("--min-seconds", type=float, default=0.6, help="GPU time to spend in timed repetitions (at least 11 repetitions)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not spawn the rocprofv3 --pmc passes that measure roofline.traffic")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline_large / igd_config3 / lola_config4 / host path")
+    ap.add_argument("--min-seconds", type=float, default=0.6, help="--full: GPU time to spend in timed repetitions (at least 11 repetitions)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not spawn the rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip roofline_large / igd_config3 / lola_config4 / host path")
     ap.add_argument("--large", type=str, default="16000000,64000000,256000000,1000000000", help="batch sizes of roofline_large (SURVEY 8d: 1.6e7 / 2.56e8 / 1e9, and 64M)")
     ap.add_argument("--c5-files", type=int, default=48, help="fragment files (1e5 fragments each) of fragsplit_config5 (the config names 10,000)")
     ap.add_argument("--scale-configs", type=int, default=1, help="tests only: divide the sizes of configs 3 / 4 (sharded objects) by this")
     ap.add_argument("--igd-pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.igd_pmc_child:
         return igd_pmc_child()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly: this process becomes the launcher of the N ranks (no GPU call has been made here)
-        sys.exit(spawn_ranks(args.gpus))
+        sys.exit(spawn_ranks(args.gpus, args.dump_outputs))
 
     import torch
 
@@ -1178,15 +1217,19 @@ def main():
     nu = len(u["chrom"])
     ix = gtars_amd.OverlapIndex(u["chrom"], u["start"], u["end"], n_chrom=synth.N_CHROM)
     stream = torch.cuda.current_stream().cuda_stream
-    q0 = None
+    # the batches are generated on a few host threads (each from its own seed: the same data as one after the other)
+    from concurrent.futures import ThreadPoolExecutor
+
+    gen_threads = max(1, min(8, len(os.sched_getaffinity(0)) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))))
+    with ThreadPoolExecutor(max_workers=gen_threads) as ex:
+        host_batches = list(ex.map(lambda b: synth.make_queries(u, nq, seed=4 + 100 * rank + 7919 * b), range(nb)))
+    q0 = host_batches[0]
     batches = []
-    for b in range(nb):
-        qb = synth.make_queries(u, nq, seed=4 + 100 * rank + 7919 * b)
-        if b == 0:
-            q0 = qb
+    for qb in host_batches:
         qc, qs, qe = (_dev(qb[k], dev) for k in ("chrom", "start", "end"))
         offsets = torch.empty(nq + 1, dtype=torch.int64, device=dev)
         batches.append([qc, qs, qe, offsets, None, 0])
+    del host_batches, qb
     for bt in batches:  # size the id buffers: one offsets-only pass per batch
         qc, qs, qe, offsets = bt[:4]
         h = ix.tokenize_device(qc.data_ptr(), qs.data_ptr(), qe.data_ptr(), nq, offsets.data_ptr(), 0, 0, stream, sync=True)
@@ -1221,27 +1264,49 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # ---- timed repetitions: K steps each, barrier + synchronize on both sides, MAX over ranks; median reported ----
+    # ---- the timed steps: exactly K of them, back to back, barrier + synchronize on both sides, MAX over ranks ----
     ts = torch.cuda.current_stream()
-    rep_wall, rep_kernel_ms = [], []
-    gpu_s, reps_min, reps_max = 0.0, 11, 20000
-    while len(rep_wall) < reps_min or (gpu_s < args.min_seconds and len(rep_wall) < reps_max):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        barrier()
-        t0 = time.perf_counter()
-        e0.record(ts)
-        for _ in range(args.steps):
-            step()
-        e1.record(ts)
-        barrier()
-        dt = max_over_ranks(time.perf_counter() - t0)
-        rep_wall.append(dt)
-        rep_kernel_ms.append(e0.elapsed_time(e1) / args.steps)
-        gpu_s += dt
-    elapsed = statistics.median(rep_wall)
-    avg_ms = statistics.median(rep_kernel_ms)
-    # the outputs the timed launches left behind, against the oracle (bit-exact): batch 0 on every rank
-    verified = verify_tokenization(u, q0, batches[0][3], batches[0][4], batches[0][5], f"rank {rank}: the timed output of batch 0")
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    barrier()
+    elapsed = max_over_ranks(time.perf_counter() - t0)
+    timing = {"timed_steps": args.steps, "timed_seconds": elapsed,
+              "statistic": "wall time of the K timed steps back to back, barrier + synchronize on both sides, max over ranks"}
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = (counter[0] - 1) % nb  # the batch of the last timed step
+        _, _, _, offsets, ids, h = batches[last]
+        arrays = {"offsets": offsets.cpu().numpy().view(np.uint64), "token_ids": ids[:h].cpu().numpy().view(np.uint32)}
+        dumped = {"dir": args.dump_outputs, "batch": last, "dtype": "float64",
+                  "elements": dump_outputs(args.dump_outputs, arrays), "of": {k: int(v.size) for k, v in arrays.items()}}
+        del arrays
+
+    verified = None
+    if args.full:
+        # ---- repetitions of the K steps as many as keep the GPU busy for --min-seconds (at least 11), median reported ----
+        rep_wall, rep_kernel_ms = [], []
+        gpu_s, reps_min, reps_max = 0.0, 11, 20000
+        while len(rep_wall) < reps_min or (gpu_s < args.min_seconds and len(rep_wall) < reps_max):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            barrier()
+            t0 = time.perf_counter()
+            e0.record(ts)
+            for _ in range(args.steps):
+                step()
+            e1.record(ts)
+            barrier()
+            dt = max_over_ranks(time.perf_counter() - t0)
+            rep_wall.append(dt)
+            rep_kernel_ms.append(e0.elapsed_time(e1) / args.steps)
+            gpu_s += dt
+        avg_ms = statistics.median(rep_kernel_ms)
+        timing.update({"repetitions": len(rep_wall), "repetition_statistic": "median over repetitions of K back-to-back steps",
+                       "repetitions_seconds": sum(rep_wall), "median_ms_per_step": statistics.median(rep_wall) / args.steps * 1e3,
+                       "min_ms_per_step": min(rep_wall) / args.steps * 1e3, "max_ms_per_step": max(rep_wall) / args.steps * 1e3})
+        # the outputs the timed launches left behind, against the oracle (bit-exact): batch 0 on every rank
+        verified = verify_tokenization(u, q0, batches[0][3], batches[0][4], batches[0][5], f"rank {rank}: the timed output of batch 0")
     # what every rank saw (device, backend): "did RCCL see N ranks" is answerable from the line
     me = {"rank": rank, "local_rank": local_rank, "device": dev_index, "name": torch.cuda.get_device_name(dev_index),
           "pci_bus_id": getattr(torch.cuda.get_device_properties(dev_index), "pci_bus_id", None),
@@ -1253,7 +1318,7 @@ def main():
 
     # ---- the dominant kernel: its name from the library's profiling hooks, its duration from the events above ----
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         _lib.lib.gtars_prof_reset()
         _lib.lib.gtars_prof_enable(1)
         step()
@@ -1266,8 +1331,8 @@ def main():
         traffic, traffic_source, fetch_b, write_b = None, "not measured in this run (needs rocprofv3 --pmc passes)", None, None
         tpath = os.path.join(ROOT, "profiles", PROFILE_ROUND, "traffic_tokenize_1M.json")
         if world == 1 and not args.no_extras and not args.no_pmc:
-            live = measure_traffic_with_rocprof(["--steps", "20", "--warmup", "5", "--queries", str(nq), "--universe", str(args.universe),
-                                                 "--no-cpu-baseline", "--no-extras", "--no-pmc", "--min-seconds", "0.05"])
+            live = measure_traffic_with_rocprof(["--full", "--steps", "20", "--warmup", "5", "--queries", str(nq), "--universe",
+                                                 str(args.universe), "--no-cpu-baseline", "--no-extras", "--no-pmc", "--min-seconds", "0.05"])
             tok = [v for k, v in (live or {}).items() if "k_tok_lds" in k and v["fetch_dispatches"] and v["write_dispatches"]]
             if tok:
                 # each counter's sum over ITS OWN pass's dispatches (the passes are separate runs of a --min-seconds loop)
@@ -1307,7 +1372,7 @@ def main():
     # ---- the same steps on POSITION-SORTED batches: what Tokenizer.tokenize(path) delivers (a file-loaded RegionSet is sorted by
     # (chr, start), gtars-core/src/models/region_set.rs:182) -- reported next to the shuffled headline, never instead of it ----
     sorted_input = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         ns_b = min(nb, 8)  # 8 x 45 MB of queries and results: past the Infinity Cache like the headline's rotation
         sb = []
         for b in range(ns_b):
@@ -1349,7 +1414,7 @@ def main():
 
     # ---- N > 1: the same steps when one consumer needs the whole batch (all-gatherv of the CSR over RCCL) ----
     with_allgather = None
-    if dist is not None:
+    if args.full and dist is not None:
         from gtars_amd import sharding
 
         # warm-up: communicator setup, and one size exchange per distinct batch -- the per-rank (queries, ids) shapes of a
@@ -1371,7 +1436,7 @@ def main():
                                   "CSR; per-rank sizes exchanged once per distinct batch (warm-up), host wall time incl. barriers"}
 
     sharded = None
-    if dist is not None and not args.no_extras:
+    if args.full and dist is not None and not args.no_extras:
         del batches[:]
         torch.cuda.empty_cache()
         sharded = bench_sharded(dist, backend, dev, rank, world, max_over_ranks, barrier, max(1, args.scale_configs))
@@ -1405,16 +1470,16 @@ def main():
                 "resident_bytes_rotated": resident_bytes,
                 "sharding": "independent query ranges per rank, universe index replicated, no collective",
             },
-            "timing": {"repetitions": len(rep_wall), "statistic": "median over repetitions of K back-to-back steps",
-                       "timed_seconds": sum(rep_wall), "min_ms_per_step": min(rep_wall) / args.steps * 1e3,
-                       "max_ms_per_step": max(rep_wall) / args.steps * 1e3},
+            "timing": timing,
             "roofline": roofline,
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
         if world > 1:
             out["headline_scaling_note"] = (
                 "the headline is weak-scaled replicas by construction: every rank tokenizes its own 1M-query batches against a replicated "
                 "index and nothing crosses ranks, so value at N GPUs is ~N x the single-GPU value and says nothing about the interconnect. "
-                "Read scaling from the objects that exchange or partition data: with_allgather (CSR all-gatherv), igd_config3_weak "
+                "Read scaling from the objects that exchange or partition data (with --full): with_allgather (CSR all-gatherv), igd_config3_weak "
                 "(chromosome buckets + one all-reduce per call, the genome grows with the ranks), igd_config3_sharded / "
                 "lola_config4_sharded (strong-scaled, latency-bound at 8 ranks: see their per_rank_ms) and fragsplit_config5_weak")
         if sorted_input:
@@ -1423,7 +1488,7 @@ def main():
             out["with_allgather"] = with_allgather
         if sharded:
             out.update(sharded)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             sizes = [int(t) for t in args.large.split(",") if t]
             out["roofline_large"] = bench_large(ix, u, q0, nu, sizes, dev, stream)
             # the same kernel on a 64M-query batch IN ORDER (what Tokenizer.tokenize(path) delivers at that size): neighbouring
@@ -1490,7 +1555,7 @@ def main():
             out["lola_config4"] = bench_lola_config4(dev, stream, cpu=cpu)
             out["fragsplit_config5"] = bench_fragsplit_config5(files=args.c5_files)
             out["fragsplit_config5_1000"] = bench_fragsplit_many_files()
-        if not args.no_cpu_baseline and world == 1:  # a reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # a reported baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(u, q0)
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(u, q0)
         print(json.dumps(out), flush=True)

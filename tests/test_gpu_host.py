@@ -509,7 +509,7 @@ def test_bench_line_contract():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -528,6 +528,46 @@ def test_bench_line_contract():
     assert r["traffic"] is not None and r["traffic"] > 12.0 * d["config"]["queries_per_step_per_gpu"], r
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert d["value"] > 1e9 and abs(d["value"] - d["config"]["queries_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain bench.py run (no --full): the headline line only, exactly --steps timed steps, and with --dump-outputs the offsets
+    and token ids of the last timed step's batch as float64 -- equal to the oracle's tokenization of that batch."""
+    import json
+    import subprocess
+    import sys
+
+    from gtars_amd import synth
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nq, nb, steps, warmup = 200_000, 3, 7, 2
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--queries", str(nq), "--batches", str(nb), "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == steps and d["warmup"] == warmup and d["timing"]["timed_steps"] == steps
+    assert d["unit"] == "query intervals/s" and d["dtype"] == "u32" and d["higher_is_better"] is True
+    assert abs(d["ms_per_step"] - d["timing"]["timed_seconds"] / steps * 1e3) < 1e-9 * d["ms_per_step"] + 1e-12
+    assert abs(d["value"] - nq / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    # nothing of --full
+    assert d["roofline"] is None and d["verified"] is None and "repetitions" not in d["timing"]
+    assert not {"sorted_input", "roofline_large", "igd_config3", "lola_config4", "cpu_baseline"} & set(d)
+    # the dumped arrays: the batch the last timed step worked on (nb sizing-checked steps, warm-up, timed steps rotate over nb batches)
+    dm = d["dumped_outputs"]
+    assert dm["batch"] == (nb + warmup + steps - 1) % nb and dm["dtype"] == "float64"
+    off = np.load(tmp_path / "dump" / "offsets.npy")
+    ids = np.load(tmp_path / "dump" / "token_ids.npy")
+    assert off.dtype == np.float64 and ids.dtype == np.float64
+    u = synth.make_universe(100_000, seed=3)
+    q = synth.make_queries(u, nq, seed=4 + 7919 * dm["batch"])
+    off_o, ids_o = oracle.Index(u["chrom"], u["start"], u["end"], None, n_chrom=synth.N_CHROM).tokenize(q["chrom"], q["start"], q["end"])
+    assert dm["elements"] == {"offsets": nq + 1, "token_ids": len(ids_o)}
+    assert np.array_equal(off, off_o.astype(np.float64)) and np.array_equal(ids, ids_o.astype(np.float64))
 
 
 # ------------------------------------------------------------ two ranks on one GPU: the sharded drivers on the HIP path
@@ -1129,7 +1169,7 @@ def test_bench_py_two_ranks_on_one_gpu():
     env = dict(os.environ, GTARS_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--queries", "200000", "--batches", "3", "--min-seconds", "0.01", "--no-cpu-baseline", "--no-extras"]
+           "--queries", "200000", "--batches", "3", "--min-seconds", "0.01", "--no-cpu-baseline", "--no-extras", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
@@ -1154,7 +1194,7 @@ def test_bench_py_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["GTARS_BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--queries", "200000",
-           "--batches", "3", "--min-seconds", "0.01", "--no-cpu-baseline", "--scale-configs", "100"]
+           "--batches", "3", "--min-seconds", "0.01", "--no-cpu-baseline", "--scale-configs", "100", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
@@ -1233,7 +1273,7 @@ def test_bench_py_with_eight_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
     env["GTARS_BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--queries", "100000",
-           "--batches", "2", "--min-seconds", "0.01", "--no-cpu-baseline", "--scale-configs", "100"]
+           "--batches", "2", "--min-seconds", "0.01", "--no-cpu-baseline", "--scale-configs", "100", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])

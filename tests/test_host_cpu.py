@@ -604,3 +604,29 @@ def test_bench_traffic_is_each_counters_mean_over_its_own_pass(tmp_path):
     wrong = (tok["fetch"] + tok["write"]) / tok["fetch_dispatches"]
     assert abs(wrong - tok["bytes_per_dispatch"]) > 1.9e6
     assert res["k_scan_blocks"]["fetch_dispatches"] == 3 and res["k_scan_blocks"]["write_dispatches"] == 2
+
+
+def test_bench_dump_outputs_exact_under_the_limit_and_a_fixed_sample_above_it(tmp_path):
+    """bench.py --dump-outputs: arrays that fit the limit are written whole as float64 (u64 offsets and u32 ids exactly); above it
+    each array keeps the same fraction of its elements, at sorted positions that are the same in every run."""
+    import bench
+
+    rng = np.random.default_rng(5)
+    offsets = np.cumsum(rng.integers(0, 3, 10_001)).astype(np.uint64)
+    ids = rng.integers(0, 2**32, 20_000, dtype=np.uint64).astype(np.uint32)
+    n = bench.dump_outputs(str(tmp_path / "whole"), {"offsets": offsets, "token_ids": ids})
+    assert n == {"offsets": 10_001, "token_ids": 20_000}
+    o, t = np.load(tmp_path / "whole" / "offsets.npy"), np.load(tmp_path / "whole" / "token_ids.npy")
+    assert o.dtype == np.float64 and t.dtype == np.float64
+    assert np.array_equal(o.astype(np.uint64), offsets) and np.array_equal(t.astype(np.uint32), ids)
+
+    limit = 8 * 3_000
+    for d in ("a", "b"):
+        n = bench.dump_outputs(str(tmp_path / d), {"offsets": offsets, "token_ids": ids}, limit=limit)
+        assert 8 * sum(n.values()) <= limit and n["offsets"] == 10_001 * limit // (8 * 30_001)
+    for name, full in (("offsets", offsets), ("token_ids", ids)):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(a, b) and a.dtype == np.float64
+        assert np.isin(a, full.astype(np.float64)).all()
+    # offsets ascend, so a sample at sorted positions ascends too
+    assert (np.diff(np.load(tmp_path / "a" / "offsets.npy")) >= 0).all()

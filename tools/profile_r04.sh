@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 D=$PWD/gpurun_out/prof_r04
 rm -rf $D; mkdir -p $D
 # (bench.py under rocprofv3 needs --no-pmc: it must not start child profilers from a profiled process)
-BENCH="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-pmc --min-seconds 0.05"
+BENCH="python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-pmc --min-seconds 0.05"
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- $BENCH > $D/bench_trace.json 2> $D/trace.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/fetch -- $BENCH > $D/bench_fetch.json 2> $D/fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/write -- $BENCH > $D/bench_write.json 2> $D/write.err

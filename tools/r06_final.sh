@@ -11,7 +11,7 @@ python -m pytest tests -m gpu -q 2>&1 | tail -8 > $D/gputest_full_suite.txt
  timeout 1800 python tests/soak/fuzz_igd.py 1000 2>&1 | tail -1
  timeout 900 python tests/soak/fuzz_igd.py big 12 2>&1 | tail -1
  timeout 1500 python tests/soak/fuzz_fragments.py 900 2>&1 | tail -1) > $D/soak_summary.txt 2>&1
-python bench.py > $D/bench_default_run.json 2> $D/bench_default_run.err
+python bench.py --full > $D/bench_default_run.json 2> $D/bench_default_run.err
 sh tools/profile_r06.sh > $D/profile_r06.log 2>&1
 python tools/collect_profiles.py gpurun_out/prof_r06 $D > $D/collect.log 2>&1
 cp gpurun_out/prof_r06/igd_chain/chain_summary.txt $D/igd_chain_summary.txt 2>/dev/null
