@@ -149,6 +149,16 @@ _HOST_SIG = {
     "gtars_regionset_count_overlaps": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, vp]),
     "gtars_regionset_any_overlaps": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, vp]),
     "gtars_regionset_find_overlaps": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, vp, pp, pu64]),
+    "gtars_regionset_reduce": (C.c_int, [vp, pp]),
+    "gtars_regionset_union": (C.c_int, [vp, vp, pp]),
+    "gtars_regionset_setdiff": (C.c_int, [vp, vp, pp]),
+    "gtars_regionset_intersect": (C.c_int, [vp, vp, pp]),
+    "gtars_regionset_jaccard": (C.c_int, [vp, vp, vp]),
+    "gtars_regionset_coverage": (C.c_int, [vp, vp, vp]),
+    "gtars_regionset_overlap_coefficient": (C.c_int, [vp, vp, vp]),
+    "gtars_regionset_closest": (C.c_int, [vp, vp, pp, pp, pp, pu64]),
+    "gtars_regionset_cluster": (C.c_int, [vp, u32, vp]),
+    "gtars_regionset_pairwise_jaccard": (C.c_int, [vp, u64, vp]),
     "gtars_tokenizer_from_auto": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_config": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_bed": (C.c_int, [cstr, pp]),

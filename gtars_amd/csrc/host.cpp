@@ -34,6 +34,7 @@
 #include "../../include/gtars_amd_host.h"
 #include "frag_device.h"
 #include "inflate_fast.h"
+#include "setops.h"
 
 namespace gtars {
 gtars_status fail(gtars_status st, const std::string &msg);
@@ -872,6 +873,226 @@ gtars_status gtars_regionset_find_overlaps(const gtars_regionset_t *self, const 
     const std::vector<uint32_t> qc = translate_chroms(self, other->chroms);
     return gtars_find_overlap_indices(ix.ix, qc.data(), self->starts.data(), self->ends.data(), self->size(),
                                       has_min, min_overlap, offsets, out_idx, out_n);
+}
+
+}  // extern "C"
+
+// ============================================================ RegionSet set algebra
+// IntervalSetOps and the structural operations of gtars-core (region_set.rs:675-1420), computed by setops.hip.  The
+// chromosomes of the sets a call involves are ranked in the bytewise order of their names (String's Ord: "chr10" <
+// "chr2"), so that sorting by rank is the reference's sort by name.  Result sets carry no rest, no header.
+
+namespace {
+
+struct RankSpace {
+    std::vector<std::string> names;  // rank -> name
+    std::unordered_map<std::string, uint32_t> rank;
+    void build(std::initializer_list<const gtars_regionset *> sets) {
+        std::set<std::string> all;
+        for (const gtars_regionset *s : sets)
+            for (const std::string &n : s->chroms.names) all.insert(n);
+        names.assign(all.begin(), all.end());
+        for (uint32_t r = 0; r < names.size(); ++r) rank.emplace(names[r], r);
+    }
+    void build_list(const gtars_regionset *const *sets, uint64_t n) {
+        std::set<std::string> all;
+        for (uint64_t k = 0; k < n; ++k)
+            for (const std::string &nm : sets[k]->chroms.names) all.insert(nm);
+        names.assign(all.begin(), all.end());
+        for (uint32_t r = 0; r < names.size(); ++r) rank.emplace(names[r], r);
+    }
+    // the set's regions as ranks of this space (GTARS_UNKNOWN_CHROM where the name is not in it)
+    std::vector<uint32_t> ranks_of(const gtars_regionset *s) const {
+        std::vector<uint32_t> map(s->chroms.names.size());
+        for (size_t i = 0; i < map.size(); ++i) {
+            auto it = rank.find(s->chroms.names[i]);
+            map[i] = it == rank.end() ? GTARS_UNKNOWN_CHROM : it->second;
+        }
+        std::vector<uint32_t> out(s->size());
+        for (size_t i = 0; i < out.size(); ++i) out[i] = map[s->chrom_ids[i]];
+        return out;
+    }
+    uint32_t size() const { return (uint32_t)names.size(); }
+};
+
+gtars::SetCols cols_of(const gtars_regionset *s, const std::vector<uint32_t> &ranks) {
+    return gtars::SetCols{ranks.data(), s->starts.data(), s->ends.data(), (uint64_t)s->size()};
+}
+
+// PyRegionSet::from_regionset: chromosome names from the ranks, rest None, no header
+gtars_regionset *regionset_from(const RankSpace &rs, const gtars::SetOut &o) {
+    auto *out = new gtars_regionset();
+    const size_t n = o.start.size();
+    out->chrom_ids.resize(n);
+    out->rest_off.assign(n, 0);
+    out->has_rest.assign(n, 0);
+    std::vector<uint32_t> id_of(rs.size(), GTARS_UNKNOWN_CHROM);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t &id = id_of[o.rank[i]];
+        if (id == GTARS_UNKNOWN_CHROM) id = out->chroms.get_or_add(rs.names[o.rank[i]]);
+        out->chrom_ids[i] = id;
+    }
+    out->starts = o.start;
+    out->ends = o.end;
+    return out;
+}
+
+template <class F>
+gtars_status set_result(const gtars_regionset *a, const gtars_regionset *b, gtars_regionset_t **out, F &&op) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!a || !b || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        RankSpace rs;
+        rs.build({a, b});
+        const std::vector<uint32_t> ra = rs.ranks_of(a), rb = rs.ranks_of(b);
+        gtars::SetOut o;
+        gtars_status st = op(cols_of(a, ra), cols_of(b, rb), rs.size(), o);
+        if (st) return st;
+        *out = regionset_from(rs, o);
+        return GTARS_OK;
+    });
+}
+
+gtars_status set_totals(const gtars_regionset *a, const gtars_regionset *b, bool want_diff, gtars::SetTotals &t) {
+    RankSpace rs;
+    rs.build({a, b});
+    const std::vector<uint32_t> ra = rs.ranks_of(a), rb = rs.ranks_of(b);
+    return gtars::setops_totals(cols_of(a, ra), cols_of(b, rb), rs.size(), want_diff, t);
+}
+
+}  // namespace
+
+extern "C" {
+
+gtars_status gtars_regionset_reduce(const gtars_regionset_t *rs, gtars_regionset_t **out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        RankSpace sp;
+        sp.build({rs});
+        const std::vector<uint32_t> r = sp.ranks_of(rs);
+        gtars::SetOut o;
+        gtars_status st = gtars::setops_reduce(cols_of(rs, r), sp.size(), o);
+        if (st) return st;
+        *out = regionset_from(sp, o);
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_union(const gtars_regionset_t *self, const gtars_regionset_t *other, gtars_regionset_t **out) {
+    return set_result(self, other, out, [](const gtars::SetCols &a, const gtars::SetCols &b, uint32_t n_rank, gtars::SetOut &o) {
+        std::vector<uint32_t> r(a.rank, a.rank + a.n), s(a.start, a.start + a.n), e(a.end, a.end + a.n);
+        r.insert(r.end(), b.rank, b.rank + b.n);
+        s.insert(s.end(), b.start, b.start + b.n);
+        e.insert(e.end(), b.end, b.end + b.n);
+        return gtars::setops_reduce(gtars::SetCols{r.data(), s.data(), e.data(), (uint64_t)r.size()}, n_rank, o);
+    });
+}
+
+gtars_status gtars_regionset_setdiff(const gtars_regionset_t *self, const gtars_regionset_t *other, gtars_regionset_t **out) {
+    return set_result(self, other, out, gtars::setops_setdiff);
+}
+
+gtars_status gtars_regionset_intersect(const gtars_regionset_t *self, const gtars_regionset_t *other, gtars_regionset_t **out) {
+    return set_result(self, other, out, gtars::setops_intersect);
+}
+
+gtars_status gtars_regionset_jaccard(const gtars_regionset_t *self, const gtars_regionset_t *other, double *out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!self || !other || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        gtars::SetTotals t;
+        gtars_status st = set_totals(self, other, false, t);
+        if (st) return st;
+        const uint32_t inter = t.a_bp + t.b_bp - t.union_bp;
+        *out = t.union_bp == 0 ? 0.0 : (double)inter / (double)t.union_bp;
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_coverage(const gtars_regionset_t *self, const gtars_regionset_t *other, double *out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!self || !other || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        gtars::SetTotals t;
+        gtars_status st = set_totals(self, other, true, t);
+        if (st) return st;
+        *out = t.a_bp == 0 ? 0.0 : 1.0 - ((double)t.diff_bp / (double)t.a_bp);
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_overlap_coefficient(const gtars_regionset_t *self, const gtars_regionset_t *other, double *out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!self || !other || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        gtars::SetTotals t;
+        gtars_status st = set_totals(self, other, false, t);
+        if (st) return st;
+        const uint32_t min_bp = std::min(t.a_bp, t.b_bp), inter = t.a_bp + t.b_bp - t.union_bp;
+        *out = min_bp == 0 ? 0.0 : (double)inter / (double)min_bp;
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_closest(const gtars_regionset_t *self, const gtars_regionset_t *other, uint64_t **out_self,
+                                     uint64_t **out_other, int64_t **out_dist, uint64_t *out_n) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!self || !other || !out_self || !out_other || !out_dist || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_self = *out_other = nullptr;
+        *out_dist = nullptr;
+        *out_n = 0;
+        RankSpace sp;
+        sp.build({other});  // a chromosome of self that other lacks maps to GTARS_UNKNOWN_CHROM: skipped
+        const std::vector<uint32_t> ra = sp.ranks_of(self), rb = sp.ranks_of(other);
+        std::vector<uint32_t> si, oi;
+        std::vector<int64_t> d;
+        gtars_status st = gtars::setops_closest(cols_of(self, ra), cols_of(other, rb), sp.size(), si, oi, d);
+        if (st) return st;
+        const size_t m = si.size();
+        uint64_t *ps = (uint64_t *)malloc(std::max<size_t>(m, 1) * 8), *po = (uint64_t *)malloc(std::max<size_t>(m, 1) * 8);
+        int64_t *pd = (int64_t *)malloc(std::max<size_t>(m, 1) * 8);
+        if (!ps || !po || !pd) {
+            free(ps);
+            free(po);
+            free(pd);
+            return fail(GTARS_ERR_INTERNAL, "out of host memory");
+        }
+        for (size_t i = 0; i < m; ++i) {
+            ps[i] = si[i];
+            po[i] = oi[i];
+            pd[i] = d[i];
+        }
+        *out_self = ps;
+        *out_other = po;
+        *out_dist = pd;
+        *out_n = m;
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_cluster(const gtars_regionset_t *rs, uint32_t max_gap, uint32_t *ids) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || (rs->size() && !ids)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        RankSpace sp;
+        sp.build({rs});
+        const std::vector<uint32_t> r = sp.ranks_of(rs);
+        return gtars::setops_cluster(cols_of(rs, r), sp.size(), max_gap, ids);
+    });
+}
+
+gtars_status gtars_regionset_pairwise_jaccard(const gtars_regionset_t *const *sets, uint64_t n, double *out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if ((n && (!sets || !out))) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        for (uint64_t k = 0; k < n; ++k)
+            if (!sets[k]) return fail(GTARS_ERR_INVALID_ARG, "NULL region set");
+        RankSpace sp;
+        sp.build_list(sets, n);
+        std::vector<std::vector<uint32_t>> ranks(n);
+        std::vector<gtars::SetCols> cols(n);
+        for (uint64_t k = 0; k < n; ++k) {
+            ranks[k] = sp.ranks_of(sets[k]);
+            cols[k] = cols_of(sets[k], ranks[k]);
+        }
+        return gtars::setops_pairwise_jaccard(cols, sp.size(), out);
+    });
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""``gtars.models`` mirror: ``Region`` and ``RegionSet``.
+"""``gtars.models`` mirror: ``Region``, ``RegionSet`` and ``RegionSetList``.
 
 Signature-compatible with the reference's pyo3 classes
 (gtars-python/src/models/region.rs, gtars-python/src/models/region_set.rs:69-478)
@@ -7,17 +7,25 @@ for the part of the surface that sits on the overlap hot path: construction
 ``count_overlaps / any_overlaps / find_overlaps / subset_by_overlaps`` which
 index ``other`` on the GPU (IndexedRegionSet::new -> AIList by default) and
 query ``self``.  BED parsing + sorting is done by the C++ host layer.
+
+The set algebra of region_set.rs:369-494 (reduce / union / setdiff / intersect_all, jaccard / coverage /
+overlap_coefficient, closest, cluster) and ``RegionSetList.pairwise_jaccard`` (region_set_list.rs:74-84) run
+on the GPU (csrc/setops.hip); results are bit-exact against the reference's semantics, ``closest`` with
+one pinned choice the reference leaves open (the walk starts at the first of several ``other`` regions that
+share the query's start).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Iterable, List, Optional, Sequence
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import KIND_AILIST, check, cstr_array, dec, lib, ptr, take_u32
+
+_U32_MAX = 0xFFFFFFFF
 
 
 class Region:
@@ -197,3 +205,99 @@ class RegionSet:
         counts = self.count_overlaps(other)
         regs = self.regions
         return RegionSet.from_regions([r for r, c in zip(regs, counts) if c > 0])
+
+    # -- set algebra (gtars-python/src/models/region_set.rs:369-494) -------------------
+    # Results are new sets with no rest, no header and strand "*" (PyRegionSet::from_regionset).
+    def _result(self, fn, *args) -> "RegionSet":
+        h = C.c_void_p()
+        check(fn(self._h, *args, C.byref(h)))
+        return RegionSet._from_handle(h)
+
+    def reduce(self) -> "RegionSet":
+        return self._result(lib.gtars_regionset_reduce)
+
+    def union(self, other: "RegionSet") -> "RegionSet":
+        return self._result(lib.gtars_regionset_union, other._h)
+
+    def setdiff(self, other: "RegionSet") -> "RegionSet":
+        return self._result(lib.gtars_regionset_setdiff, other._h)
+
+    def intersect_all(self, other: "RegionSet") -> "RegionSet":
+        return self._result(lib.gtars_regionset_intersect, other._h)
+
+    def _metric(self, fn, other: "RegionSet") -> float:
+        out = C.c_double()
+        check(fn(self._h, other._h, C.byref(out)))
+        return out.value
+
+    def jaccard(self, other: "RegionSet") -> float:
+        return self._metric(lib.gtars_regionset_jaccard, other)
+
+    def coverage(self, other: "RegionSet") -> float:
+        return self._metric(lib.gtars_regionset_coverage, other)
+
+    def overlap_coefficient(self, other: "RegionSet") -> float:
+        return self._metric(lib.gtars_regionset_overlap_coefficient, other)
+
+    def get_nucleotide_length(self) -> int:
+        """nucleotides_length(): the u32 sum of (u32)(end - start), wrapping as the reference's release build does"""
+        w = (self.ends - self.starts).astype(np.uint32)
+        return int(w.sum(dtype=np.uint64)) & _U32_MAX
+
+    def closest(self, other: "RegionSet") -> List[Tuple[int, int, int]]:
+        ps, po, pd = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = C.c_uint64()
+        check(lib.gtars_regionset_closest(self._h, other._h, C.byref(ps), C.byref(po), C.byref(pd), C.byref(n)))
+        cols = []
+        for p, t in ((ps, C.c_uint64), (po, C.c_uint64), (pd, C.c_int64)):
+            try:
+                cols.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(t)), shape=(n.value,)).tolist() if n.value else [])
+            finally:
+                if p.value:
+                    lib.gtars_free(p)
+        return list(zip(*cols))
+
+    def cluster(self, max_gap: int = 0) -> List[int]:
+        if not 0 <= int(max_gap) <= _U32_MAX:
+            raise OverflowError("max_gap must fit in u32")
+        out = np.zeros(len(self), dtype=np.uint32)
+        check(lib.gtars_regionset_cluster(self._h, int(max_gap), ptr(out)))
+        return out.tolist()
+
+
+class RegionSetList:
+    """gtars.models.RegionSetList -- an ordered collection of RegionSets (gtars-python/src/models/region_set_list.rs)."""
+
+    def __init__(self, sets: Iterable[RegionSet]):
+        self._sets: List[RegionSet] = list(sets)
+
+    def __len__(self) -> int:
+        return len(self._sets)
+
+    def __getitem__(self, index: int) -> RegionSet:
+        n = len(self._sets)
+        i = index + n if index < 0 else index
+        if not 0 <= i < n:
+            raise IndexError(f"Index {index} out of range for RegionSetList of length {n}")
+        return self._sets[i]
+
+    def __iter__(self):
+        return iter(list(self._sets))
+
+    def __repr__(self) -> str:
+        return f"RegionSetList with {len(self)} region sets."
+
+    def concat(self) -> RegionSet:
+        """every set's regions one after the other, in list order (no merging)"""
+        return RegionSet.from_regions([r for s in self._sets for r in s.regions])
+
+    def names(self) -> Optional[List[str]]:
+        return None
+
+    def pairwise_jaccard(self) -> List[List[float]]:
+        """N x N: M[i][j] = reduce(S_i).jaccard(reduce(S_j)), 1.0 on the diagonal; all pairs in one device pass"""
+        n = len(self._sets)
+        out = np.zeros((n, n), dtype=np.float64)
+        handles = (C.c_void_p * max(n, 1))(*[s._h for s in self._sets])
+        check(lib.gtars_regionset_pairwise_jaccard(C.cast(handles, C.c_void_p), n, ptr(out)))
+        return out.tolist()

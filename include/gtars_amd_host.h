@@ -66,6 +66,43 @@ gtars_status gtars_regionset_find_overlaps(const gtars_regionset_t *self,
                                            uint32_t **out_idx, uint64_t *out_n);
 
 /* ------------------------------------------------------------------------
+ * RegionSet set algebra (gtars-core/src/models/region_set.rs:675-1420, the
+ * IntervalSetOps trait; gtars-python/src/models/region_set.rs:369-494), on
+ * the current device.  Chromosome names order bytewise ("chr10" < "chr2").
+ * Result sets have no rest and no header.  Widths and bp totals are the
+ * reference's release-build u32 values: (u32)(end - start) summed modulo
+ * 2^32, intersection = a_bp + b_bp - union_bp in wrapping u32.
+ * ---------------------------------------------------------------------- */
+/* reduce (:675-707): stable sort by (chr, start), merge while next.start <= current.end */
+gtars_status gtars_regionset_reduce(const gtars_regionset_t *rs, gtars_regionset_t **out);
+/* union (:731-733): reduce(concat(self, other)) */
+gtars_status gtars_regionset_union(const gtars_regionset_t *self, const gtars_regionset_t *other,
+                                   gtars_regionset_t **out);
+/* IntervalSetOps::setdiff / intersect (:1229-1370): both sets reduced, one sweep per chromosome of self */
+gtars_status gtars_regionset_setdiff(const gtars_regionset_t *self, const gtars_regionset_t *other,
+                                     gtars_regionset_t **out);
+gtars_status gtars_regionset_intersect(const gtars_regionset_t *self, const gtars_regionset_t *other,
+                                       gtars_regionset_t **out);
+/* jaccard / coverage / overlap_coefficient (:1383-1415), 0.0 on a zero denominator */
+gtars_status gtars_regionset_jaccard(const gtars_regionset_t *self, const gtars_regionset_t *other, double *out);
+gtars_status gtars_regionset_coverage(const gtars_regionset_t *self, const gtars_regionset_t *other, double *out);
+gtars_status gtars_regionset_overlap_coefficient(const gtars_regionset_t *self, const gtars_regionset_t *other,
+                                                 double *out);
+/* closest (:1132-1225): (self_idx, other_idx, distance) in self order; regions of self on a chromosome
+ * other lacks are skipped; nothing when other is empty.  Where several regions of other share the
+ * query's start, the walk starts at the FIRST of them (the reference's binary_search_by_key leaves
+ * that index unspecified).  The three arrays: gtars_free each (*out_n entries). */
+gtars_status gtars_regionset_closest(const gtars_regionset_t *self, const gtars_regionset_t *other,
+                                     uint64_t **out_self_idx, uint64_t **out_other_idx, int64_t **out_dist,
+                                     uint64_t *out_n);
+/* cluster (:1093-1129): ids[gtars_regionset_len(rs)] in input order, counted up from 0 in (chr, start, end)
+ * order; a new cluster on a chromosome change or where start > cluster_end.saturating_add(max_gap) */
+gtars_status gtars_regionset_cluster(const gtars_regionset_t *rs, uint32_t max_gap, uint32_t *ids);
+/* RegionSetList::pairwise_jaccard (gtars-genomicdist/src/region_set_list_ops.rs:20-45): out[i * n + j] =
+ * reduce(S_i).jaccard(reduce(S_j)), 1.0 on the diagonal; every pair in one device pass */
+gtars_status gtars_regionset_pairwise_jaccard(const gtars_regionset_t *const *sets, uint64_t n, double *out);
+
+/* ------------------------------------------------------------------------
  * Tokenizer  (gtars-tokenizers/src/tokenizer.rs:36-279, universe/mod.rs,
  * config.rs, utils/mod.rs:34-99, utils/special_tokens.rs)
  * ---------------------------------------------------------------------- */
