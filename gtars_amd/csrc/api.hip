@@ -239,39 +239,6 @@ void prof_note_fact(const char *name) {
     if (g_prof_on) g_prof_entries[prof_entry(name)].launches += 1;
 }
 
-// -------------------------------------------------------------- device bufs
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    gtars_status upload(const std::vector<T> &h) {
-        n = h.size();
-        GT_HIP(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T) + 32));  // + slack: the IGD sweep stages whole 16-byte vectors
-        if (n) GT_HIP(hipMemcpy(p, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
-        return GTARS_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-struct ScopedDev {
-    void *p = nullptr;
-    ~ScopedDev() {
-        if (p) (void)hipFree(p);
-    }
-    gtars_status alloc(size_t bytes) {
-        GT_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16)));
-        return GTARS_OK;
-    }
-    template <class T>
-    T *as() {
-        return (T *)p;
-    }
-};
-
 // the calling thread's current device for the scope: `want`, and what it was before again afterwards
 struct DeviceScope {
     int before = -1;
@@ -346,15 +313,13 @@ static gtars_status sorted_perm_device(const std::vector<u32> &chrom, const std:
     const u32 n = (u32)chrom.size();
     perm.resize(n);
     if (!n) return GTARS_OK;
-    ScopedDev buf;
-    gtars_status st = buf.alloc((size_t)n * 4 * 4);
-    if (st) return st;
-    u32 *dc = buf.as<u32>(), *d1 = dc + n, *d2 = d1 + n, *dp = d2 + n;
+    DevBuf<u32> buf;
+    GT_TRY(buf.alloc((size_t)n * 4));
+    u32 *dc = buf.p, *d1 = dc + n, *d2 = d1 + n, *dp = d2 + n;
     GT_HIP(hipMemcpy(dc, chrom.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     GT_HIP(hipMemcpy(d1, k1.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     if (k2) GT_HIP(hipMemcpy(d2, k2->data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    st = device_sort_perm(dc, d1, k2 ? d2 : nullptr, n, n_chrom, dp, nullptr);
-    if (st) return st;
+    GT_TRY(device_sort_perm(dc, d1, k2 ? d2 : nullptr, n, n_chrom, dp, nullptr));
     GT_HIP(hipMemcpy(perm.data(), dp, (size_t)n * 4, hipMemcpyDeviceToHost));
     return GTARS_OK;
 }
@@ -384,7 +349,7 @@ struct gtars_index {
     // intersect_all -- does not depend on the enumeration order, so those calls run on the companion's LDS kernels; only
     // enumeration in AIList::find order (ailist.rs:153-178, 238-263) stays on this index.  flat_pos[p'] = this index's stored
     // position of the companion's stored position p' (for the device bitmap of gtars_mark_overlapped_device).
-    gtars_index *flat = nullptr;
+    std::unique_ptr<gtars_index> flat;
     DevBuf<u32> flat_pos;
     // ... and, round 5, enumeration in AIList::find order as well: the companion's LDS tokenizer writes the hits as its own stored
     // positions, and k_ailist_reorder sorts every query's hits by ail_key[position] -- the hit's mirrored position in THIS index's
@@ -462,8 +427,8 @@ struct gtars_igd {
     u64 n = 0;
     int device = 0;  // the device the database was built on (and everything built lazily later lives on)
     // Databases with records longer than the piece length keep a second index of PIECES for the min_overlap == 1 counts (see
-    // build_pieces_view below); null otherwise.  Owned.
-    gtars_igd *pieces = nullptr;
+    // build_pieces_view below); null otherwise.
+    std::unique_ptr<gtars_igd> pieces;
     // host copy of the stored starts / ends: filled at build by the host-sort path, on first use
     // (total_records / export) after a device build
     mutable std::vector<i32> h_starts, h_ends;
@@ -515,7 +480,9 @@ struct gtars_igd {
             for (u32 p = off[c]; p < off[c + 1]; ++p) mx = std::max(mx, h_ends[p]);
             nt[c] = off[c + 1] > off[c] ? (mx - 1) / 16384 + 1 : 0;
         }
-        if ((st = chrom_ntiles.upload(nt))) return st;
+        DevBuf<i32> d;
+        GT_TRY(d.upload(nt));
+        chrom_ntiles = std::move(d);
         ntiles_ready = true;
         return GTARS_OK;
     }
@@ -531,20 +498,15 @@ struct gtars_igd {
     gtars_status ensure_pme() const {
         std::lock_guard<std::mutex> lk(pme_mu);
         if (pme_ready || n == 0) return GTARS_OK;
-        ScopedDev ws;
         const size_t wsb = igd_pme_ws_bytes((u32)n);
-        gtars_status st = ws.alloc(wsb);
-        if (st) return st;
-        i32 *p = nullptr;
-        GT_HIP(hipMalloc((void **)&p, (size_t)n * 4 + 32));
-        st = igd_build_pme_file(view(), p, ws.p, wsb, nullptr);
+        DevBuf<u8> ws;
+        GT_TRY(ws.alloc(wsb));
+        DevBuf<i32> pme;
+        GT_TRY(pme.alloc(n));
+        gtars_status st = igd_build_pme_file(view(), pme.p, ws.p, wsb, nullptr);
         hipError_t e = hipDeviceSynchronize();
-        if (st || e != hipSuccess) {
-            (void)hipFree(p);
-            return st ? st : fail(GTARS_ERR_HIP, "pme_file build failed");
-        }
-        pme_file.p = p;
-        pme_file.n = n;
+        if (st || e != hipSuccess) return st ? st : fail(GTARS_ERR_HIP, "pme_file build failed");
+        pme_file = std::move(pme);
         pme_ready = true;
         return GTARS_OK;
     }
@@ -559,20 +521,17 @@ struct gtars_igd {
                 values_unique = 1;
             } else {
                 const u32 n32 = (u32)n;
-                ScopedDev buf;
+                DevBuf<u8> buf;
                 const size_t wsb = radix_sort_ws_bytes(n32);
-                gtars_status st = buf.alloc((size_t)n32 * 16 + wsb + 64);
-                if (st) return st;
-                u32 *k0 = buf.as<u32>(), *v0 = k0 + n32, *k1 = v0 + n32, *v1 = k1 + n32;
+                GT_TRY(buf.alloc((size_t)n32 * 16 + wsb + 64));
+                u32 *k0 = (u32 *)buf.p, *v0 = k0 + n32, *k1 = v0 + n32, *v1 = k1 + n32;
                 void *ws = (void *)(v1 + n32);
                 u32 *d_dup = (u32 *)((char *)ws + wsb);
                 GT_HIP(hipMemcpy(k0, values.p, (size_t)n32 * 4, hipMemcpyDeviceToDevice));
                 GT_HIP(hipMemset(d_dup, 0, 4));
                 int res = 0;
-                st = radix_sort_pairs(k0, v0, k1, v1, n32, 0, 32, ws, wsb, &res, nullptr);
-                if (st) return st;
-                st = launch_has_adjacent_equal(res ? k1 : k0, n32, d_dup, nullptr);
-                if (st) return st;
+                GT_TRY(radix_sort_pairs(k0, v0, k1, v1, n32, 0, 32, ws, wsb, &res, nullptr));
+                GT_TRY(launch_has_adjacent_equal(res ? k1 : k0, n32, d_dup, nullptr));
                 u32 h = 1;
                 GT_HIP(hipMemcpy(&h, d_dup, 4, hipMemcpyDeviceToHost));
                 values_unique = h ? 0 : 1;
@@ -622,33 +581,24 @@ struct gtars_igd {
         if ((st = launch_igd_tile_bounds(view(), tile_first.p, tile_cnt.p, tile_chrom.p, n_tiles, tile_bnd.p, nullptr))) return st;
         if (n_tiles && n_files <= 65535) {
             // one pass over the database: prefix maxima, u16 file ids, search tables (what the sweep streams with the records)
-            GT_HIP(hipMalloc((void **)&tile_pm.p, (size_t)n * 4 + 32));  // + slack: staged as whole 16-byte vectors
-            tile_pm.n = n;
-            GT_HIP(hipMalloc((void **)&tile_files16.p, ((size_t)n + 1) / 2 * 4 + 32));
-            tile_files16.n = n;
-            GT_HIP(hipMalloc((void **)&tile_tab.p, (size_t)n_tiles * IGD_TILE_TAB_WORDS * 4));
-            tile_tab.n = (size_t)n_tiles * IGD_TILE_TAB_WORDS;
-            if ((st = launch_igd_tile_tables(view(), tile_first.p, tile_cnt.p, tile_chrom.p, tile_carry.p, n_tiles, tile_pm.p, tile_files16.p,
-                                             tile_tab.p, nullptr)))
-                return st;
+            GT_TRY(tile_pm.alloc(n));
+            GT_TRY(tile_files16.alloc(((size_t)n + 1) & ~(size_t)1));  // (u16 pairs: whole words)
+            GT_TRY(tile_tab.alloc((size_t)n_tiles * IGD_TILE_TAB_WORDS));
+            GT_TRY(launch_igd_tile_tables(view(), tile_first.p, tile_cnt.p, tile_chrom.p, tile_carry.p, n_tiles, tile_pm.p, tile_files16.p,
+                                          tile_tab.p, nullptr));
             // the rank-histogram form's blocks (sorted ends + eranks: 6 bytes per staged record, ~7 per record).  Not for a pieces
             // view (its continuation rule is not a rank difference) and not under GTARS_IGD_NO_RANK_TABLES (tests / A-B runs)
             if (!piece_flags && n_files <= 16384 && !cfg_flag("GTARS_IGD_NO_RANK_TABLES")) {
                 const size_t slots = (size_t)n_tiles * IGD_TILE_BLOCK;
-                hipError_t e = hipMalloc((void **)&tile_ends_sorted.p, slots * 4 + 32);
-                if (e == hipSuccess) e = hipMalloc((void **)&tile_erank.p, slots * 2 + 32);
-                if (e == hipSuccess) e = hipMalloc((void **)&tile_tab_r.p, (size_t)n_tiles * IGD_TILE_TABR_WORDS * 4);
-                if (e == hipSuccess) {
-                    tile_ends_sorted.n = tile_erank.n = slots;
-                    tile_tab_r.n = (size_t)n_tiles * IGD_TILE_TABR_WORDS;
-                    if ((st = launch_igd_tile_tables_rank(view(), tile_first.p, tile_cnt.p, tile_chrom.p, n_tiles, tile_ends_sorted.p,
-                                                          tile_erank.p, tile_tab_r.p, nullptr)))
-                        return st;
+                if (tile_ends_sorted.try_alloc(slots) == hipSuccess && tile_erank.try_alloc(slots) == hipSuccess &&
+                    tile_tab_r.try_alloc((size_t)n_tiles * IGD_TILE_TABR_WORDS) == hipSuccess) {
+                    GT_TRY(launch_igd_tile_tables_rank(view(), tile_first.p, tile_cnt.p, tile_chrom.p, n_tiles, tile_ends_sorted.p,
+                                                       tile_erank.p, tile_tab_r.p, nullptr));
                 } else {
                     (void)hipGetLastError();  // out of device memory: the database keeps the walked form
-                    tile_ends_sorted.release();
-                    tile_erank.release();
-                    tile_tab_r.release();
+                    tile_ends_sorted.reset();
+                    tile_erank.reset();
+                    tile_tab_r.reset();
                 }
             }
         }
@@ -812,7 +762,7 @@ static gtars_status gtars_index_build_impl(const uint32_t *chrom, const uint32_t
         for (u64 i = 0; i < n; ++i) perm[fillp[chrom[i]]++] = (u32)i;
     }
 
-    auto *ix = new gtars_index();
+    std::unique_ptr<gtars_index> ix(new gtars_index());
     ix->kind = kind;
     ix->n_chrom = n_chrom;
     ix->n = n;
@@ -827,11 +777,7 @@ static gtars_status gtars_index_build_impl(const uint32_t *chrom, const uint32_t
         if (dev_sort) {
             // K1: (chrom, start, end, input order) by stable radix passes on the device
             std::vector<u32> hc(chrom, chrom + n), hs(start, start + n), he(end, end + n);
-            gtars_status s1 = sorted_perm_device(hc, hs, &he, n_chrom, perm);
-            if (s1) {
-                delete ix;
-                return s1;
-            }
+            GT_TRY(sorted_perm_device(hc, hs, &he, n_chrom, perm));
         }
         for (u32 c = 0; c < n_chrom; ++c) {
             // Bits::build: stable sort by (start, end) (bits.rs:105, interval.rs:18-31)
@@ -1140,22 +1086,19 @@ static gtars_status gtars_index_build_impl(const uint32_t *chrom, const uint32_t
     if (!st) st = ix->chrom_aux.upload(ix->h_chrom_aux);
     if (!st) st = ix->chrom_sub.upload(ix->h_chrom_sub);
     if (!st) st = ix->sub_off.upload(ix->h_sub_off);
-    if (st) {
-        gtars_index_free(ix);
-        return st;
-    }
+    if (st) return st;
     if (kind == GTARS_KIND_AILIST && !single_sublist && n > 0) {
         // nested sub-lists: the flat companion (see gtars_index::flat) -- optional: an index without it answers every call on
         // the generic kernels, as before
-        gtars_index *fl = nullptr;
-        if (gtars_index_build_impl(chrom, start, end, val, n, n_chrom, GTARS_KIND_BITS, &fl) == GTARS_OK && fl && fl->has_accel &&
-            tokenize_lds_supported(fl->accel())) {
+        gtars_index *built = nullptr;
+        (void)gtars_index_build_impl(chrom, start, end, val, n, n_chrom, GTARS_KIND_BITS, &built);  // (*out stays null on failure)
+        std::unique_ptr<gtars_index> fl(built);
+        if (fl && fl->has_accel && tokenize_lds_supported(fl->accel())) {
             std::vector<u32> inv(n), map(n);
             for (u64 p = 0; p < n; ++p) inv[ix->h_rows[p]] = (u32)p;
             for (u64 p = 0; p < n; ++p) map[p] = inv[fl->h_rows[p]];
             if (ix->flat_pos.upload(map) == GTARS_OK) {
-                ix->flat = fl;
-                fl = nullptr;
+                ix->flat = std::move(fl);
                 // mirrored positions: for stored position a of sub-list [s0, s1): key = s0 + (s1 - 1 - a)
                 std::vector<u32> mirror(n), key(n), val(n);
                 for (u32 c = 0; c < n_chrom; ++c)
@@ -1183,45 +1126,18 @@ static gtars_status gtars_index_build_impl(const uint32_t *chrom, const uint32_t
                     ix->ail_depth = span > 0 ? bp / span : 0;
                 }
                 if (ix->ail_key.upload(key) != GTARS_OK || ix->ail_val.upload(val) != GTARS_OK) {
-                    ix->ail_key.release();  // (out of device memory: enumeration stays on the generic kernel)
-                    ix->ail_val.release();
+                    ix->ail_key.reset();  // (out of device memory: enumeration stays on the generic kernel)
+                    ix->ail_val.reset();
                 }
             }
         }
-        if (fl) gtars_index_free(fl);
         set_error("");
     }
-    *out = ix;
+    *out = ix.release();
     return GTARS_OK;
 }
 
-void gtars_index_free(gtars_index_t *ix) {
-    if (!ix) return;
-    gtars_index_free(ix->flat);
-    ix->flat_pos.release();
-    ix->ail_key.release();
-    ix->ail_val.release();
-    ix->starts.release();
-    ix->ends.release();
-    ix->vals.release();
-    ix->max_ends.release();
-    ix->chrom_off.release();
-    ix->chrom_aux.release();
-    ix->chrom_sub.release();
-    ix->sub_off.release();
-    ix->acc_rec2.release();
-    ix->acc_rec4.release();
-    ix->acc_rec8.release();
-    ix->acc_idc.release();
-    ix->acc_idc_pos.release();
-    ix->acc_blk_first.release();
-    ix->acc_chrom_iv_end.release();
-    ix->acc_lut.release();
-    ix->ends_sorted.release();
-    ix->acc_qkeys.release();
-    ix->acc_chrom_tab.release();
-    delete ix;
-}
+void gtars_index_free(gtars_index_t *ix) { delete ix; }
 
 uint64_t gtars_index_len(const gtars_index_t *ix) { return ix ? ix->n : 0; }
 uint32_t gtars_index_n_chrom(const gtars_index_t *ix) { return ix ? ix->n_chrom : 0; }
@@ -1289,7 +1205,7 @@ static bool sweep_wanted(const gtars_index *ix, const EnumOut &out) {
 // index (gtars_index::flat), or null (generic kernels)
 static const gtars_index *lds_target(const gtars_index *ix) {
     if (use_lds_path(ix)) return ix;
-    if (ix->flat && use_lds_path(ix->flat)) return ix->flat;
+    if (ix->flat && use_lds_path(ix->flat.get())) return ix->flat.get();
     return nullptr;
 }
 static gtars_status count_dispatch(const gtars_index *ix, const u32 *qc, const u32 *qs, const u32 *qe, u64 nq, int has_min,
@@ -1312,7 +1228,7 @@ static gtars_status run_fused(const gtars_index *ix, const u32 *qc, const u32 *q
     if (use_lds_path(ix) && !out.starts && !out.ends)
         return launch_tokenize_lds(ix->accel(), qc, qs, qe, nq, has_min, min_overlap, out, ws, ws_bytes, ep, s, nullptr, nullptr,
                                    ix->kind == GTARS_KIND_AILIST);
-    if (ix->kind == GTARS_KIND_AILIST && ix->flat && ix->ail_key.p && ix->ail_val.p && use_lds_path(ix->flat) && !out.starts && !out.ends &&
+    if (ix->kind == GTARS_KIND_AILIST && ix->flat && ix->ail_key.p && ix->ail_val.p && use_lds_path(ix->flat.get()) && !out.starts && !out.ends &&
         !cfg_flag("GTARS_AILIST_NO_REORDER") && ix->ail_depth < (double)cfg_int("GTARS_AILIST_REORDER_MAX_DEPTH", 6)) {
         // a nested AIList index: the hit SET from the flat companion's LDS tokenizer (its stored positions, Bits order), the ORDER
         // by k_ailist_reorder -- one more pass over the offsets and ids instead of the one-thread-per-query generic kernel
@@ -1475,15 +1391,14 @@ gtars_status gtars_count_overlaps_device(const gtars_index_t *ix, const uint32_t
 // host-pointer helpers -------------------------------------------------------
 
 struct DevQueries {
-    ScopedDev buf;
+    DevBuf<u8> buf;
     u32 *c = nullptr, *s = nullptr, *e = nullptr;
     gtars_status upload(const u32 *qc, const u32 *qs, const u32 *qe, u64 nq) {
         const size_t pad = ((size_t)nq * 4 + 255) & ~(size_t)255;
-        gtars_status st = buf.alloc(pad * 3);
-        if (st) return st;
+        GT_TRY(buf.alloc(pad * 3));
         c = (u32 *)buf.p;
-        s = (u32 *)((char *)buf.p + pad);
-        e = (u32 *)((char *)buf.p + 2 * pad);
+        s = (u32 *)(buf.p + pad);
+        e = (u32 *)(buf.p + 2 * pad);
         if (nq) {
             GT_HIP(hipMemcpy(c, qc, nq * 4, hipMemcpyHostToDevice));
             GT_HIP(hipMemcpy(s, qs, nq * 4, hipMemcpyHostToDevice));
@@ -1507,14 +1422,13 @@ static gtars_status enumerate_to_host(const gtars_index_t *ix, const u32 *qc, co
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d_off, d_ws;
-    st = d_off.alloc((nq + 1) * 8);
-    if (st) return st;
+    DevBuf<u64> d_off;
+    DevBuf<u8> d_ws;
+    GT_TRY(d_off.alloc(nq + 1));
     const size_t wsb = fused_ws_bytes(ix, nq);
-    st = d_ws.alloc(wsb);
-    if (st) return st;
+    GT_TRY(d_ws.alloc(wsb));
     // pass 1: offsets + total only (no payload buffers)
-    EnumOut o1{d_off.as<u64>(), nullptr, nullptr, nullptr, 0};
+    EnumOut o1{d_off.p, nullptr, nullptr, nullptr, 0};
     ScanEpoch ep;
     u64 h = 0;
     st = run_fused_sync(ix, q.c, q.s, q.e, nq, has_min, min_overlap, o1, d_ws.p, wsb, ep, nullptr, &h);
@@ -1523,27 +1437,26 @@ static gtars_status enumerate_to_host(const gtars_index_t *ix, const u32 *qc, co
     if (out_n) *out_n = h;
     const int nout = (out_val ? 1 : 0) + (out_start ? 1 : 0) + (out_end ? 1 : 0);
     if (nout) {
-        ScopedDev d_out;
+        DevBuf<u8> d_out;
         const size_t pad = ((size_t)h * 4 + 255) & ~(size_t)255;
-        st = d_out.alloc(pad * 3);
-        if (st) return st;
+        GT_TRY(d_out.alloc(pad * 3));
         u32 *dv = out_val ? (u32 *)d_out.p : nullptr;
-        u32 *ds = out_start ? (u32 *)((char *)d_out.p + pad) : nullptr;
-        u32 *de = out_end ? (u32 *)((char *)d_out.p + 2 * pad) : nullptr;
+        u32 *ds = out_start ? (u32 *)(d_out.p + pad) : nullptr;
+        u32 *de = out_end ? (u32 *)(d_out.p + 2 * pad) : nullptr;
         if (use_lds_path(ix)) {
             // the fused tokenizer once more, this time emitting the hits' stored positions (reference order, Bits or
             // AIList), and one gather of the payload columns by position -- instead of the generic per-query fill pass
-            ScopedDev d_pos;
-            if ((st = d_pos.alloc(pad))) return st;
-            EnumOut o2{d_off.as<u64>(), d_pos.as<u32>(), nullptr, nullptr, h};
+            DevBuf<u32> d_pos;
+            GT_TRY(d_pos.alloc(pad / 4));
+            EnumOut o2{d_off.p, d_pos.p, nullptr, nullptr, h};
             st = launch_tokenize_lds(ix->accel_pos(), q.c, q.s, q.e, nq, has_min, min_overlap, o2, d_ws.p, wsb, ep, nullptr, nullptr,
                                      nullptr, ix->kind == GTARS_KIND_AILIST);
             if (st) return st;
-            st = launch_gather_hits(ix->view(), d_pos.as<u32>(), h, dv, ds, de, nullptr);
+            st = launch_gather_hits(ix->view(), d_pos.p, h, dv, ds, de, nullptr);
             if (st) return st;
             GT_HIP(hipDeviceSynchronize());
         } else {
-            st = launch_fill(ix->view(), ix->kind, q.c, q.s, q.e, nq, has_min, min_overlap, d_off.as<u64>(), dv, ds,
+            st = launch_fill(ix->view(), ix->kind, q.c, q.s, q.e, nq, has_min, min_overlap, d_off.p, dv, ds,
                              de, nullptr);
             if (st) return st;
             GT_HIP(hipDeviceSynchronize());
@@ -1926,10 +1839,9 @@ gtars_status gtars_count_overlaps(const gtars_index_t *ix, const uint32_t *qc, c
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d;
-    st = d.alloc(nq * 4);
-    if (st) return st;
-    st = count_dispatch(ix, q.c, q.s, q.e, nq, has_min, min_overlap, d.as<u32>(), nullptr, nullptr);
+    DevBuf<u32> d;
+    GT_TRY(d.alloc(nq));
+    st = count_dispatch(ix, q.c, q.s, q.e, nq, has_min, min_overlap, d.p, nullptr, nullptr);
     if (st) return st;
     GT_HIP(hipMemcpy(counts, d.p, nq * 4, hipMemcpyDeviceToHost));
     return GTARS_OK;
@@ -1941,8 +1853,9 @@ static gtars_status bits_count_prepare(const gtars_index_t *ix) {
     if (ix->ends_ready) return GTARS_OK;
     std::vector<u32> e(ix->h_ends);
     for (u32 c = 0; c < ix->n_chrom; ++c) std::sort(e.begin() + ix->h_chrom_off[c], e.begin() + ix->h_chrom_off[c + 1]);
-    gtars_status st = ix->ends_sorted.upload(e);
-    if (st) return st;
+    DevBuf<u32> d;
+    GT_TRY(d.upload(e));
+    ix->ends_sorted = std::move(d);
     ix->ends_ready = true;
     return GTARS_OK;
 }
@@ -1971,10 +1884,9 @@ gtars_status gtars_bits_count(const gtars_index_t *ix, const uint32_t *qc, const
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d;
-    st = d.alloc(nq * 8);
-    if (st) return st;
-    st = launch_bits_count(ix->view(), ix->ends_sorted.p, q.c, q.s, q.e, nq, d.as<u64>(), nullptr);
+    DevBuf<u64> d;
+    GT_TRY(d.alloc(nq));
+    st = launch_bits_count(ix->view(), ix->ends_sorted.p, q.c, q.s, q.e, nq, d.p, nullptr);
     if (st) return st;
     GT_HIP(hipMemcpy(counts, d.p, nq * 8, hipMemcpyDeviceToHost));
     return GTARS_OK;
@@ -1993,10 +1905,9 @@ gtars_status gtars_any_overlaps(const gtars_index_t *ix, const uint32_t *qc, con
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d;
-    st = d.alloc(nq);
-    if (st) return st;
-    st = count_dispatch(ix, q.c, q.s, q.e, nq, has_min, min_overlap, nullptr, d.as<u8>(), nullptr);
+    DevBuf<u8> d;
+    GT_TRY(d.alloc(nq));
+    st = count_dispatch(ix, q.c, q.s, q.e, nq, has_min, min_overlap, nullptr, d.p, nullptr);
     if (st) return st;
     GT_HIP(hipMemcpy(out, d.p, nq, hipMemcpyDeviceToHost));
     return GTARS_OK;
@@ -2027,39 +1938,38 @@ gtars_status gtars_find_overlap_indices(const gtars_index_t *ix, const uint32_t 
     *out_n = 0;
     st = require_device();
     if (st) return st;
-    if (lds_target(ix) == ix->flat && ix->flat) ix = ix->flat;  // (sorted unique source rows: the same from either order)
+    if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (sorted unique source rows: the same from either order)
     // Every source row that shares a hit's coordinates is itself a hit (same
     // overlap, same filter), so "all rows sharing coordinates, sorted, dedup"
     // (indexed_region_set.rs:246-263) == the hit source indices, sorted.
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d_off, d_ws, d_cnt, d_off2;
-    if ((st = d_off.alloc((nq + 1) * 8))) return st;
-    if ((st = d_off2.alloc((nq + 1) * 8))) return st;
-    if ((st = d_cnt.alloc(nq * 4))) return st;
+    DevBuf<u64> d_off, d_off2;
+    DevBuf<u32> d_cnt;
+    DevBuf<u8> d_ws;
+    GT_TRY(d_off.alloc(nq + 1));
+    GT_TRY(d_off2.alloc(nq + 1));
+    GT_TRY(d_cnt.alloc(nq));
     const size_t wsb = std::max(fused_ws_bytes(ix, nq), scan_ws_bytes(nq));
-    if ((st = d_ws.alloc(wsb))) return st;
-    EnumOut o1{d_off.as<u64>(), nullptr, nullptr, nullptr, 0};
+    GT_TRY(d_ws.alloc(wsb));
+    EnumOut o1{d_off.p, nullptr, nullptr, nullptr, 0};
     ScanEpoch ep;
     u64 h = 0;
     st = run_fused_sync(ix, q.c, q.s, q.e, nq, has_min, min_overlap, o1, d_ws.p, wsb, ep, nullptr, &h);
     if (st) return st;
-    ScopedDev d_val;
-    if ((st = d_val.alloc(h * 4))) return st;
+    DevBuf<u32> d_val;
+    GT_TRY(d_val.alloc(h));
     if (use_lds_path(ix)) {  // the fused tokenizer writes the source indices itself (the order inside a query does not matter here)
-        EnumOut o2{d_off.as<u64>(), d_val.as<u32>(), nullptr, nullptr, h};
+        EnumOut o2{d_off.p, d_val.p, nullptr, nullptr, h};
         st = launch_tokenize_lds(ix->accel(), q.c, q.s, q.e, nq, has_min, min_overlap, o2, d_ws.p, wsb, ep, nullptr, nullptr, nullptr,
                                  ix->kind == GTARS_KIND_AILIST);
     } else {
-        st = launch_fill(ix->view(), ix->kind, q.c, q.s, q.e, nq, has_min, min_overlap, d_off.as<u64>(),
-                         d_val.as<u32>(), nullptr, nullptr, nullptr);
+        st = launch_fill(ix->view(), ix->kind, q.c, q.s, q.e, nq, has_min, min_overlap, d_off.p, d_val.p, nullptr, nullptr, nullptr);
     }
     if (st) return st;
-    st = launch_sort_unique_segments(d_val.as<u32>(), d_off.as<u64>(), nq, d_cnt.as<u32>(), nullptr);
-    if (st) return st;
-    st = launch_scan_u32_to_u64(d_cnt.as<u32>(), nq, d_off2.as<u64>(), d_ws.p, wsb, nullptr);
-    if (st) return st;
+    GT_TRY(launch_sort_unique_segments(d_val.p, d_off.p, nq, d_cnt.p, nullptr));
+    GT_TRY(launch_scan_u32_to_u64(d_cnt.p, nq, d_off2.p, d_ws.p, wsb, nullptr));
     // compact on the host side of the copy: segments are already contiguous
     // when nothing was de-duplicated (the overwhelmingly common case)
     std::vector<u64> off1(nq + 1), off2(nq + 1);
@@ -2116,9 +2026,9 @@ static gtars_status subset_positions(const gtars_index_t *ix, const u32 *qc, con
     gtars_status st = q.upload(qc, qs, qe, nq);
     if (st) return st;
     const size_t words = ((size_t)ix->n + 31) / 32;
-    ScopedDev d_mark;
-    if ((st = d_mark.alloc(words * 4))) return st;
-    st = gtars_mark_overlapped_device(ix, q.c, q.s, q.e, nq, has_min, min_overlap, d_mark.as<u32>(), nullptr);
+    DevBuf<u32> d_mark;
+    GT_TRY(d_mark.alloc(words));
+    st = gtars_mark_overlapped_device(ix, q.c, q.s, q.e, nq, has_min, min_overlap, d_mark.p, nullptr);
     if (st) return st;
     std::vector<u32> mark(words);
     GT_HIP(hipMemcpy(mark.data(), d_mark.p, words * 4, hipMemcpyDeviceToHost));
@@ -2150,7 +2060,7 @@ static gtars_status gtars_subset_by_overlaps_impl(const gtars_index_t *ix, const
         bool operator==(const Trip &o) const { return c == o.c && s == o.s && e == o.e; }
     };
     std::vector<Trip> hits;
-    if (lds_target(ix) == ix->flat && ix->flat) ix = ix->flat;  // (a set of coordinates: the same from either stored order)
+    if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (a set of coordinates: the same from either stored order)
     if (use_lds_path(ix)) {
         std::vector<u32> pos;
         if ((st = subset_positions(ix, qc, qs, qe, nq, has_min, min_overlap, pos))) return st;
@@ -2217,7 +2127,7 @@ static gtars_status gtars_subset_source_indices_impl(const gtars_index_t *ix, co
     *out_n = 0;
     if ((st = require_device())) return st;
     std::vector<u32> vals;
-    if (lds_target(ix) == ix->flat && ix->flat) ix = ix->flat;  // (a set of source rows: the same from either stored order)
+    if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (a set of source rows: the same from either stored order)
     if (use_lds_path(ix)) {
         std::vector<u32> pos;
         if ((st = subset_positions(ix, qc, qs, qe, nq, has_min, min_overlap, pos))) return st;
@@ -2286,46 +2196,41 @@ static gtars_status gtars_igd_build_core(const uint32_t *chrom, const int32_t *s
             ++kept;
         }
         for (u32 c = 0; c < n_chrom; ++c) hoff[c + 1] += hoff[c];
-        auto *g = new gtars_igd();
+        std::unique_ptr<gtars_igd> g(new gtars_igd());
         (void)hipGetDevice(&g->device);
         g->piece_flags = piece_flags;
         g->n_chrom = n_chrom;
         g->n_files = n_files;
         g->n = kept;
-        auto bail = [&](gtars_status e) {
-            gtars_igd_free(g);
-            return e;
-        };
-        ScopedDev in, ws;
         const u32 n32 = (u32)n;
         // (a pieces view serves counts only: no values column, here or on the host path below)
         const bool with_values = !piece_flags;
-        if ((st = in.alloc((size_t)n * 4 * (with_values ? 6 : 5)))) return bail(st);
-        u32 *d_kc = in.as<u32>(), *d_s = d_kc + n, *d_e = d_s + n, *d_f = d_e + n, *d_v = d_f + n, *d_perm = with_values ? d_v + n : d_v;
+        DevBuf<u32> in;
+        GT_TRY(in.alloc((size_t)n * (with_values ? 6 : 5)));
+        u32 *d_kc = in.p, *d_s = d_kc + n, *d_e = d_s + n, *d_f = d_e + n, *d_v = d_f + n, *d_perm = with_values ? d_v + n : d_v;
         if (hipMemcpy(d_kc, kc.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_s, start, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_e, end, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_f, file_idx, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
             (!with_values ? hipSuccess
                           : value ? hipMemcpy(d_v, value, n * 4, hipMemcpyHostToDevice) : hipMemset(d_v, 0, n * 4)) != hipSuccess)
-            return bail(fail(GTARS_ERR_HIP, "IGD build: upload failed"));
+            return fail(GTARS_ERR_HIP, "IGD build: upload failed");
         // chromosome-major, then start, ties in insertion order (finalize: stable sort by start, igd.rs:157-167);
         // kept starts are >= 0, so u32 order == i32 order
         const size_t ws_bytes = device_sort_perm_ws_bytes(n32);
-        if ((st = ws.alloc(ws_bytes))) return bail(st);
-        if ((st = device_sort_perm_ws(d_kc, d_s, nullptr, n32, n_chrom + 1, d_perm, ws.p, ws_bytes, nullptr))) return bail(st);
-        const size_t kb = std::max<u64>(kept, 1) * 4 + 32;  // + slack: the sweep stages whole 16-byte vectors
-        if (hipMalloc((void **)&g->starts.p, kb) != hipSuccess || hipMalloc((void **)&g->ends.p, kb) != hipSuccess ||
-            hipMalloc((void **)&g->files.p, kb) != hipSuccess || (with_values && hipMalloc((void **)&g->values.p, kb) != hipSuccess))
-            return bail(fail(GTARS_ERR_HIP, "IGD build: device allocation failed"));
-        g->starts.n = g->ends.n = g->files.n = kept;
-        g->values.n = with_values ? kept : 0;
+        DevBuf<u8> ws;
+        GT_TRY(ws.alloc(ws_bytes));
+        GT_TRY(device_sort_perm_ws(d_kc, d_s, nullptr, n32, n_chrom + 1, d_perm, ws.p, ws_bytes, nullptr));
+        GT_TRY(g->starts.alloc(kept));
+        GT_TRY(g->ends.alloc(kept));
+        GT_TRY(g->files.alloc(kept));
+        if (with_values) GT_TRY(g->values.alloc(kept));
         const u32 k32 = (u32)kept;
-        if ((st = device_gather_u32(d_s, d_perm, k32, (u32 *)g->starts.p, nullptr))) return bail(st);
-        if ((st = device_gather_u32(d_e, d_perm, k32, (u32 *)g->ends.p, nullptr))) return bail(st);
-        if ((st = device_gather_u32(d_f, d_perm, k32, g->files.p, nullptr))) return bail(st);
-        if (with_values && (st = device_gather_u32(d_v, d_perm, k32, (u32 *)g->values.p, nullptr))) return bail(st);
-        if (hipDeviceSynchronize() != hipSuccess) return bail(fail(GTARS_ERR_HIP, "IGD build: device sort failed"));
+        if ((st = device_gather_u32(d_s, d_perm, k32, (u32 *)g->starts.p, nullptr))) return st;
+        if ((st = device_gather_u32(d_e, d_perm, k32, (u32 *)g->ends.p, nullptr))) return st;
+        if ((st = device_gather_u32(d_f, d_perm, k32, g->files.p, nullptr))) return st;
+        if (with_values && (st = device_gather_u32(d_v, d_perm, k32, (u32 *)g->values.p, nullptr))) return st;
+        if (hipDeviceSynchronize() != hipSuccess) return fail(GTARS_ERR_HIP, "IGD build: device sort failed");
         std::vector<u32> tf, tc, tch;
         for (u32 c = 0; c < n_chrom; ++c)
             for (u32 p = hoff[c]; p < hoff[c + 1]; p += IGD_TILE_RECORDS) {
@@ -2339,26 +2244,25 @@ static gtars_status gtars_igd_build_core(const uint32_t *chrom, const int32_t *s
         if (!st) st = g->tile_chrom.upload(tch);
         if (!st) st = g->chrom_off.upload(hoff);
         if (!st) st = g->chrom_maxlen.upload(hml);
-        if (st) return bail(st);
+        if (st) return st;
         {
             // tile_carry: per-tile maximum end on the device, exclusive running maximum per chromosome on the host
             std::vector<i32> tmax(g->n_tiles, 0), carry(g->n_tiles, 0);
-            ScopedDev d_tmax;
-            if ((st = d_tmax.alloc((size_t)g->n_tiles * 4))) return bail(st);
-            if ((st = launch_igd_tile_max_end(g->ends.p, g->tile_first.p, g->tile_cnt.p, g->n_tiles, d_tmax.as<i32>(), nullptr)))
-                return bail(st);
+            DevBuf<i32> d_tmax;
+            GT_TRY(d_tmax.alloc(g->n_tiles));
+            GT_TRY(launch_igd_tile_max_end(g->ends.p, g->tile_first.p, g->tile_cnt.p, g->n_tiles, d_tmax.p, nullptr));
             if (g->n_tiles && hipMemcpy(tmax.data(), d_tmax.p, (size_t)g->n_tiles * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return bail(fail(GTARS_ERR_HIP, "IGD build: tile maxima readback failed"));
+                return fail(GTARS_ERR_HIP, "IGD build: tile maxima readback failed");
             i32 run = 0;
             for (u32 t = 0; t < g->n_tiles; ++t) {
                 if (t == 0 || tch[t] != tch[t - 1]) run = 0;
                 carry[t] = run;
                 run = std::max(run, tmax[t]);
             }
-            if ((st = g->tile_carry.upload(carry))) return bail(st);
+                GT_TRY(g->tile_carry.upload(carry));
         }
-        if ((st = g->finish_tiles(tch))) return bail(st);
-        *out = g;
+        GT_TRY(g->finish_tiles(tch));
+        *out = g.release();
         return GTARS_OK;
     }
     // ---- small builds: host stable sort
@@ -2376,7 +2280,7 @@ static gtars_status gtars_igd_build_core(const uint32_t *chrom, const int32_t *s
         if (chrom[a] != chrom[b]) return chrom[a] < chrom[b];
         return start[a] < start[b];
     });
-    auto *g = new gtars_igd();
+    std::unique_ptr<gtars_igd> g(new gtars_igd());
     (void)hipGetDevice(&g->device);
     g->piece_flags = piece_flags;
     g->n_chrom = n_chrom;
@@ -2425,11 +2329,8 @@ static gtars_status gtars_igd_build_core(const uint32_t *chrom, const int32_t *s
     if (!st) st = g->chrom_off.upload(hoff);
     if (!st) st = g->chrom_maxlen.upload(hml);
     if (!st) st = g->finish_tiles(tch);
-    if (st) {
-        gtars_igd_free(g);
-        return st;
-    }
-    *out = g;
+    if (st) return st;
+    *out = g.release();
     return GTARS_OK;
 }
 
@@ -2515,7 +2416,7 @@ static gtars_status build_pieces_view(gtars_igd *g, const uint32_t *chrom, const
     gtars_igd *pv = nullptr;
     gtars_status st = gtars_igd_build_core(pc.data(), ps.data(), pe.data(), nullptr, pf.data(), k, g->n_chrom, g->n_files, true, &pv);
     if (st) return st;
-    g->pieces = pv;
+    g->pieces.reset(pv);
     return GTARS_OK;
 }
 
@@ -2550,40 +2451,10 @@ static gtars_status gtars_igd_build_impl(const uint32_t *chrom, const int32_t *s
 static const gtars_igd *igd_count_target(const gtars_igd *g, int32_t min_overlap, int binary) {
     if (!g->pieces || min_overlap != 1) return g;
     if (binary && cfg_get("GTARS_IGD_NO_PME")) return g;
-    return g->pieces;
+    return g->pieces.get();
 }
 
-void gtars_igd_free(gtars_igd_t *g) {
-    if (!g) return;
-    gtars_igd_free(g->pieces);
-    g->starts.release();
-    g->ends.release();
-    g->values.release();
-    g->files.release();
-    g->chrom_off.release();
-    g->chrom_maxlen.release();
-    g->tile_first.release();
-    g->tile_cnt.release();
-    g->tile_chrom.release();
-    g->tile_carry.release();
-    g->tile_bnd.release();
-    g->chrom_tile_off.release();
-    g->tile_pm.release();
-    g->tile_files16.release();
-    g->tile_tab.release();
-    g->tile_ends_sorted.release();
-    g->tile_erank.release();
-    g->tile_tab_r.release();
-    g->chrom_ntiles.release();
-    g->route_lut.release();
-    g->route_base.release();
-    g->route_len.release();
-    g->route_flut.release();
-    g->route_kq.release();
-    g->route_fbase.release();
-    g->pme_file.release();
-    delete g;
-}
+void gtars_igd_free(gtars_igd_t *g) { delete g; }
 
 uint64_t gtars_igd_len(const gtars_igd_t *g) { return g ? g->n : 0; }
 uint32_t gtars_igd_n_files(const gtars_igd_t *g) { return g ? g->n_files : 0; }
@@ -2738,11 +2609,9 @@ gtars_status gtars_igd_count_sets(const gtars_igd_t *g, const uint32_t *qc, cons
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d;
-    const size_t cells = (size_t)std::max<u32>(g->n_files, 1) * n_sets;
-    st = d.alloc(cells * 8);
-    if (st) return st;
-    st = gtars_igd_count_sets_device(g, q.c, q.s, q.e, set_off, n_sets, min_overlap, binary, d.as<u64>(), nullptr);
+    DevBuf<u64> d;
+    GT_TRY(d.alloc((size_t)std::max<u32>(g->n_files, 1) * n_sets));
+    st = gtars_igd_count_sets_device(g, q.c, q.s, q.e, set_off, n_sets, min_overlap, binary, d.p, nullptr);
     if (st) return st;
     if (g->n_files) GT_HIP(hipMemcpy(hits, d.p, (size_t)g->n_files * n_sets * 8, hipMemcpyDeviceToHost));
     return GTARS_OK;
@@ -2759,10 +2628,9 @@ gtars_status gtars_igd_count(const gtars_igd_t *g, const uint32_t *qc, const uin
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d;
-    st = d.alloc((size_t)std::max<u32>(g->n_files, 1) * 8);
-    if (st) return st;
-    st = gtars_igd_count_device(g, q.c, q.s, q.e, nq, min_overlap, binary, d.as<u64>(), nullptr);
+    DevBuf<u64> d;
+    GT_TRY(d.alloc(std::max<u32>(g->n_files, 1)));
+    st = gtars_igd_count_device(g, q.c, q.s, q.e, nq, min_overlap, binary, d.p, nullptr);
     if (st) return st;
     if (g->n_files) GT_HIP(hipMemcpy(hits, d.p, (size_t)g->n_files * 8, hipMemcpyDeviceToHost));
     return GTARS_OK;
@@ -2781,12 +2649,11 @@ gtars_status gtars_igd_count_per_query(const gtars_igd_t *g, const uint32_t *qc,
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d;
-    st = d.alloc(nq * 4);
-    if (st) return st;
+    DevBuf<u32> d;
+    GT_TRY(d.alloc(nq));
     bool uniq = false;
     if ((st = g->ensure_values_unique(&uniq))) return st;
-    st = launch_igd_count_per_query(g->view(), q.c, q.s, q.e, nq, min_overlap, d.as<u32>(), uniq, nullptr);
+    st = launch_igd_count_per_query(g->view(), q.c, q.s, q.e, nq, min_overlap, d.p, uniq, nullptr);
     if (st) return st;
     GT_HIP(hipMemcpy(counts, d.p, nq * 4, hipMemcpyDeviceToHost));
     return GTARS_OK;
@@ -2807,25 +2674,23 @@ gtars_status gtars_igd_find_pairs(const gtars_igd_t *g, const uint32_t *qc, cons
     DevQueries q;
     st = q.upload(qc, qs, qe, nq);
     if (st) return st;
-    ScopedDev d_cnt, d_off, d_ws;
-    if ((st = d_cnt.alloc(nq * 4))) return st;
-    if ((st = d_off.alloc((nq + 1) * 8))) return st;
+    DevBuf<u32> d_cnt;
+    DevBuf<u64> d_off;
+    DevBuf<u8> d_ws;
+    GT_TRY(d_cnt.alloc(nq));
+    GT_TRY(d_off.alloc(nq + 1));
     const size_t wsb = scan_ws_bytes(nq);
-    if ((st = d_ws.alloc(wsb))) return st;
+    GT_TRY(d_ws.alloc(wsb));
     bool uniq = false;
     if ((st = g->ensure_values_unique(&uniq))) return st;
-    st = launch_igd_count_per_query(g->view(), q.c, q.s, q.e, nq, min_overlap, d_cnt.as<u32>(), uniq, nullptr);
-    if (st) return st;
-    st = launch_scan_u32_to_u64(d_cnt.as<u32>(), nq, d_off.as<u64>(), d_ws.p, wsb, nullptr);
-    if (st) return st;
+    GT_TRY(launch_igd_count_per_query(g->view(), q.c, q.s, q.e, nq, min_overlap, d_cnt.p, uniq, nullptr));
+    GT_TRY(launch_scan_u32_to_u64(d_cnt.p, nq, d_off.p, d_ws.p, wsb, nullptr));
     u64 h = 0;
-    GT_HIP(hipMemcpy(&h, d_off.as<u64>() + nq, 8, hipMemcpyDeviceToHost));
-    ScopedDev d_q, d_s;
-    if ((st = d_q.alloc(h * 4))) return st;
-    if ((st = d_s.alloc(h * 4))) return st;
-    st = launch_igd_fill_pairs(g->view(), q.c, q.s, q.e, nq, min_overlap, d_off.as<u64>(), d_q.as<u32>(),
-                               d_s.as<u32>(), uniq, nullptr);
-    if (st) return st;
+    GT_HIP(hipMemcpy(&h, d_off.p + nq, 8, hipMemcpyDeviceToHost));
+    DevBuf<u32> d_q, d_s;
+    GT_TRY(d_q.alloc(h));
+    GT_TRY(d_s.alloc(h));
+    GT_TRY(launch_igd_fill_pairs(g->view(), q.c, q.s, q.e, nq, min_overlap, d_off.p, d_q.p, d_s.p, uniq, nullptr));
     *out_q = host_alloc<u32>(h);
     *out_s = host_alloc<u32>(h);
     if (!*out_q || !*out_s) return fail(GTARS_ERR_INTERNAL, "out of host memory");

@@ -3,12 +3,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <string>
 #include <vector>
 
 #include "../../include/gtars_amd.h"
+#include "frag_device.h"
 
 namespace gtars {
 
@@ -29,7 +31,101 @@ gtars_status hip_fail(hipError_t e, const char *what, const char *file, int line
         if (_e != hipSuccess) return ::gtars::hip_fail(_e, #expr, __FILE__, __LINE__); \
     } while (0)
 
+// returns the status of `expr` from the calling function unless it is GTARS_OK
+#define GT_TRY(expr)                                  \
+    do {                                              \
+        const gtars_status gt_try_ = (expr);          \
+        if (gt_try_) return gt_try_;                  \
+    } while (0)
+
 gtars_status require_device();
+
+// ---- owning device memory -----------------------------------------------------
+// n elements of T on the current device, freed with the buffer; move-only.  Every allocation is at least
+// max(n, 1) * sizeof(T) + 32 bytes and never fewer than 256: kernels stage whole 16-byte vectors, so the last vector
+// a kernel loads from an array may reach past its last element (the IGD sweep's records, for one).
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p, n = o.n;
+            o.p = nullptr, o.n = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr, n = 0;
+    }
+    // records no error: for optional allocations whose failure the caller handles
+    hipError_t try_alloc(size_t count) {
+        reset();
+        const size_t bytes = std::max<size_t>(std::max<size_t>(count, 1) * sizeof(T) + 32, 256);
+        hipError_t e = hipMalloc((void **)&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        n = count;
+        return hipSuccess;
+    }
+    gtars_status alloc(size_t count) {
+        GT_HIP(try_alloc(count));
+        return GTARS_OK;
+    }
+    gtars_status upload(const std::vector<T> &h) {
+        GT_TRY(alloc(h.size()));
+        if (n) GT_HIP(hipMemcpy(p, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
+        return GTARS_OK;
+    }
+    // stream-ordered: `h` must stay valid until the copy has run
+    gtars_status upload(const T *h, size_t count, hipStream_t st) {
+        GT_TRY(alloc(count));
+        if (n) GT_HIP(hipMemcpyAsync(p, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return GTARS_OK;
+    }
+};
+
+// ---- one call's stream and the memory its queued work uses -----------------------
+// The destructor drains the stream; the members (device buffers, host blocks) are destroyed after its body, so whichever
+// way a call returns, no copy or kernel still in flight can touch memory that went back to the runtime or the pinned pool.
+struct StreamFrame {
+    hipStream_t st;
+    std::vector<DevBuf<u8>> bufs;
+    std::vector<HostBlock> blocks;
+    explicit StreamFrame(hipStream_t s) : st(s) {}
+    StreamFrame(const StreamFrame &) = delete;
+    StreamFrame &operator=(const StreamFrame &) = delete;
+    ~StreamFrame() { (void)hipStreamSynchronize(st); }
+    // (n elements of T as n * sizeof(T) bytes: the same allocation as a DevBuf<T>)
+    template <class T>
+    gtars_status alloc(T **out, size_t n) {
+        bufs.emplace_back();
+        GT_TRY(bufs.back().alloc(n * sizeof(T)));
+        *out = (T *)bufs.back().p;
+        return GTARS_OK;
+    }
+    template <class T>
+    gtars_status upload(T **out, const T *h, size_t n, hipStream_t s) {
+        bufs.emplace_back();
+        GT_TRY(bufs.back().upload((const u8 *)h, n * sizeof(T), s));
+        *out = (T *)bufs.back().p;
+        return GTARS_OK;
+    }
+    // host memory for the stream's copies (pinned when the pool has it); null: out of host memory
+    void *host(size_t bytes) {
+        blocks.emplace_back();
+        return blocks.back().alloc(bytes) ? blocks.back().p : nullptr;
+    }
+};
 
 // ---- environment switches -----------------------------------------------------
 // Every GTARS_* variable is read ONCE, into an immutable snapshot taken at first use (a getenv per call raced with a host

@@ -527,21 +527,6 @@ const CrcTables &crc_tables_host() {
     return t;
 }
 
-struct DevMem {
-    void *p = nullptr;
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-    gtars_status alloc(size_t bytes) {
-        GT_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-        return GTARS_OK;
-    }
-    template <class T>
-    T *as() const {
-        return (T *)p;
-    }
-};
-
 // pieces of a workspace, 256-byte aligned
 struct Carve {
     char *p = nullptr;
@@ -583,7 +568,9 @@ void build_table(const std::vector<std::pair<const char *, u32>> &keys, const st
 }  // namespace
 
 struct FragChroms {
-    DevMem slots, keys, crc;  // the chromosome table; the CRC-32 tables (device copy, made with it)
+    DevBuf<FragSlot> slots;  // the chromosome table
+    DevBuf<unsigned char> keys;
+    DevBuf<CrcTables> crc;  // the CRC-32 tables (device copy, made with it)
     u32 n_slots = 0;
     int device = 0;
 };
@@ -603,12 +590,11 @@ gtars_status frag_chroms_create(const std::vector<std::string> &names, FragChrom
     build_table(keys, values, slots, blob);
     std::unique_ptr<FragChroms> c(new FragChroms());
     GT_HIP(hipGetDevice(&c->device));
-    if ((st = c->slots.alloc(slots.size() * sizeof(FragSlot)))) return st;
-    if ((st = c->keys.alloc(blob.size() + 16))) return st;
-    GT_HIP(hipMemcpy(c->slots.p, slots.data(), slots.size() * sizeof(FragSlot), hipMemcpyHostToDevice));
+    GT_TRY(c->slots.upload(slots));
+    GT_TRY(c->keys.alloc(blob.size()));
     if (!blob.empty()) GT_HIP(hipMemcpy(c->keys.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
     c->n_slots = (u32)slots.size();
-    if ((st = c->crc.alloc(sizeof(CrcTables)))) return st;
+    GT_TRY(c->crc.alloc(1));
     GT_HIP(hipMemcpy(c->crc.p, &crc_tables_host(), sizeof(CrcTables), hipMemcpyHostToDevice));
     *out = c.release();
     return GTARS_OK;
@@ -731,11 +717,6 @@ static gtars_status wait_stream(hipStream_t st) {
     GT_HIP(hipEventSynchronize(ev));
     return GTARS_OK;
 }
-#define GT_WAIT(st_)                                   \
-    do {                                               \
-        const gtars_status ws_ = wait_stream(st_);     \
-        if (ws_) return ws_;                           \
-    } while (0)
 
 gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms, const std::vector<FragFileIn> &files, uint32_t n_clusters,
                               uint32_t unk_id, FragWaveOut &out) {
@@ -778,13 +759,10 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
     }
     // Whatever way this call ends, the stream is idle when it does (round-5 advisor): copies and kernels queued on `st` read and
     // write pinned pool blocks (the files' texts, `staging`, `mailbox`) and pooled workspaces that go back to their pools when
-    // this frame unwinds -- an early error return with work still in flight would let a loader thread inflate the next file
-    // into a block the DMA engine is still reading.  The success paths have waited already: a second wait on an idle stream
-    // returns at once.
-    struct DrainStream {
-        hipStream_t s;
-        ~DrainStream() { (void)hipStreamSynchronize(s); }
-    } drain_on_exit{st};
+    // this call returns -- an early error return with work still in flight would let a loader thread inflate the next file
+    // into a block the DMA engine is still reading.  The frame drains `st` before it gives its own blocks back.  The success
+    // paths have waited already: a second wait on an idle stream returns at once.
+    StreamFrame fr(st);
     const u32 n_bytes = (u32)total;
     const u32 n_chunks = (n_bytes + FP_CHUNK - 1) / FP_CHUNK;
     // ---- text + tables to the device ----
@@ -809,28 +787,28 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
     for (const FragFileIn &f : files) n_members += f.n_members;
     const size_t stage_slots = pad(3 * m1 * 4), stage_keys = stage_slots + pad(total_slots * sizeof(FragSlot)),
                  stage_mem = stage_keys + pad(total_keys + 16), stage_bytes = stage_mem + pad(n_members * sizeof(CrcMember)) + 256;
-    HostBlock staging;
-    if (!staging.alloc(stage_bytes)) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    char *staging = (char *)fr.host(stage_bytes);
+    if (!staging) return fail(GTARS_ERR_INTERNAL, "out of host memory");
     // the small answers (line count, error file, per-cluster and per-file counts) land in a pinned mailbox: a copy into pageable
     // memory is synchronous, and that wait polls
-    HostBlock mailbox;
     const size_t mb_coff = 64, mb_written = mb_coff + pad(((size_t)n_clusters + 1) * 4), mb_fline = mb_written + pad((size_t)n_files * 4),
                  mb_cbase = mb_fline + pad(m1 * 4), mb_bytes = mb_cbase + pad(((size_t)n_clusters + 1) * 8);
-    if (!mailbox.alloc(mb_bytes)) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    volatile u32 *mb_words = (volatile u32 *)mailbox.p;  // [0] line count, [1] error file, [2] wide flag
-    u32 *file_off = (u32 *)staging.p, *slot_off = file_off + m1, *key_off = slot_off + m1;
+    char *mailbox = (char *)fr.host(mb_bytes);
+    if (!mailbox) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    volatile u32 *mb_words = (volatile u32 *)mailbox;  // [0] line count, [1] error file, [2] wide flag
+    u32 *file_off = (u32 *)staging, *slot_off = file_off + m1, *key_off = slot_off + m1;
     file_off[0] = slot_off[0] = key_off[0] = 0;
     for (u32 f = 0; f < n_files; ++f) {
         file_off[f + 1] = file_off[f] + (u32)files[f].n;
         slot_off[f + 1] = slot_off[f] + files[f].n_slots;
         key_off[f + 1] = key_off[f] + files[f].n_key_bytes;
         if (files[f].n) GT_HIP(hipMemcpyAsync(d_text.as<char>() + file_off[f], files[f].text, files[f].n, hipMemcpyHostToDevice, st));
-        if (files[f].n_slots) memcpy((char *)staging.p + stage_slots + (size_t)slot_off[f] * sizeof(FragSlot), files[f].slots, (size_t)files[f].n_slots * sizeof(FragSlot));
-        if (files[f].n_key_bytes) memcpy((char *)staging.p + stage_keys + key_off[f], files[f].keys, files[f].n_key_bytes);
+        if (files[f].n_slots) memcpy(staging + stage_slots + (size_t)slot_off[f] * sizeof(FragSlot), files[f].slots, (size_t)files[f].n_slots * sizeof(FragSlot));
+        if (files[f].n_key_bytes) memcpy(staging + stage_keys + key_off[f], files[f].keys, files[f].n_key_bytes);
     }
     for (u32 f = 0; f <= n_files; ++f) out.slot_off[f] = slot_off[f];
-    if (total_slots) GT_HIP(hipMemcpyAsync(d_slots.as<FragSlot>(), (char *)staging.p + stage_slots, total_slots * sizeof(FragSlot), hipMemcpyHostToDevice, st));
-    if (total_keys) GT_HIP(hipMemcpyAsync(d_keys.as<char>(), (char *)staging.p + stage_keys, total_keys, hipMemcpyHostToDevice, st));
+    if (total_slots) GT_HIP(hipMemcpyAsync(d_slots.as<FragSlot>(), staging + stage_slots, total_slots * sizeof(FragSlot), hipMemcpyHostToDevice, st));
+    if (total_keys) GT_HIP(hipMemcpyAsync(d_keys.as<char>(), staging + stage_keys, total_keys, hipMemcpyHostToDevice, st));
     GT_HIP(hipMemsetAsync(d_text.as<char>() + n_bytes, 0, (size_t)std::max<u32>(n_chunks, 1) * FP_CHUNK + 64 - n_bytes, st));
     // meta: file_off | slot_off | key_off | file_line [n_files + 1 each] | n_written [n_files] | err_file | coff [n_clusters + 1]
     u32 *d_file_off = d_meta.as<u32>(), *d_slot_off = d_file_off + m1, *d_key_off = d_slot_off + m1, *d_file_line = d_key_off + m1;
@@ -839,7 +817,7 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
     GT_HIP(hipMemsetAsync(d_written, 0, (size_t)n_files * 4, st));
     GT_HIP(hipMemsetAsync(d_err, 0xFF, 4, st));
     // ---- the gzip members' CRC-32 (the host threads inflated them raw) ----
-    CrcMember *h_mem_p = (CrcMember *)((char *)staging.p + stage_mem);
+    CrcMember *h_mem_p = (CrcMember *)(staging + stage_mem);
     size_t h_mem_n = 0;
     u32 crc_chunks = 0, crc_groups = 0;
     for (u32 f = 0; f < n_files; ++f)
@@ -859,7 +837,7 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
         CrcMember *d_mem = cc.take<CrcMember>(h_mem_n);
         u32 *d_part = cc.take<u32>(crc_chunks), *d_gpart = cc.take<u32>(crc_groups);
         GT_HIP(hipMemcpyAsync(d_mem, h_mem_p, h_mem_n * sizeof(CrcMember), hipMemcpyHostToDevice, st));
-        const CrcTables *d_tb = chroms->crc.as<CrcTables>();
+        const CrcTables *d_tb = chroms->crc.p;
         const u32 nm = (u32)h_mem_n;
         if (crc_chunks)
             hipLaunchKernelGGL(k_crc_chunks, dim3((crc_chunks + 255) / 256), dim3(256), 0, st, d_text.as<unsigned char>(), (const CrcMember *)d_mem, nm,
@@ -870,7 +848,7 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
         hipLaunchKernelGGL(k_crc_members, dim3((nm + 63) / 64), dim3(64), 0, st, (const CrcMember *)d_mem, nm, d_tb, (const u32 *)d_gpart, d_err);
         GT_HIP(hipGetLastError());
     }
-    GT_WAIT(st);
+    GT_TRY(wait_stream(st));
     const double t1 = now_s();
     out.t_h2d = t1 - t0;
     // ---- line ends ----
@@ -882,11 +860,11 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
         hipLaunchKernelGGL(k_frag_scan_chunks, dim3(1), dim3(1024), 0, st, (const u32 *)d_cnt, n_chunks, d_base);
         GT_HIP(hipMemcpyAsync((void *)&mb_words[0], d_base + n_chunks, 4, hipMemcpyDeviceToHost, st));
         GT_HIP(hipMemcpyAsync((void *)&mb_words[1], d_err, 4, hipMemcpyDeviceToHost, st));
-        GT_WAIT(st);
+        GT_TRY(wait_stream(st));
         n_lines = mb_words[0];
     } else {
         GT_HIP(hipMemcpyAsync((void *)&mb_words[1], d_err, 4, hipMemcpyDeviceToHost, st));
-        GT_WAIT(st);
+        GT_TRY(wait_stream(st));
     }
     if (!n_lines) {  // (no text at all: a member's CRC may still be wrong)
         const u32 h_err0 = mb_words[1];
@@ -908,8 +886,8 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
                            (const u32 *)d_file_off, n_files, d_file_line);
         // ---- parse: per-line columns key | chrom | start | end ----
         u32 *d_key = d_cols.as<u32>(), *d_qc = d_key + n_lines, *d_qs = d_qc + n_lines, *d_qe = d_qs + n_lines;
-        FragTables tb{d_slots.as<FragSlot>(), d_keys.as<unsigned char>(), d_slot_off, d_key_off, chroms->slots.as<FragSlot>(),
-                      chroms->keys.as<unsigned char>(), chroms->n_slots};
+        FragTables tb{d_slots.as<FragSlot>(), d_keys.as<unsigned char>(), d_slot_off, d_key_off, chroms->slots.p,
+                      chroms->keys.p, chroms->n_slots};
         const u32 no_key = (u32)total_slots;  // (< 2^32: the tables of a wave's files are 16 bytes a slot, of < 4 GiB of text)
         const u32 n_parse_wg = (n_lines + FP_TPB - 1) / FP_TPB;
         hipLaunchKernelGGL(k_frag_parse, dim3(n_parse_wg), dim3(FP_TPB), 0, st, d_text.as<unsigned char>(), (const u32 *)d_line_end, n_lines,
@@ -925,12 +903,12 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
         if ((s = radix_sort_pairs(d_key, d_v0, d_k1, d_v1, n_lines, 0, key_bits, ws, sort_ws, &res, st))) return s;
         const u32 *sk = res ? d_k1 : d_key, *sp = res ? d_v1 : d_v0;
         hipLaunchKernelGGL(k_frag_lower_bound, dim3(1), dim3(64), 0, st, sk, n_lines, no_key, d_coff);
-        const u32 *h_written = (const u32 *)((char *)mailbox.p + mb_written), *h_file_line = (const u32 *)((char *)mailbox.p + mb_fline);
+        const u32 *h_written = (const u32 *)(mailbox + mb_written), *h_file_line = (const u32 *)(mailbox + mb_fline);
         GT_HIP(hipMemcpyAsync((void *)&mb_words[3], d_coff, 4, hipMemcpyDeviceToHost, st));
         GT_HIP(hipMemcpyAsync((void *)h_written, d_written, (size_t)n_files * 4, hipMemcpyDeviceToHost, st));
         GT_HIP(hipMemcpyAsync((void *)h_file_line, d_file_line, m1 * 4, hipMemcpyDeviceToHost, st));
         GT_HIP(hipMemcpyAsync((void *)&mb_words[1], d_err, 4, hipMemcpyDeviceToHost, st));
-        GT_WAIT(st);
+        GT_TRY(wait_stream(st));
         const u32 h_err = mb_words[1];
         const double t2 = now_s();
         out.t_parse = t2 - t1;
@@ -961,18 +939,16 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
             hipLaunchKernelGGL(k_frag_gather, dim3((n + 255) / 256), dim3(256), 0, st, sp, n, (const u32 *)d_qc, (const u32 *)d_qs,
                                (const u32 *)d_qe, oc, os, oe);
             GT_HIP(hipGetLastError());
-            GT_WAIT(st);
+            GT_TRY(wait_stream(st));
             const double t3 = now_s();
             out.t_group = t3 - t2;
             // ---- tokenize where the columns lie: one fused pass with a guessed capacity, the fill pass when it was short ----
-            DevMem bigger;  // (only when the guess was short: a hit-heavy universe)
             u32 *d_ids_p = d_ids_ws;
             s = gtars_tokenize_device(ix, oc, os, oe, n, (uint64_t *)d_off, d_ids_p, cap, &h, st);
             if (s == GTARS_ERR_CAPACITY) {
-                if ((s = bigger.alloc(h * 4))) return s;
-                d_ids_p = bigger.as<u32>();
+                GT_TRY(fr.alloc(&d_ids_p, h));  // (only when the guess was short: a hit-heavy universe)
                 if ((s = gtars_fill_device_n(ix, oc, os, oe, n, (const uint64_t *)d_off, d_ids_p, h, st))) return s;
-                GT_WAIT(st);
+                GT_TRY(wait_stream(st));
             } else if (s) {
                 return s;
             }
@@ -993,13 +969,13 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
             if (!out.run_start.alloc((size_t)no_key + 1) || !out.run_line.alloc((size_t)no_key + 1)) return fail(GTARS_ERR_INTERNAL, "out of host memory");
             GT_HIP(hipMemcpyAsync(out.run_start.get(), d_run_start, ((size_t)no_key + 1) * 4, hipMemcpyDeviceToHost, st));
             GT_HIP(hipMemcpyAsync(out.run_line.get(), d_run_line, ((size_t)no_key + 1) * 4, hipMemcpyDeviceToHost, st));
-            GT_WAIT(st);
+            GT_TRY(wait_stream(st));
             const u32 n_ids = mb_words[2];
             out.n_ids = n_ids;
             // (the results land in pinned blocks: one DMA each, no staging by the runtime)
             if (!out.ids.alloc(std::max<u32>(n_ids, 1))) return fail(GTARS_ERR_INTERNAL, "out of host memory");
             GT_HIP(hipMemcpyAsync(out.ids.get(), d_ids2, (size_t)n_ids * 4, hipMemcpyDeviceToHost, st));
-            GT_WAIT(st);
+            GT_TRY(wait_stream(st));
             out.t_d2h = now_s() - t4;
         }
     }

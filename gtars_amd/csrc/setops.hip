@@ -36,41 +36,6 @@ constexpr u32 SO_PAIR_CHUNK = 2048;  // regions of the smaller set per work item
 constexpr u32 SO_MAX_N = 0xFFFFF000u;
 enum { SWEEP_SETDIFF = 0, SWEEP_INTERSECT = 1 };
 
-// device allocations of one call; freed when the call returns
-struct Arena {
-    std::vector<void *> ptrs;
-    ~Arena() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    gtars_status alloc(T **out, size_t n) {
-        void *p = nullptr;
-        GT_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T) + 16));
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return GTARS_OK;
-    }
-    template <class T>
-    gtars_status upload(T **out, const T *h, size_t n, hipStream_t st) {
-        gtars_status s = alloc(out, n);
-        if (s) return s;
-        if (n) GT_HIP(hipMemcpyAsync(*out, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-        return GTARS_OK;
-    }
-};
-
-// whatever way a call ends, the stream is idle when it does (the arena frees after this)
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
-#define SO_TRY(expr)                  \
-    do {                              \
-        gtars_status _s = (expr);     \
-        if (_s) return _s;            \
-    } while (0)
-
 inline unsigned grid_for(u64 n, u32 per = 256) { return (unsigned)std::min<u64>(std::max<u64>(1, (n + per - 1) / per), 1u << 16); }
 
 // ---------------------------------------------------------------------------------------------- segmented max-scan
@@ -158,12 +123,12 @@ k_sm_apply(const u32 *__restrict__ seg, const u32 *__restrict__ val, const u32 *
     }
 }
 
-gtars_status seg_max_pass(bool incl, const u32 *seg, const u32 *val, const u32 *start, u32 n, u32 gap, u32 *out, Arena &ar,
+gtars_status seg_max_pass(bool incl, const u32 *seg, const u32 *val, const u32 *start, u32 n, u32 gap, u32 *out, StreamFrame &fr,
                           hipStream_t st) {
     if (!n) return GTARS_OK;
     const u32 tiles = (n + SO_TILE - 1) / SO_TILE;
     u64 *agg = nullptr;
-    SO_TRY(ar.alloc(&agg, tiles));
+    GT_TRY(fr.alloc(&agg, tiles));
     hipLaunchKernelGGL(k_sm_tiles, dim3(tiles), dim3(SO_TPB), 0, st, seg, val, n, agg);
     hipLaunchKernelGGL(k_sm_carry, dim3(1), dim3(1024), 0, st, agg, tiles);
     if (incl)
@@ -175,12 +140,12 @@ gtars_status seg_max_pass(bool incl, const u32 *seg, const u32 *val, const u32 *
 }
 
 // exclusive scan of u32 flags / counts; returns the total
-gtars_status scan_counts(const u32 *cnt, u32 n, u64 **off, u64 *total, Arena &ar, hipStream_t st) {
-    SO_TRY(ar.alloc(off, (size_t)n + 1));
+gtars_status scan_counts(const u32 *cnt, u32 n, u64 **off, u64 *total, StreamFrame &fr, hipStream_t st) {
+    GT_TRY(fr.alloc(off, (size_t)n + 1));
     void *ws = nullptr;
     const size_t wsb = scan_ws_bytes(n);
-    SO_TRY(ar.alloc((u8 **)&ws, wsb));
-    SO_TRY(launch_scan_u32_to_u64(cnt, n, *off, ws, wsb, st));
+    GT_TRY(fr.alloc((u8 **)&ws, wsb));
+    GT_TRY(launch_scan_u32_to_u64(cnt, n, *off, ws, wsb, st));
     GT_HIP(hipMemcpyAsync(total, *off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
     GT_HIP(hipStreamSynchronize(st));
     return GTARS_OK;
@@ -267,41 +232,41 @@ struct DevSet {
 };
 
 // reduce() of n device regions (unsorted) whose segment keys are < n_seg
-gtars_status dev_reduce(const u32 *seg, const u32 *start, const u32 *end, u32 n, u32 n_seg, Arena &ar, hipStream_t st, DevSet &out) {
+gtars_status dev_reduce(const u32 *seg, const u32 *start, const u32 *end, u32 n, u32 n_seg, StreamFrame &fr, hipStream_t st, DevSet &out) {
     out = DevSet();
     if (!n) return GTARS_OK;
     u32 *perm, *sseg, *sstart, *send, *flag, *rid, *rmax;
-    SO_TRY(ar.alloc(&perm, n));
+    GT_TRY(fr.alloc(&perm, n));
     const size_t sb = device_sort_perm_ws_bytes(n);
     u8 *scratch;
-    SO_TRY(ar.alloc(&scratch, sb));
-    SO_TRY(device_sort_perm_ws(seg, start, nullptr, n, n_seg, perm, scratch, sb, st));  // (segment, start), ties in input order
-    SO_TRY(ar.alloc(&sseg, n));
-    SO_TRY(ar.alloc(&sstart, n));
-    SO_TRY(ar.alloc(&send, n));
+    GT_TRY(fr.alloc(&scratch, sb));
+    GT_TRY(device_sort_perm_ws(seg, start, nullptr, n, n_seg, perm, scratch, sb, st));  // (segment, start), ties in input order
+    GT_TRY(fr.alloc(&sseg, n));
+    GT_TRY(fr.alloc(&sstart, n));
+    GT_TRY(fr.alloc(&send, n));
     hipLaunchKernelGGL(k_gather3, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, sseg, sstart, send);
-    SO_TRY(ar.alloc(&flag, n));
-    SO_TRY(seg_max_pass(false, sseg, send, sstart, n, 0, flag, ar, st));
+    GT_TRY(fr.alloc(&flag, n));
+    GT_TRY(seg_max_pass(false, sseg, send, sstart, n, 0, flag, fr, st));
     u64 *off, m = 0;
-    SO_TRY(scan_counts(flag, n, &off, &m, ar, st));
-    SO_TRY(ar.alloc(&rid, n));
+    GT_TRY(scan_counts(flag, n, &off, &m, fr, st));
+    GT_TRY(fr.alloc(&rid, n));
     hipLaunchKernelGGL(k_run_ids, dim3(grid_for(n)), dim3(256), 0, st, flag, off, n, rid);
-    SO_TRY(ar.alloc(&rmax, n));
-    SO_TRY(seg_max_pass(true, rid, send, nullptr, n, 0, rmax, ar, st));
+    GT_TRY(fr.alloc(&rmax, n));
+    GT_TRY(seg_max_pass(true, rid, send, nullptr, n, 0, rmax, fr, st));
     out.n = (u32)m;
-    SO_TRY(ar.alloc(&out.seg, m));
-    SO_TRY(ar.alloc(&out.start, m));
-    SO_TRY(ar.alloc(&out.end, m));
+    GT_TRY(fr.alloc(&out.seg, m));
+    GT_TRY(fr.alloc(&out.start, m));
+    GT_TRY(fr.alloc(&out.end, m));
     hipLaunchKernelGGL(k_reduce_write, dim3(grid_for(n)), dim3(256), 0, st, sseg, sstart, flag, rid, rmax, n, out.seg, out.start,
                        out.end);
     GT_HIP(hipGetLastError());
     return GTARS_OK;
 }
 
-gtars_status upload_set(const SetCols &a, Arena &ar, hipStream_t st, u32 **seg, u32 **start, u32 **end) {
-    SO_TRY(ar.upload(seg, a.rank, a.n, st));
-    SO_TRY(ar.upload(start, a.start, a.n, st));
-    return ar.upload(end, a.end, a.n, st);
+gtars_status upload_set(const SetCols &a, StreamFrame &fr, hipStream_t st, u32 **seg, u32 **start, u32 **end) {
+    GT_TRY(fr.upload(seg, a.rank, a.n, st));
+    GT_TRY(fr.upload(start, a.start, a.n, st));
+    return fr.upload(end, a.end, a.n, st);
 }
 
 gtars_status download(const DevSet &d, hipStream_t st, SetOut &out) {
@@ -323,10 +288,10 @@ gtars_status check_sizes(u64 n, u32 n_rank) {
     return require_device();
 }
 
-gtars_status reduce_cols(const SetCols &a, u32 n_rank, Arena &ar, hipStream_t st, DevSet &out) {
+gtars_status reduce_cols(const SetCols &a, u32 n_rank, StreamFrame &fr, hipStream_t st, DevSet &out) {
     u32 *seg, *start, *end;
-    SO_TRY(upload_set(a, ar, st, &seg, &start, &end));
-    return dev_reduce(seg, start, end, (u32)a.n, n_rank, ar, st, out);
+    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    return dev_reduce(seg, start, end, (u32)a.n, n_rank, fr, st, out);
 }
 
 // ------------------------------------------------------------------------------------------- setdiff / intersect
@@ -404,30 +369,30 @@ __global__ void k_sweep_seq(const u32 *__restrict__ as, const u32 *__restrict__ 
 }
 
 template <int MODE>
-gtars_status dev_sweep(const DevSet &A, const DevSet &B, u32 n_rank, Arena &ar, hipStream_t st, DevSet &out) {
+gtars_status dev_sweep(const DevSet &A, const DevSet &B, u32 n_rank, StreamFrame &fr, hipStream_t st, DevSet &out) {
     out = DevSet();
     if (!A.n) return GTARS_OK;
     u32 *aoff, *boff, *dirty, *cnt;
-    SO_TRY(ar.alloc(&aoff, (size_t)n_rank + 1));
-    SO_TRY(ar.alloc(&boff, (size_t)n_rank + 1));
-    SO_TRY(ar.alloc(&dirty, n_rank));
+    GT_TRY(fr.alloc(&aoff, (size_t)n_rank + 1));
+    GT_TRY(fr.alloc(&boff, (size_t)n_rank + 1));
+    GT_TRY(fr.alloc(&dirty, n_rank));
     hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)A.n + 1)), dim3(256), 0, st, A.seg, A.n, n_rank, aoff);
     hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)B.n + 1)), dim3(256), 0, st, B.seg, B.n, n_rank, boff);
     GT_HIP(hipMemsetAsync(dirty, 0, (size_t)std::max<u32>(n_rank, 1) * 4, st));
     hipLaunchKernelGGL(k_mark_inverted, dim3(grid_for(A.n)), dim3(256), 0, st, A.seg, A.start, A.end, A.n, 1u, dirty);
     if (B.n) hipLaunchKernelGGL(k_mark_inverted, dim3(grid_for(B.n)), dim3(256), 0, st, B.seg, B.start, B.end, B.n, 1u, dirty);
-    SO_TRY(ar.alloc(&cnt, A.n));
+    GT_TRY(fr.alloc(&cnt, A.n));
     hipLaunchKernelGGL((k_sweep_par<MODE, false>), dim3(grid_for(A.n)), dim3(256), 0, st, A.seg, A.start, A.end, A.n, B.start, B.end,
                        boff, dirty, cnt, nullptr, nullptr, nullptr, nullptr);
     hipLaunchKernelGGL((k_sweep_seq<MODE, false>), dim3(grid_for(n_rank, 64)), dim3(64), 0, st, A.start, A.end, aoff, B.start, B.end,
                        boff, n_rank, dirty, cnt, nullptr, nullptr, nullptr, nullptr);
     u64 *off, m = 0;
-    SO_TRY(scan_counts(cnt, A.n, &off, &m, ar, st));
+    GT_TRY(scan_counts(cnt, A.n, &off, &m, fr, st));
     if (m > SO_MAX_N) return fail(GTARS_ERR_CAPACITY, "set operation result too large: need " + std::to_string(m));
     out.n = (u32)m;
-    SO_TRY(ar.alloc(&out.seg, m));
-    SO_TRY(ar.alloc(&out.start, m));
-    SO_TRY(ar.alloc(&out.end, m));
+    GT_TRY(fr.alloc(&out.seg, m));
+    GT_TRY(fr.alloc(&out.start, m));
+    GT_TRY(fr.alloc(&out.end, m));
     hipLaunchKernelGGL((k_sweep_par<MODE, true>), dim3(grid_for(A.n)), dim3(256), 0, st, A.seg, A.start, A.end, A.n, B.start, B.end,
                        boff, dirty, nullptr, off, out.seg, out.start, out.end);
     hipLaunchKernelGGL((k_sweep_seq<MODE, true>), dim3(grid_for(n_rank, 64)), dim3(64), 0, st, A.start, A.end, aoff, B.start, B.end,
@@ -438,14 +403,13 @@ gtars_status dev_sweep(const DevSet &A, const DevSet &B, u32 n_rank, Arena &ar, 
 
 template <int MODE>
 gtars_status two_set(const SetCols &a, const SetCols &b, u32 n_rank, SetOut &res) {
-    SO_TRY(check_sizes(a.n + b.n, n_rank));
+    GT_TRY(check_sizes(a.n + b.n, n_rank));
     hipStream_t st = nullptr;
-    Arena ar;
-    Drain drain{st};
+    StreamFrame fr(st);
     DevSet A, B, R;
-    SO_TRY(reduce_cols(a, n_rank, ar, st, A));
-    SO_TRY(reduce_cols(b, n_rank, ar, st, B));
-    SO_TRY(dev_sweep<MODE>(A, B, n_rank, ar, st, R));
+    GT_TRY(reduce_cols(a, n_rank, fr, st, A));
+    GT_TRY(reduce_cols(b, n_rank, fr, st, B));
+    GT_TRY(dev_sweep<MODE>(A, B, n_rank, fr, st, R));
     return download(R, st, res);
 }
 
@@ -594,12 +558,11 @@ double jaccard_of(const SetTotals &t) {
 
 // ======================================================================================================= entries
 gtars_status setops_reduce(const SetCols &a, uint32_t n_rank, SetOut &res) {
-    SO_TRY(check_sizes(a.n, n_rank));
+    GT_TRY(check_sizes(a.n, n_rank));
     hipStream_t st = nullptr;
-    Arena ar;
-    Drain drain{st};
+    StreamFrame fr(st);
     DevSet R;
-    SO_TRY(reduce_cols(a, n_rank, ar, st, R));
+    GT_TRY(reduce_cols(a, n_rank, fr, st, R));
     return download(R, st, res);
 }
 
@@ -612,16 +575,15 @@ gtars_status setops_intersect(const SetCols &a, const SetCols &b, uint32_t n_ran
 }
 
 gtars_status setops_totals(const SetCols &a, const SetCols &b, uint32_t n_rank, bool want_diff, SetTotals &out) {
-    SO_TRY(check_sizes(a.n + b.n, n_rank));
+    GT_TRY(check_sizes(a.n + b.n, n_rank));
     hipStream_t st = nullptr;
-    Arena ar;
-    Drain drain{st};
+    StreamFrame fr(st);
     // a and b side by side: reduce(a), reduce(b) and reduce(concat(a, b)) from the same columns
     const u64 n = a.n + b.n;
     u32 *seg, *start, *end;
-    SO_TRY(ar.alloc(&seg, n));
-    SO_TRY(ar.alloc(&start, n));
-    SO_TRY(ar.alloc(&end, n));
+    GT_TRY(fr.alloc(&seg, n));
+    GT_TRY(fr.alloc(&start, n));
+    GT_TRY(fr.alloc(&end, n));
     const SetCols *parts[2] = {&a, &b};
     u64 at = 0;
     for (const SetCols *p : parts) {
@@ -633,12 +595,12 @@ gtars_status setops_totals(const SetCols &a, const SetCols &b, uint32_t n_rank, 
         at += p->n;
     }
     DevSet A, B, U, D;
-    SO_TRY(dev_reduce(seg, start, end, (u32)a.n, n_rank, ar, st, A));
-    SO_TRY(dev_reduce(seg + a.n, start + a.n, end + a.n, (u32)b.n, n_rank, ar, st, B));
-    SO_TRY(dev_reduce(seg, start, end, (u32)n, n_rank, ar, st, U));
-    if (want_diff) SO_TRY(dev_sweep<SWEEP_SETDIFF>(A, B, n_rank, ar, st, D));
+    GT_TRY(dev_reduce(seg, start, end, (u32)a.n, n_rank, fr, st, A));
+    GT_TRY(dev_reduce(seg + a.n, start + a.n, end + a.n, (u32)b.n, n_rank, fr, st, B));
+    GT_TRY(dev_reduce(seg, start, end, (u32)n, n_rank, fr, st, U));
+    if (want_diff) GT_TRY(dev_sweep<SWEEP_SETDIFF>(A, B, n_rank, fr, st, D));
     u64 *acc;
-    SO_TRY(ar.alloc(&acc, 4));
+    GT_TRY(fr.alloc(&acc, 4));
     GT_HIP(hipMemsetAsync(acc, 0, 4 * sizeof(u64), st));
     const DevSet *sets[4] = {&A, &B, &U, &D};
     for (int k = 0; k < 4; ++k)
@@ -661,44 +623,43 @@ gtars_status setops_closest(const SetCols &a, const SetCols &other, uint32_t n_r
     self_idx.clear();
     other_idx.clear();
     dist.clear();
-    SO_TRY(check_sizes(std::max(a.n, other.n), n_rank));
+    GT_TRY(check_sizes(std::max(a.n, other.n), n_rank));
     if (!other.n || !a.n) return GTARS_OK;
     hipStream_t st = nullptr;
-    Arena ar;
-    Drain drain{st};
+    StreamFrame fr(st);
     const u32 no = (u32)other.n, nq = (u32)a.n;
     // candidates: `other` stably sorted by (chromosome, start)
     u32 *oseg, *ostart, *oend, *perm, *cseg, *cs, *ce, *coff, *maxw;
-    SO_TRY(upload_set(other, ar, st, &oseg, &ostart, &oend));
-    SO_TRY(ar.alloc(&perm, no));
+    GT_TRY(upload_set(other, fr, st, &oseg, &ostart, &oend));
+    GT_TRY(fr.alloc(&perm, no));
     const size_t sb = device_sort_perm_ws_bytes(no);
     u8 *scratch;
-    SO_TRY(ar.alloc(&scratch, sb));
-    SO_TRY(device_sort_perm_ws(oseg, ostart, nullptr, no, n_rank, perm, scratch, sb, st));
-    SO_TRY(ar.alloc(&cseg, no));
-    SO_TRY(ar.alloc(&cs, no));
-    SO_TRY(ar.alloc(&ce, no));
+    GT_TRY(fr.alloc(&scratch, sb));
+    GT_TRY(device_sort_perm_ws(oseg, ostart, nullptr, no, n_rank, perm, scratch, sb, st));
+    GT_TRY(fr.alloc(&cseg, no));
+    GT_TRY(fr.alloc(&cs, no));
+    GT_TRY(fr.alloc(&ce, no));
     hipLaunchKernelGGL(k_gather3, dim3(grid_for(no)), dim3(256), 0, st, perm, no, oseg, ostart, oend, cseg, cs, ce);
-    SO_TRY(ar.alloc(&coff, (size_t)n_rank + 1));
+    GT_TRY(fr.alloc(&coff, (size_t)n_rank + 1));
     hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)no + 1)), dim3(256), 0, st, cseg, no, n_rank, coff);
-    SO_TRY(ar.alloc(&maxw, n_rank));
+    GT_TRY(fr.alloc(&maxw, n_rank));
     GT_HIP(hipMemsetAsync(maxw, 0, (size_t)std::max<u32>(n_rank, 1) * 4, st));
     hipLaunchKernelGGL(k_max_width, dim3(grid_for((no + 63) / 64)), dim3(256), 0, st, cseg, cs, ce, no, maxw);
     u32 *qr, *qs, *qe, *found, *bidx;
     i64 *bd;
-    SO_TRY(upload_set(a, ar, st, &qr, &qs, &qe));
-    SO_TRY(ar.alloc(&found, nq));
-    SO_TRY(ar.alloc(&bidx, nq));
-    SO_TRY(ar.alloc(&bd, nq));
+    GT_TRY(upload_set(a, fr, st, &qr, &qs, &qe));
+    GT_TRY(fr.alloc(&found, nq));
+    GT_TRY(fr.alloc(&bidx, nq));
+    GT_TRY(fr.alloc(&bd, nq));
     hipLaunchKernelGGL(k_closest, dim3(grid_for(nq)), dim3(256), 0, st, qr, qs, qe, nq, cs, ce, perm, coff, maxw, n_rank, found, bidx, bd);
     GT_HIP(hipGetLastError());
     u64 *off, m = 0;
-    SO_TRY(scan_counts(found, nq, &off, &m, ar, st));
+    GT_TRY(scan_counts(found, nq, &off, &m, fr, st));
     u32 *o_self, *o_other;
     i64 *o_d;
-    SO_TRY(ar.alloc(&o_self, m));
-    SO_TRY(ar.alloc(&o_other, m));
-    SO_TRY(ar.alloc(&o_d, m));
+    GT_TRY(fr.alloc(&o_self, m));
+    GT_TRY(fr.alloc(&o_other, m));
+    GT_TRY(fr.alloc(&o_d, m));
     hipLaunchKernelGGL(k_closest_compact, dim3(grid_for(nq)), dim3(256), 0, st, found, off, bidx, bd, nq, o_self, o_other, o_d);
     GT_HIP(hipGetLastError());
     self_idx.resize(m);
@@ -714,28 +675,27 @@ gtars_status setops_closest(const SetCols &a, const SetCols &other, uint32_t n_r
 }
 
 gtars_status setops_cluster(const SetCols &a, uint32_t n_rank, uint32_t max_gap, uint32_t *ids) {
-    SO_TRY(check_sizes(a.n, n_rank));
+    GT_TRY(check_sizes(a.n, n_rank));
     if (!a.n) return GTARS_OK;
     hipStream_t st = nullptr;
-    Arena ar;
-    Drain drain{st};
+    StreamFrame fr(st);
     const u32 n = (u32)a.n;
     u32 *seg, *start, *end, *perm, *sseg, *sstart, *send, *flag, *d_ids;
-    SO_TRY(upload_set(a, ar, st, &seg, &start, &end));
-    SO_TRY(ar.alloc(&perm, n));
+    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    GT_TRY(fr.alloc(&perm, n));
     const size_t sb = device_sort_perm_ws_bytes(n);
     u8 *scratch;
-    SO_TRY(ar.alloc(&scratch, sb));
-    SO_TRY(device_sort_perm_ws(seg, start, end, n, n_rank, perm, scratch, sb, st));  // (chromosome, start, end)
-    SO_TRY(ar.alloc(&sseg, n));
-    SO_TRY(ar.alloc(&sstart, n));
-    SO_TRY(ar.alloc(&send, n));
+    GT_TRY(fr.alloc(&scratch, sb));
+    GT_TRY(device_sort_perm_ws(seg, start, end, n, n_rank, perm, scratch, sb, st));  // (chromosome, start, end)
+    GT_TRY(fr.alloc(&sseg, n));
+    GT_TRY(fr.alloc(&sstart, n));
+    GT_TRY(fr.alloc(&send, n));
     hipLaunchKernelGGL(k_gather3, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, sseg, sstart, send);
-    SO_TRY(ar.alloc(&flag, n));
-    SO_TRY(seg_max_pass(false, sseg, send, sstart, n, max_gap, flag, ar, st));
+    GT_TRY(fr.alloc(&flag, n));
+    GT_TRY(seg_max_pass(false, sseg, send, sstart, n, max_gap, flag, fr, st));
     u64 *off, m = 0;
-    SO_TRY(scan_counts(flag, n, &off, &m, ar, st));
-    SO_TRY(ar.alloc(&d_ids, n));
+    GT_TRY(scan_counts(flag, n, &off, &m, fr, st));
+    GT_TRY(fr.alloc(&d_ids, n));
     hipLaunchKernelGGL(k_cluster_scatter, dim3(grid_for(n)), dim3(256), 0, st, perm, flag, off, n, d_ids);
     GT_HIP(hipGetLastError());
     GT_HIP(hipMemcpyAsync(ids, d_ids, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -747,7 +707,7 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
     const u64 n_sets = sets.size();
     u64 n = 0;
     for (const SetCols &s : sets) n += s.n;
-    SO_TRY(check_sizes(n, n_rank));
+    GT_TRY(check_sizes(n, n_rank));
     if (!n_sets) return GTARS_OK;
     const u64 n_seg64 = n_sets * std::max<u32>(n_rank, 1);
     if (n_seg64 > 0x7FFFFFFFull || n_sets > 0xFFFFFFull) return fail(GTARS_ERR_INVALID_ARG, "too many sets x chromosomes for one pairwise call");
@@ -756,13 +716,12 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
         for (u64 j = 0; j < n_sets; ++j) out[i * n_sets + j] = i == j ? 1.0 : 0.0;
     if (!n) return GTARS_OK;  // every off-diagonal pair has union 0
     hipStream_t st = nullptr;
-    Arena ar;
-    Drain drain{st};
+    StreamFrame fr(st);
     // every set reduced in one pass: segment = set * n_rank + chromosome rank
     std::vector<u32> hseg(n);
     u32 *seg, *start, *end;
-    SO_TRY(ar.alloc(&start, n));
-    SO_TRY(ar.alloc(&end, n));
+    GT_TRY(fr.alloc(&start, n));
+    GT_TRY(fr.alloc(&end, n));
     u64 at = 0;
     for (u64 k = 0; k < n_sets; ++k) {
         const SetCols &s = sets[k];
@@ -773,25 +732,25 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
         }
         at += s.n;
     }
-    SO_TRY(ar.upload(&seg, hseg.data(), n, st));
+    GT_TRY(fr.upload(&seg, hseg.data(), n, st));
     DevSet R;
-    SO_TRY(dev_reduce(seg, start, end, (u32)n, n_seg, ar, st, R));
+    GT_TRY(dev_reduce(seg, start, end, (u32)n, n_seg, fr, st, R));
     u32 *seg_off, *dirty, *w, *d_set_off;
-    SO_TRY(ar.alloc(&seg_off, (size_t)n_seg + 1));
+    GT_TRY(fr.alloc(&seg_off, (size_t)n_seg + 1));
     hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)R.n + 1)), dim3(256), 0, st, R.seg, R.n, n_seg, seg_off);
-    SO_TRY(ar.alloc(&dirty, n_sets));
+    GT_TRY(fr.alloc(&dirty, n_sets));
     GT_HIP(hipMemsetAsync(dirty, 0, n_sets * 4, st));
     hipLaunchKernelGGL(k_mark_inverted, dim3(grid_for(R.n)), dim3(256), 0, st, R.seg, R.start, R.end, R.n, nr, dirty);
-    SO_TRY(ar.alloc(&w, R.n));
+    GT_TRY(fr.alloc(&w, R.n));
     hipLaunchKernelGGL(k_widths, dim3(grid_for(R.n)), dim3(256), 0, st, R.start, R.end, R.n, w);
     u64 *P, total = 0;
-    SO_TRY(scan_counts(w, R.n, &P, &total, ar, st));
+    GT_TRY(scan_counts(w, R.n, &P, &total, fr, st));
     std::vector<u32> h_seg_off((size_t)n_seg + 1), h_dirty(n_sets), set_off(n_sets + 1);
     GT_HIP(hipMemcpyAsync(h_seg_off.data(), seg_off, h_seg_off.size() * 4, hipMemcpyDeviceToHost, st));
     GT_HIP(hipMemcpyAsync(h_dirty.data(), dirty, n_sets * 4, hipMemcpyDeviceToHost, st));
     GT_HIP(hipStreamSynchronize(st));
     for (u64 k = 0; k <= n_sets; ++k) set_off[k] = h_seg_off[k * nr];
-    SO_TRY(ar.upload(&d_set_off, set_off.data(), set_off.size(), st));
+    GT_TRY(fr.upload(&d_set_off, set_off.data(), set_off.size(), st));
     // work list over the pairs of clean sets (no inverted region after reduce)
     std::vector<uint2> pairs;
     std::vector<uint4> items;
@@ -813,18 +772,18 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
         uint4 *d_items;
         u64 *inter;
         double *dM;
-        SO_TRY(ar.upload(&d_pairs, pairs.data(), pairs.size(), st));
-        SO_TRY(ar.alloc(&inter, pairs.size()));
+        GT_TRY(fr.upload(&d_pairs, pairs.data(), pairs.size(), st));
+        GT_TRY(fr.alloc(&inter, pairs.size()));
         GT_HIP(hipMemsetAsync(inter, 0, pairs.size() * 8, st));
         if (!items.empty()) {
-            SO_TRY(ar.upload(&d_items, items.data(), items.size(), st));
+            GT_TRY(fr.upload(&d_items, items.data(), items.size(), st));
             for (size_t b = 0; b < items.size(); b += (1u << 20)) {  // grids of at most 2^20 workgroups
                 const size_t nb = std::min<size_t>(items.size() - b, 1u << 20);
                 hipLaunchKernelGGL(k_pair_inter, dim3((unsigned)nb), dim3(256), 0, st, d_items + b, R.seg, R.start, R.end, P, d_set_off,
                                    seg_off, nr, inter);
             }
         }
-        SO_TRY(ar.alloc(&dM, n_sets * n_sets));
+        GT_TRY(fr.alloc(&dM, n_sets * n_sets));
         GT_HIP(hipMemcpyAsync(dM, out, n_sets * n_sets * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_pair_finish, dim3(grid_for(pairs.size())), dim3(256), 0, st, d_pairs, (u32)pairs.size(), inter, P, d_set_off,
                            (u32)n_sets, dM);
@@ -835,14 +794,14 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
     if (!dirty_pairs.empty()) {
         // a set that keeps an inverted region: the two-set path on the reduced sets, both orders
         SetOut h;
-        SO_TRY(download(R, st, h));
+        GT_TRY(download(R, st, h));
         for (u32 k = 0; k < R.n; ++k) h.rank[k] %= nr;
         auto cols = [&](u32 k) { return SetCols{h.rank.data() + set_off[k], h.start.data() + set_off[k], h.end.data() + set_off[k],
                                                 (u64)(set_off[k + 1] - set_off[k])}; };
         for (const auto &pr : dirty_pairs) {
             SetTotals t1, t2;
-            SO_TRY(setops_totals(cols(pr.first), cols(pr.second), n_rank, false, t1));
-            SO_TRY(setops_totals(cols(pr.second), cols(pr.first), n_rank, false, t2));
+            GT_TRY(setops_totals(cols(pr.first), cols(pr.second), n_rank, false, t1));
+            GT_TRY(setops_totals(cols(pr.second), cols(pr.first), n_rank, false, t2));
             out[(u64)pr.first * n_sets + pr.second] = jaccard_of(t1);
             out[(u64)pr.second * n_sets + pr.first] = jaccard_of(t2);
         }

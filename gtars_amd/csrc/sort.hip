@@ -756,12 +756,11 @@ gtars_status device_sort_perm_ws(const u32 *d_chrom, const u32 *d_k1, const u32 
 gtars_status device_sort_perm(const u32 *d_chrom, const u32 *d_k1, const u32 *d_k2, u32 n, u32 n_chrom, u32 *d_perm,
                               hipStream_t st) {
     if (n == 0) return GTARS_OK;
-    void *buf = nullptr;
     const size_t bytes = device_sort_perm_ws_bytes(n);
-    GT_HIP(hipMalloc(&buf, bytes));
-    gtars_status s = device_sort_perm_ws(d_chrom, d_k1, d_k2, n, n_chrom, d_perm, buf, bytes, st);
+    DevBuf<u8> buf;
+    GT_TRY(buf.alloc(bytes));
+    gtars_status s = device_sort_perm_ws(d_chrom, d_k1, d_k2, n, n_chrom, d_perm, buf.p, bytes, st);
     hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
     if (s) return s;
     GT_HIP(e);
     return GTARS_OK;
