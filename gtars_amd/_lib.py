@@ -159,6 +159,13 @@ _HOST_SIG = {
     "gtars_regionset_closest": (C.c_int, [vp, vp, pp, pp, pp, pu64]),
     "gtars_regionset_cluster": (C.c_int, [vp, u32, vp]),
     "gtars_regionset_pairwise_jaccard": (C.c_int, [vp, u64, vp]),
+    "gtars_regionset_disjoin": (C.c_int, [vp, pp]),
+    "gtars_regionset_gaps": (C.c_int, [vp, vp, vp, u64, pp]),
+    "gtars_regionset_consensus": (C.c_int, [vp, u64, pp, pp]),
+    "gtars_regionset_neighbor_distances": (C.c_int, [vp, pp, pu64]),
+    "gtars_regionset_nearest_neighbors": (C.c_int, [vp, pp, pu64]),
+    "gtars_regionset_distribution": (C.c_int, [vp, u32, C.c_int, vp, vp, u64, pp, pu64]),
+    "gtars_regionset_chromosome_statistics": (C.c_int, [vp, pp, pp, pu64]),
     "gtars_tokenizer_from_auto": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_config": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_bed": (C.c_int, [cstr, pp]),

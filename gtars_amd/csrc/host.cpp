@@ -28,6 +28,7 @@
 #include <string>
 #include <string_view>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -1092,6 +1093,304 @@ gtars_status gtars_regionset_pairwise_jaccard(const gtars_regionset_t *const *se
             cols[k] = cols_of(sets[k], ranks[k]);
         }
         return gtars::setops_pairwise_jaccard(cols, sp.size(), out);
+    });
+}
+
+}  // extern "C"
+
+// ============================================================ structural operations and region-set statistics
+// disjoin / gaps (region_set.rs:786-1090), consensus (gtars-genomicdist/src/consensus.rs:29-68) and the statistics of
+// gtars-genomicdist/src/statistics.rs:88-316, computed by setops.hip (K9).  chrom_sizes arrive as parallel name / size
+// arrays; a later entry of a name replaces an earlier one, as collecting the pairs into a HashMap does.
+
+namespace {
+
+using ChromSizes = std::unordered_map<std::string, uint32_t>;
+
+gtars_status read_sizes(const char *const *names, const uint32_t *sizes, uint64_t n, ChromSizes &out) {
+    if (n && (!names || !sizes)) return fail(GTARS_ERR_INVALID_ARG, "NULL chrom_sizes");
+    out.clear();
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!names[i]) return fail(GTARS_ERR_INVALID_ARG, "NULL chromosome name");
+        out[names[i]] = sizes[i];
+    }
+    return GTARS_OK;
+}
+
+// chrom_karyotype_key (gtars-core/src/utils.rs:359-370): "chr" stripped; numbers (u32::from_str: an optional '+', then
+// decimal digits that fit in u32) first, then X, Y, M / MT, then everything else by the bare name, bytewise
+struct KaryoKey {
+    int cls;
+    uint32_t num;
+    std::string rest;
+    bool operator<(const KaryoKey &o) const { return std::tie(cls, num, rest) < std::tie(o.cls, o.num, o.rest); }
+    bool operator==(const KaryoKey &o) const { return cls == o.cls && num == o.num && rest == o.rest; }
+};
+
+KaryoKey karyotype_key(const std::string &chr) {
+    const std::string bare = chr.compare(0, 3, "chr") == 0 ? chr.substr(3) : chr;
+    if (bare == "X") return {1, 0, ""};
+    if (bare == "Y") return {2, 0, ""};
+    if (bare == "M" || bare == "MT") return {3, 0, ""};
+    size_t i = !bare.empty() && bare[0] == '+' ? 1 : 0;
+    bool ok = i < bare.size();
+    uint64_t v = 0;
+    for (; ok && i < bare.size(); ++i) {
+        const char c = bare[i];
+        if (c < '0' || c > '9') ok = false;
+        else if ((v = v * 10 + (uint64_t)(c - '0')) > 0xFFFFFFFFull) ok = false;
+    }
+    if (ok) return {0, (uint32_t)v, ""};
+    return {4, 0, bare};
+}
+
+// rank -> id of the same name in the set's own dictionary
+std::vector<uint32_t> ids_of_ranks(const RankSpace &sp, const gtars_regionset *rs) {
+    std::vector<uint32_t> id(sp.size(), GTARS_UNKNOWN_CHROM);
+    for (uint32_t r = 0; r < sp.size(); ++r) {
+        const int64_t k = rs->chroms.find(sp.names[r]);
+        if (k >= 0) id[r] = (uint32_t)k;
+    }
+    return id;
+}
+
+template <class T>
+gtars_status to_malloc(const std::vector<T> &v, T **out) {
+    T *p = (T *)malloc(std::max<size_t>(v.size(), 1) * sizeof(T));
+    if (!p) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
+    *out = p;
+    return GTARS_OK;
+}
+
+// get_max_end_per_chr (region_set.rs:584-606): per chromosome id, the largest end of its LAST contiguous run in set order
+std::vector<uint32_t> max_end_last_run(const gtars_regionset *rs) {
+    std::vector<uint32_t> out(rs->chroms.names.size(), 0);
+    const size_t n = rs->size();
+    for (size_t i = 0; i < n;) {
+        const uint32_t c = rs->chrom_ids[i];
+        uint32_t m = rs->ends[i];
+        size_t j = i + 1;
+        for (; j < n && rs->chrom_ids[j] == c; ++j) m = std::max(m, rs->ends[j]);
+        out[c] = m;
+        i = j;
+    }
+    return out;
+}
+
+}  // namespace
+
+extern "C" {
+
+gtars_status gtars_regionset_disjoin(const gtars_regionset_t *rs, gtars_regionset_t **out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        RankSpace sp;
+        sp.build({rs});
+        const std::vector<uint32_t> r = sp.ranks_of(rs);
+        gtars::SetOut o;
+        if (const gtars_status e = gtars::setops_disjoin(cols_of(rs, r), sp.size(), o)) return e;
+        *out = regionset_from(sp, o);
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_gaps(const gtars_regionset_t *rs, const char *const *names, const uint32_t *sizes, uint64_t n_sizes,
+                                  gtars_regionset_t **out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        ChromSizes cs;
+        if (const gtars_status e = read_sizes(names, sizes, n_sizes, cs)) return e;
+        // ranks over the set's names and the sized ones
+        RankSpace sp;
+        std::set<std::string> all(rs->chroms.names.begin(), rs->chroms.names.end());
+        for (const auto &kv : cs) all.insert(kv.first);
+        sp.names.assign(all.begin(), all.end());
+        for (uint32_t k = 0; k < sp.names.size(); ++k) sp.rank.emplace(sp.names[k], k);
+        std::vector<uint32_t> size(sp.size(), 0), group(sp.size(), 0);
+        std::vector<KaryoKey> keys(sp.size());
+        for (uint32_t k = 0; k < sp.size(); ++k) {
+            auto it = cs.find(sp.names[k]);
+            if (it != cs.end()) size[k] = it->second;
+            keys[k] = karyotype_key(sp.names[k]);
+        }
+        std::vector<KaryoKey> uniq = keys;
+        std::sort(uniq.begin(), uniq.end());
+        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+        for (uint32_t k = 0; k < sp.size(); ++k) group[k] = (uint32_t)(std::lower_bound(uniq.begin(), uniq.end(), keys[k]) - uniq.begin());
+        const std::vector<uint32_t> r = sp.ranks_of(rs);
+        gtars::SetOut o;
+        if (const gtars_status e = gtars::setops_gaps(cols_of(rs, r), sp.size(), size, group, (uint32_t)uniq.size(), o)) return e;
+        *out = regionset_from(sp, o);
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_consensus(const gtars_regionset_t *const *sets, uint64_t n, gtars_regionset_t **out_union,
+                                       uint32_t **out_count) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out_union || !out_count || (n && !sets)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_union = nullptr;
+        *out_count = nullptr;
+        for (uint64_t k = 0; k < n; ++k)
+            if (!sets[k]) return fail(GTARS_ERR_INVALID_ARG, "NULL region set");
+        RankSpace sp;
+        sp.build_list(sets, n);
+        std::vector<std::vector<uint32_t>> ranks(n);
+        std::vector<gtars::SetCols> cols(n);
+        for (uint64_t k = 0; k < n; ++k) {
+            ranks[k] = sp.ranks_of(sets[k]);
+            cols[k] = cols_of(sets[k], ranks[k]);
+        }
+        gtars::SetOut o;
+        std::vector<uint32_t> count;
+        if (const gtars_status e = gtars::setops_consensus(cols, sp.size(), o, count)) return e;
+        if (const gtars_status e = to_malloc(count, out_count)) return e;
+        *out_union = regionset_from(sp, o);
+        return GTARS_OK;
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+// iter_chroms (region_set.rs:399-407): chromosomes ranked by first appearance in the set
+template <class F>
+gtars_status by_first_appearance(const gtars_regionset *rs, F &&op) {
+    std::vector<uint32_t> fa(rs->chroms.names.size(), GTARS_UNKNOWN_CHROM), r(rs->size());
+    uint32_t next = 0;
+    for (size_t i = 0; i < rs->size(); ++i) {
+        uint32_t &f = fa[rs->chrom_ids[i]];
+        if (f == GTARS_UNKNOWN_CHROM) f = next++;
+        r[i] = f;
+    }
+    return op(cols_of(rs, r), next);
+}
+
+}  // namespace
+
+extern "C" {
+
+gtars_status gtars_regionset_neighbor_distances(const gtars_regionset_t *rs, int64_t **out, uint64_t *out_n) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        *out_n = 0;
+        std::vector<int64_t> d;
+        if (const gtars_status e = by_first_appearance(rs, [&](const gtars::SetCols &c, uint32_t n_rank) {
+            return gtars::setops_neighbor_distances(c, n_rank, d);
+        })) return e;
+        if (const gtars_status e = to_malloc(d, out)) return e;
+        *out_n = d.size();
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_nearest_neighbors(const gtars_regionset_t *rs, uint32_t **out, uint64_t *out_n) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        *out_n = 0;
+        std::vector<uint32_t> d;
+        if (const gtars_status e = by_first_appearance(rs, [&](const gtars::SetCols &c, uint32_t n_rank) {
+            return gtars::setops_nearest_neighbors(c, n_rank, d);
+        })) return e;
+        if (const gtars_status e = to_malloc(d, out)) return e;
+        *out_n = d.size();
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_distribution(const gtars_regionset_t *rs, uint32_t n_bins, int has_sizes, const char *const *names,
+                                          const uint32_t *sizes, uint64_t n_sizes, uint32_t **out_rows, uint64_t *out_n) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out_rows || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_rows = nullptr;
+        *out_n = 0;
+        ChromSizes cs;
+        if (const gtars_status e = has_sizes ? read_sizes(names, sizes, n_sizes, cs) : GTARS_OK) return e;
+        if (const gtars_status e = gtars::require_device()) return e;
+        RankSpace sp;
+        sp.build({rs});
+        const std::vector<uint32_t> r = sp.ranks_of(rs), id = ids_of_ranks(sp, rs);
+        std::vector<uint32_t> limit(sp.size(), 0), rows;
+        uint32_t bin_size = 1;
+        const bool empty = rs->size() == 0 || (has_sizes && n_bins == 0);
+        if (!empty && has_sizes) {
+            // region_distribution_with_chrom_sizes (statistics.rs:199-256): one bin width from the longest listed chromosome
+            uint64_t longest = 0;
+            for (const auto &kv : cs) longest = std::max<uint64_t>(longest, kv.second);
+            if (cs.empty()) longest = 1;
+            bin_size = (uint32_t)std::max<uint64_t>(longest / n_bins, 1);
+            for (uint32_t k = 0; k < sp.size(); ++k) {
+                auto it = cs.find(sp.names[k]);
+                if (it != cs.end()) limit[k] = it->second;
+            }
+        } else if (!empty) {
+            // region_distribution_with_bins (statistics.rs:143-197): bins from the largest get_max_end_per_chr value
+            const std::vector<uint32_t> me = max_end_last_run(rs);
+            uint32_t longest = 0;
+            for (uint32_t k = 0; k < sp.size(); ++k) {
+                limit[k] = me[id[k]];
+                longest = std::max(longest, limit[k]);
+            }
+            bin_size = n_bins == 0 ? std::max<uint32_t>(longest, 1) : std::max<uint32_t>(longest / n_bins, 1);
+        }
+        if (!empty) {
+            std::vector<uint32_t> kr, kid, cnt;
+            if (const gtars_status e = gtars::setops_distribution(cols_of(rs, r), sp.size(), n_bins, bin_size, has_sizes != 0, limit, kr, kid, cnt)) return e;
+            rows.resize(kr.size() * 5);
+            for (size_t k = 0; k < kr.size(); ++k) {
+                const uint32_t lim = limit[kr[k]], start = kid[k] * bin_size, stop = std::min<uint32_t>(start + bin_size, lim);
+                uint32_t *row = rows.data() + k * 5;
+                row[0] = id[kr[k]];
+                row[1] = start;
+                row[2] = has_sizes && kid[k] == n_bins - 1 ? lim : stop;
+                row[3] = cnt[k];
+                row[4] = kid[k];
+            }
+        }
+        if (const gtars_status e = to_malloc(rows, out_rows)) return e;
+        *out_n = rows.size() / 5;
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_chromosome_statistics(const gtars_regionset_t *rs, uint32_t **out_rows, double **out_f64,
+                                                   uint64_t *out_n) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out_rows || !out_f64 || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_rows = nullptr;
+        *out_f64 = nullptr;
+        *out_n = 0;
+        RankSpace sp;
+        sp.build({rs});
+        const std::vector<uint32_t> r = sp.ranks_of(rs), id = ids_of_ranks(sp, rs);
+        std::vector<gtars::ChromStat> st;
+        if (const gtars_status e = gtars::setops_chrom_stats(cols_of(rs, r), sp.size(), st)) return e;
+        std::vector<uint32_t> rows;
+        std::vector<double> f;
+        for (uint32_t k = 0; k < sp.size(); ++k) {
+            const gtars::ChromStat &s = st[k];
+            if (!s.count) continue;
+            rows.insert(rows.end(), {id[k], s.count, s.min_start, s.max_end, s.min_width, s.max_width});
+            f.insert(f.end(), {s.mean, s.median});
+        }
+        uint32_t *pr = nullptr;
+        double *pf = nullptr;
+        if (const gtars_status e = to_malloc(rows, &pr)) return e;
+        gtars_status e = to_malloc(f, &pf);
+        if (e) {
+            free(pr);
+            return e;
+        }
+        *out_rows = pr;
+        *out_f64 = pf;
+        *out_n = rows.size() / 6;
+        return GTARS_OK;
     });
 }
 

@@ -41,4 +41,34 @@ gtars_status setops_cluster(const SetCols &a, uint32_t n_rank, uint32_t max_gap,
 // RegionSetList::pairwise_jaccard: out[i * n + j] == reduce(S_i).jaccard(reduce(S_j)), 1.0 on the diagonal
 gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t n_rank, double *out);
 
+// GTARS_ERR_NO_DEVICE unless a device is visible (common.h)
+gtars_status require_device();
+
+// ---- K9: structural operations and region-set statistics (gtars-genomicdist) -----------------------------------------
+// RegionSet::disjoin (region_set.rs:1051-1090): pieces between consecutive boundaries (every start and end) of a
+// chromosome that some well-formed region (start < end) covers, in (rank, start) order
+gtars_status setops_disjoin(const SetCols &a, uint32_t n_rank, SetOut &out);
+// RegionSet::gaps (region_set.rs:786-878).  size[r]: chromosome size of rank r, 0 where it is absent or 0 (nothing is
+// emitted for it); group[r] < n_group: its karyotype key's position among the keys.  Out: (group, start, rank) order.
+gtars_status setops_gaps(const SetCols &a, uint32_t n_rank, const std::vector<uint32_t> &size, const std::vector<uint32_t> &group,
+                         uint32_t n_group, SetOut &out);
+// consensus (gtars-genomicdist/src/consensus.rs:29-68): reduce of the concatenation, and for each run the number of
+// sets with a region that hits it (start < run.end && run.start < end)
+gtars_status setops_consensus(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &uni, std::vector<uint32_t> &count);
+// calc_neighbor_distances / calc_nearest_neighbors (statistics.rs:258-316); rank: first appearance in the set
+gtars_status setops_neighbor_distances(const SetCols &a, uint32_t n_rank, std::vector<int64_t> &out);
+gtars_status setops_nearest_neighbors(const SetCols &a, uint32_t n_rank, std::vector<uint32_t> &out);
+// region_distribution_with_bins / _with_chrom_sizes (statistics.rs:143-256): regions counted per (rank, rid) of their
+// midpoint.  with_sizes: limit[r] is the chromosome size (0: absent), regions with midpoint >= it are skipped and rid is
+// clamped to n_bins - 1.  Out: the occupied (rank, rid) keys in ascending order and their counts.
+gtars_status setops_distribution(const SetCols &a, uint32_t n_rank, uint32_t n_bins, uint32_t bin_size, bool with_sizes,
+                                 const std::vector<uint32_t> &limit, std::vector<uint32_t> &rank, std::vector<uint32_t> &rid,
+                                 std::vector<uint32_t> &count);
+// chromosome_statistics (statistics.rs:88-141), one entry per rank; count == 0: the rank holds no region
+struct ChromStat {
+    uint32_t count, min_start, max_end, min_width, max_width;
+    double mean, median;
+};
+gtars_status setops_chrom_stats(const SetCols &a, uint32_t n_rank, std::vector<ChromStat> &out);
+
 }  // namespace gtars

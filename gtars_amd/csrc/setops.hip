@@ -18,6 +18,8 @@
 //     F_j(x.end) - F_j(x.start).  One work list of (smaller set, other set, chunk) items covers every pair.
 // Widths and totals are the reference's release-build u32 values: (u32)(end - start), summed modulo 2^32 (u64 on the
 // device, truncated), and the intersection is a_bp + b_bp - union_bp in wrapping u32.
+// K9 (the second half of the file) builds disjoin, gaps, consensus and the region-set statistics of gtars-genomicdist
+// from the same blocks; DESIGN.md §3 K9.
 #include <algorithm>
 #include <limits>
 #include <vector>
@@ -231,9 +233,17 @@ struct DevSet {
     u32 n = 0;
 };
 
+// what a reduce leaves behind for callers that work on the members of the runs: the sort permutation, the sorted
+// columns and each sorted region's run (an index into the reduced set)
+struct ReduceWork {
+    u32 *perm = nullptr, *sseg = nullptr, *sstart = nullptr, *send = nullptr, *rid = nullptr;
+};
+
 // reduce() of n device regions (unsorted) whose segment keys are < n_seg
-gtars_status dev_reduce(const u32 *seg, const u32 *start, const u32 *end, u32 n, u32 n_seg, StreamFrame &fr, hipStream_t st, DevSet &out) {
+gtars_status dev_reduce(const u32 *seg, const u32 *start, const u32 *end, u32 n, u32 n_seg, StreamFrame &fr, hipStream_t st, DevSet &out,
+                        ReduceWork *work = nullptr) {
     out = DevSet();
+    if (work) *work = ReduceWork();
     if (!n) return GTARS_OK;
     u32 *perm, *sseg, *sstart, *send, *flag, *rid, *rmax;
     GT_TRY(fr.alloc(&perm, n));
@@ -260,6 +270,7 @@ gtars_status dev_reduce(const u32 *seg, const u32 *start, const u32 *end, u32 n,
     hipLaunchKernelGGL(k_reduce_write, dim3(grid_for(n)), dim3(256), 0, st, sseg, sstart, flag, rid, rmax, n, out.seg, out.start,
                        out.end);
     GT_HIP(hipGetLastError());
+    if (work) *work = ReduceWork{perm, sseg, sstart, send, rid};
     return GTARS_OK;
 }
 
@@ -806,6 +817,549 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
             out[(u64)pr.second * n_sets + pr.first] = jaccard_of(t2);
         }
     }
+    return GTARS_OK;
+}
+
+
+// ================================================================= K9: structural operations and region-set statistics
+// disjoin, gaps, consensus, neighbour distances, the midpoint distribution and the per-chromosome statistics of
+// gtars-core's RegionSet and gtars-genomicdist, on the same blocks as K8: the stable radix sort, the segmented max-scan
+// of reduce, and count / scan / write compaction.
+namespace {
+
+__global__ void k_fill(u32 *__restrict__ p, u32 n, u32 v) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) p[i] = v;
+}
+
+// out[i] = table[idx[i]]
+__global__ void k_lookup(const u32 *__restrict__ idx, u32 n, const u32 *__restrict__ table, u32 *__restrict__ out) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) out[i] = table[idx[i]];
+}
+
+gtars_status download_u32(u32 *h, const u32 *d, u64 n, hipStream_t st) {
+    if (n) GT_HIP(hipMemcpyAsync(h, d, n * 4, hipMemcpyDeviceToHost, st));
+    return GTARS_OK;
+}
+
+// stable sort of n device rows by (seg, k1[, k2]); returns the permutation
+gtars_status sort_rows(const u32 *seg, const u32 *k1, const u32 *k2, u32 n, u32 n_seg, StreamFrame &fr, hipStream_t st, u32 **perm) {
+    GT_TRY(fr.alloc(perm, n));
+    const size_t sb = device_sort_perm_ws_bytes(n);
+    u8 *scratch;
+    GT_TRY(fr.alloc(&scratch, sb));
+    return device_sort_perm_ws(seg, k1, k2, n, n_seg, *perm, scratch, sb, st);
+}
+
+// ------------------------------------------------------------------------------------------------------- disjoin
+// events 2i and 2i + 1: the start and the end of region i
+__global__ void k_dj_events(const u32 *__restrict__ rank, const u32 *__restrict__ start, const u32 *__restrict__ end, u32 n,
+                            u32 *__restrict__ ev_rank, u32 *__restrict__ ev_pos) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        ev_rank[2 * i] = ev_rank[2 * i + 1] = rank[i];
+        ev_pos[2 * i] = start[i];
+        ev_pos[2 * i + 1] = end[i];
+    }
+}
+
+// sorted events; opens / closes: the event is the start / end of a well-formed region (start < end).  Inverted and
+// zero-width regions add boundaries and no depth.
+__global__ void k_dj_gather(const u32 *__restrict__ perm, u32 m, const u32 *__restrict__ ev_rank, const u32 *__restrict__ ev_pos,
+                            const u32 *__restrict__ start, const u32 *__restrict__ end, u32 *__restrict__ srank, u32 *__restrict__ spos,
+                            u32 *__restrict__ opens, u32 *__restrict__ closes) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (u64)gridDim.x * blockDim.x) {
+        const u32 p = perm[j], i = p >> 1;
+        const u32 wf = start[i] < end[i];
+        srank[j] = ev_rank[p];
+        spos[j] = ev_pos[p];
+        opens[j] = wf & ~p & 1u;
+        closes[j] = wf & p & 1u;
+    }
+}
+
+// piece [pos[j], pos[j + 1]) when j is the last event at its position, the next event is on the same chromosome, and the
+// depth after j (opens minus closes so far: every chromosome's own events cancel) is positive.  WRITE: emit it at off[j].
+template <bool WRITE>
+__global__ void k_dj_pieces(const u32 *__restrict__ srank, const u32 *__restrict__ spos, const u64 *__restrict__ co,
+                            const u64 *__restrict__ cc, u32 m, u32 *__restrict__ keep, const u64 *__restrict__ off,
+                            u32 *__restrict__ orank, u32 *__restrict__ ostart, u32 *__restrict__ oend) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (u64)gridDim.x * blockDim.x) {
+        const bool k = j + 1 < m && srank[j + 1] == srank[j] && spos[j + 1] != spos[j] && co[j + 1] > cc[j + 1];
+        if (!WRITE) {
+            keep[j] = k;
+        } else if (k) {
+            const u64 o = off[j];
+            orank[o] = srank[j];
+            ostart[o] = spos[j];
+            oend[o] = spos[j + 1];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- gaps
+// per reduced run i of a chromosome with size cs > 0: the leading gap (first run) or the gap after the previous run,
+// then the trailing gap (last run), each clipped as RegionSet::gaps clips it
+template <bool WRITE>
+__global__ void k_gaps(const u32 *__restrict__ seg, const u32 *__restrict__ start, const u32 *__restrict__ end, u32 n,
+                       const u32 *__restrict__ size, u32 *__restrict__ cnt, const u64 *__restrict__ off, u32 *__restrict__ oseg,
+                       u32 *__restrict__ os, u32 *__restrict__ oe) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u32 r = seg[i], cs = size[r];
+        const bool first = i == 0 || seg[i - 1] != r, last = i + 1 == n || seg[i + 1] != r;
+        const u64 o = WRITE ? off[i] : 0;
+        u32 c = 0;
+        if (cs) {
+            if (first) {
+                if (start[i] > 0) emit<0, WRITE>(c, o, r, 0, min(start[i], cs), oseg, os, oe);
+            } else {
+                const u32 gs = end[i - 1], ge = start[i];
+                if (gs < ge && min(gs, cs) < min(ge, cs)) emit<0, WRITE>(c, o, r, min(gs, cs), min(ge, cs), oseg, os, oe);
+            }
+            if (last && end[i] < cs) emit<0, WRITE>(c, o, r, end[i], cs, oseg, os, oe);
+        }
+        if (!WRITE) cnt[i] = c;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------- consensus
+// a sorted region hits its own run when start < run.end && run.start < end (the AIList rule); set' = its set, or
+// n_sets when it does not hit
+__global__ void k_cons_hits(const u32 *__restrict__ perm, const u32 *__restrict__ set, const u32 *__restrict__ sstart,
+                            const u32 *__restrict__ send, const u32 *__restrict__ rid, const u32 *__restrict__ ustart,
+                            const u32 *__restrict__ uend, u32 n, u32 n_sets, u32 *__restrict__ hit_set) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
+        const u32 r = rid[j];
+        hit_set[j] = (sstart[j] < uend[r] && ustart[r] < send[j]) ? set[perm[j]] : n_sets;
+    }
+}
+
+// rows sorted by (run, set'): one count per distinct hitting set of a run
+__global__ void k_cons_count(const u32 *__restrict__ perm, const u32 *__restrict__ rid, const u32 *__restrict__ hit_set, u32 n,
+                             u32 n_sets, u32 *__restrict__ count) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
+        const u32 p = perm[j], s = hit_set[p];
+        if (s == n_sets) continue;
+        if (j > 0) {
+            const u32 q = perm[j - 1];
+            if (rid[q] == rid[p] && hit_set[q] == s) continue;
+        }
+        atomicAdd(&count[rid[p]], 1u);
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------- neighbours
+// rows sorted by (first-appearance rank, start, end).  NEAREST: every region of a chromosome with >= 2 regions, the
+// smaller of its gaps to the left and right neighbour clamped at 0.  Else: every gap next.start - prev.end > 0.
+template <bool NEAREST, bool WRITE>
+__global__ void k_neighbors(const u32 *__restrict__ seg, const u32 *__restrict__ start, const u32 *__restrict__ end, u32 n,
+                            u32 *__restrict__ keep, const u64 *__restrict__ off, i64 *__restrict__ odist, u32 *__restrict__ onear) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
+        const bool has_r = j + 1 < n && seg[j + 1] == seg[j];
+        const i64 dr = has_r ? (i64)start[j + 1] - (i64)end[j] : 0;
+        if (NEAREST) {
+            const bool has_l = j > 0 && seg[j - 1] == seg[j];
+            const bool k = has_l || has_r;
+            if (!WRITE) {
+                keep[j] = k;
+            } else if (k) {
+                const i64 dl = has_l ? (i64)start[j] - (i64)end[j - 1] : 0;
+                const u32 cl = dl > 0 ? (u32)dl : 0u, cr = dr > 0 ? (u32)dr : 0u;
+                onear[off[j]] = !has_l ? cr : !has_r ? cl : min(cl, cr);
+            }
+        } else {
+            const bool k = has_r && dr > 0;
+            if (!WRITE) keep[j] = k;
+            else if (k) odist[off[j]] = dr;
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------------------------- distribution
+// key of region i: (rank, rid) of its midpoint start + (u32)(end - start) / 2 (wrapping); rank n_rank: not counted
+__global__ void k_bin_keys(const u32 *__restrict__ rank, const u32 *__restrict__ start, const u32 *__restrict__ end, u32 n,
+                           u32 n_rank, u32 n_bins, u32 bin_size, int with_sizes, const u32 *__restrict__ limit,
+                           u32 *__restrict__ krank, u32 *__restrict__ krid) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u32 r = rank[i], mid = start[i] + (end[i] - start[i]) / 2u;
+        u32 rid = mid / bin_size, kr = r;
+        if (with_sizes) {
+            if (mid >= limit[r]) kr = n_rank;
+            rid = min(rid, n_bins - 1u);
+        }
+        krank[i] = kr;
+        krid[i] = rid;
+    }
+}
+
+// head[j]: row j (sorted by key) is counted and opens a key
+__global__ void k_rle_heads(const u32 *__restrict__ perm, const u32 *__restrict__ krank, const u32 *__restrict__ krid, u32 n,
+                            u32 n_rank, u32 *__restrict__ head) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
+        const u32 p = perm[j];
+        bool h = krank[p] < n_rank;
+        if (h && j > 0) {
+            const u32 q = perm[j - 1];
+            h = krank[q] != krank[p] || krid[q] != krid[p];
+        }
+        head[j] = h;
+    }
+}
+
+// key o = (rank, rid) opens at row pos[o]; pos[m] = the number of counted rows (they sort first)
+__global__ void k_rle_write(const u32 *__restrict__ perm, const u32 *__restrict__ krank, const u32 *__restrict__ krid,
+                            const u32 *__restrict__ head, const u64 *__restrict__ off, u32 n, u32 n_rank, u32 m,
+                            u32 *__restrict__ orank, u32 *__restrict__ orid, u32 *__restrict__ pos) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (u64)gridDim.x * blockDim.x) {
+        const u32 p = perm[j];
+        if (head[j]) {
+            const u64 o = off[j];
+            orank[o] = krank[p];
+            orid[o] = krid[p];
+            pos[o] = (u32)j;
+        }
+        if (krank[p] < n_rank && (j + 1 == n || krank[perm[j + 1]] == n_rank)) pos[m] = (u32)(j + 1);
+    }
+}
+
+__global__ void k_rle_counts(const u32 *__restrict__ pos, u32 m, u32 *__restrict__ count) {
+    for (u64 o = (u64)blockIdx.x * blockDim.x + threadIdx.x; o < m; o += (u64)gridDim.x * blockDim.x) count[o] = pos[o + 1] - pos[o];
+}
+
+// ---------------------------------------------------------------------------------------------- chromosome stats
+// rows sorted by (rank, width): per lane 64 consecutive rows, flushed to the rank's min start / max end / width sum
+// whenever the rank changes
+__global__ void k_stat_bounds(const u32 *__restrict__ seg, const u32 *__restrict__ start, const u32 *__restrict__ end, u32 n,
+                              u32 *__restrict__ min_start, u32 *__restrict__ max_end, u64 *__restrict__ wsum) {
+    constexpr u32 PER = 64;
+    for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t * PER < n; t += (u64)gridDim.x * blockDim.x) {
+        const u64 i1 = std::min<u64>(n, (t + 1) * PER);
+        u32 r = seg[t * PER], lo = 0xFFFFFFFFu, hi = 0;
+        u64 sum = 0;
+        for (u64 i = t * PER; i < i1; ++i) {
+            if (seg[i] != r) {
+                atomicMin(&min_start[r], lo);
+                atomicMax(&max_end[r], hi);
+                atomicAdd((unsigned long long *)&wsum[r], (unsigned long long)sum);
+                r = seg[i];
+                lo = 0xFFFFFFFFu, hi = 0, sum = 0;
+            }
+            lo = min(lo, start[i]);
+            hi = max(hi, end[i]);
+            sum += (u32)(end[i] - start[i]);
+        }
+        atomicMin(&min_start[r], lo);
+        atomicMax(&max_end[r], hi);
+        atomicAdd((unsigned long long *)&wsum[r], (unsigned long long)sum);
+    }
+}
+
+// one lane per rank: count, min / max width at the segment's ends, mean = u64 sum / count, median from the middle
+// widths (an even count adds the two in wrapping u32 before the division, as the reference's release build does)
+__global__ void k_stat_finish(const u32 *__restrict__ off, const u32 *__restrict__ w, const u64 *__restrict__ wsum, u32 n_rank,
+                              u32 *__restrict__ count, u32 *__restrict__ min_w, u32 *__restrict__ max_w, double *__restrict__ mean,
+                              double *__restrict__ median) {
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_rank; r += (u64)gridDim.x * blockDim.x) {
+        const u32 lo = off[r], c = off[r + 1] - lo;
+        count[r] = c;
+        if (!c) continue;
+        min_w[r] = w[lo];
+        max_w[r] = w[lo + c - 1];
+        mean[r] = (double)wsum[r] / (double)c;
+        median[r] = (c & 1) ? (double)w[lo + c / 2] : (double)(u32)(w[lo + c / 2 - 1] + w[lo + c / 2]) / 2.0;
+    }
+}
+
+// sorted rows of (rank, start, end) and their widths
+__global__ void k_gather_widths(const u32 *__restrict__ perm, u32 n, const u32 *__restrict__ seg, const u32 *__restrict__ start,
+                                const u32 *__restrict__ end, u32 *__restrict__ sseg, u32 *__restrict__ ss, u32 *__restrict__ se,
+                                u32 *__restrict__ sw) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u32 p = perm[i];
+        sseg[i] = seg[p];
+        ss[i] = start[p];
+        se[i] = end[p];
+        sw[i] = end[p] - start[p];
+    }
+}
+
+// rows of `a` sorted by (rank, start[, end]), gathered
+gtars_status sorted_cols(const SetCols &a, u32 n_rank, bool by_end, StreamFrame &fr, hipStream_t st, DevSet &out) {
+    const u32 n = (u32)a.n;
+    u32 *seg, *start, *end, *perm;
+    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    GT_TRY(sort_rows(seg, start, by_end ? end : nullptr, n, n_rank, fr, st, &perm));
+    out.n = n;
+    GT_TRY(fr.alloc(&out.seg, n));
+    GT_TRY(fr.alloc(&out.start, n));
+    GT_TRY(fr.alloc(&out.end, n));
+    hipLaunchKernelGGL(k_gather3, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, out.seg, out.start, out.end);
+    GT_HIP(hipGetLastError());
+    return GTARS_OK;
+}
+
+}  // namespace
+
+gtars_status setops_disjoin(const SetCols &a, uint32_t n_rank, SetOut &res) {
+    GT_TRY(check_sizes(2 * a.n, n_rank));
+    res = SetOut();
+    if (!a.n) return GTARS_OK;
+    hipStream_t st = nullptr;
+    StreamFrame fr(st);
+    const u32 n = (u32)a.n, m = 2 * n;
+    u32 *seg, *start, *end, *ev_rank, *ev_pos, *perm, *srank, *spos, *opens, *closes, *keep;
+    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    GT_TRY(fr.alloc(&ev_rank, m));
+    GT_TRY(fr.alloc(&ev_pos, m));
+    hipLaunchKernelGGL(k_dj_events, dim3(grid_for(n)), dim3(256), 0, st, seg, start, end, n, ev_rank, ev_pos);
+    GT_TRY(sort_rows(ev_rank, ev_pos, nullptr, m, n_rank, fr, st, &perm));
+    GT_TRY(fr.alloc(&srank, m));
+    GT_TRY(fr.alloc(&spos, m));
+    GT_TRY(fr.alloc(&opens, m));
+    GT_TRY(fr.alloc(&closes, m));
+    hipLaunchKernelGGL(k_dj_gather, dim3(grid_for(m)), dim3(256), 0, st, perm, m, ev_rank, ev_pos, start, end, srank, spos, opens, closes);
+    u64 *co, *cc, *off, t = 0, k = 0;
+    GT_TRY(scan_counts(opens, m, &co, &t, fr, st));
+    GT_TRY(scan_counts(closes, m, &cc, &t, fr, st));
+    GT_TRY(fr.alloc(&keep, m));
+    hipLaunchKernelGGL(k_dj_pieces<false>, dim3(grid_for(m)), dim3(256), 0, st, srank, spos, co, cc, m, keep, nullptr, nullptr, nullptr,
+                       nullptr);
+    GT_TRY(scan_counts(keep, m, &off, &k, fr, st));
+    DevSet R;
+    R.n = (u32)k;
+    GT_TRY(fr.alloc(&R.seg, k));
+    GT_TRY(fr.alloc(&R.start, k));
+    GT_TRY(fr.alloc(&R.end, k));
+    hipLaunchKernelGGL(k_dj_pieces<true>, dim3(grid_for(m)), dim3(256), 0, st, srank, spos, co, cc, m, nullptr, off, R.seg, R.start,
+                       R.end);
+    GT_HIP(hipGetLastError());
+    return download(R, st, res);
+}
+
+gtars_status setops_gaps(const SetCols &a, uint32_t n_rank, const std::vector<uint32_t> &size, const std::vector<uint32_t> &group,
+                         uint32_t n_group, SetOut &res) {
+    GT_TRY(check_sizes(a.n + n_rank, n_rank));
+    if (size.size() != n_rank || group.size() != n_rank) return fail(GTARS_ERR_INTERNAL, "gaps: per-rank tables of the wrong size");
+    res = SetOut();
+    hipStream_t st = nullptr;
+    StreamFrame fr(st);
+    DevSet R;
+    GT_TRY(reduce_cols(a, n_rank, fr, st, R));
+    // full-chromosome gaps: ranks with a size that hold no region
+    std::vector<u32> has(n_rank, 0);
+    for (u64 i = 0; i < a.n; ++i) has[a.rank[i]] = 1;
+    std::vector<u32> fr_rank, fr_end;
+    for (u32 r = 0; r < n_rank; ++r)
+        if (size[r] && !has[r]) fr_rank.push_back(r), fr_end.push_back(size[r]);
+    const u32 nf = (u32)fr_rank.size();
+    u32 *d_size, *cnt = nullptr;
+    GT_TRY(fr.upload(&d_size, size.data(), n_rank, st));
+    u64 *off = nullptr, m = 0;
+    if (R.n) {
+        GT_TRY(fr.alloc(&cnt, R.n));
+        hipLaunchKernelGGL(k_gaps<false>, dim3(grid_for(R.n)), dim3(256), 0, st, R.seg, R.start, R.end, R.n, d_size, cnt, nullptr, nullptr,
+                           nullptr, nullptr);
+        GT_TRY(scan_counts(cnt, R.n, &off, &m, fr, st));
+    }
+    const u64 total = m + nf;
+    if (total > SO_MAX_N) return fail(GTARS_ERR_CAPACITY, "gaps result too large: need " + std::to_string(total));
+    if (!total) return GTARS_OK;
+    const u32 g = (u32)total;
+    u32 *gseg, *gstart, *gend, *ggroup, *d_group, *perm;
+    GT_TRY(fr.alloc(&gseg, g));
+    GT_TRY(fr.alloc(&gstart, g));
+    GT_TRY(fr.alloc(&gend, g));
+    if (R.n)
+        hipLaunchKernelGGL(k_gaps<true>, dim3(grid_for(R.n)), dim3(256), 0, st, R.seg, R.start, R.end, R.n, d_size, nullptr, off, gseg,
+                           gstart, gend);
+    if (nf) {
+        GT_HIP(hipMemcpyAsync(gseg + m, fr_rank.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
+        GT_HIP(hipMemsetAsync(gstart + m, 0, (size_t)nf * 4, st));
+        GT_HIP(hipMemcpyAsync(gend + m, fr_end.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
+    }
+    // karyotypic order: (key, start), names of one key bytewise (rank order)
+    GT_TRY(fr.upload(&d_group, group.data(), n_rank, st));
+    GT_TRY(fr.alloc(&ggroup, g));
+    hipLaunchKernelGGL(k_lookup, dim3(grid_for(g)), dim3(256), 0, st, gseg, g, d_group, ggroup);
+    GT_TRY(sort_rows(ggroup, gstart, gseg, g, std::max<u32>(n_group, 1), fr, st, &perm));
+    DevSet O;
+    O.n = g;
+    GT_TRY(fr.alloc(&O.seg, g));
+    GT_TRY(fr.alloc(&O.start, g));
+    GT_TRY(fr.alloc(&O.end, g));
+    hipLaunchKernelGGL(k_gather3, dim3(grid_for(g)), dim3(256), 0, st, perm, g, gseg, gstart, gend, O.seg, O.start, O.end);
+    GT_HIP(hipGetLastError());
+    return download(O, st, res);
+}
+
+gtars_status setops_consensus(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &uni, std::vector<uint32_t> &count) {
+    u64 n = 0;
+    for (const SetCols &s : sets) n += s.n;
+    GT_TRY(check_sizes(n, n_rank));
+    uni = SetOut();
+    count.clear();
+    if (sets.size() >= 0xFFFFFFFFull) return fail(GTARS_ERR_INVALID_ARG, "too many region sets");
+    if (!n) return GTARS_OK;
+    const u32 n_sets = (u32)sets.size();
+    hipStream_t st = nullptr;
+    StreamFrame fr(st);
+    // the concatenation, with each row's set
+    u32 *seg, *start, *end, *set;
+    GT_TRY(fr.alloc(&seg, n));
+    GT_TRY(fr.alloc(&start, n));
+    GT_TRY(fr.alloc(&end, n));
+    GT_TRY(fr.alloc(&set, n));
+    u64 at = 0;
+    for (u32 k = 0; k < n_sets; ++k) {
+        const SetCols &s = sets[k];
+        if (s.n) {
+            GT_HIP(hipMemcpyAsync(seg + at, s.rank, s.n * 4, hipMemcpyHostToDevice, st));
+            GT_HIP(hipMemcpyAsync(start + at, s.start, s.n * 4, hipMemcpyHostToDevice, st));
+            GT_HIP(hipMemcpyAsync(end + at, s.end, s.n * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_fill, dim3(grid_for(s.n)), dim3(256), 0, st, set + at, (u32)s.n, k);
+        }
+        at += s.n;
+    }
+    DevSet U;
+    ReduceWork w;
+    GT_TRY(dev_reduce(seg, start, end, (u32)n, n_rank, fr, st, U, &w));
+    // a region can only hit its own run: a later run starts past every end of the earlier ones
+    u32 *hit_set, *perm, *d_count;
+    GT_TRY(fr.alloc(&hit_set, n));
+    hipLaunchKernelGGL(k_cons_hits, dim3(grid_for(n)), dim3(256), 0, st, w.perm, set, w.sstart, w.send, w.rid, U.start, U.end, (u32)n,
+                       n_sets, hit_set);
+    GT_TRY(sort_rows(w.rid, hit_set, nullptr, (u32)n, U.n, fr, st, &perm));
+    GT_TRY(fr.alloc(&d_count, U.n));
+    GT_HIP(hipMemsetAsync(d_count, 0, (size_t)U.n * 4, st));
+    hipLaunchKernelGGL(k_cons_count, dim3(grid_for(n)), dim3(256), 0, st, perm, w.rid, hit_set, (u32)n, n_sets, d_count);
+    GT_HIP(hipGetLastError());
+    count.resize(U.n);
+    GT_TRY(download_u32(count.data(), d_count, U.n, st));
+    return download(U, st, uni);
+}
+
+template <bool NEAREST, class T>
+gtars_status neighbors(const SetCols &a, uint32_t n_rank, std::vector<T> &res) {
+    GT_TRY(check_sizes(a.n, n_rank));
+    res.clear();
+    if (a.n < 2) return GTARS_OK;
+    hipStream_t st = nullptr;
+    StreamFrame fr(st);
+    DevSet S;
+    GT_TRY(sorted_cols(a, n_rank, true, fr, st, S));
+    u32 *keep;
+    GT_TRY(fr.alloc(&keep, S.n));
+    hipLaunchKernelGGL((k_neighbors<NEAREST, false>), dim3(grid_for(S.n)), dim3(256), 0, st, S.seg, S.start, S.end, S.n, keep, nullptr,
+                       nullptr, nullptr);
+    u64 *off, m = 0;
+    GT_TRY(scan_counts(keep, S.n, &off, &m, fr, st));
+    T *out;
+    GT_TRY(fr.alloc(&out, m));
+    hipLaunchKernelGGL((k_neighbors<NEAREST, true>), dim3(grid_for(S.n)), dim3(256), 0, st, S.seg, S.start, S.end, S.n, nullptr, off,
+                       (i64 *)out, (u32 *)out);
+    GT_HIP(hipGetLastError());
+    res.resize(m);
+    if (m) GT_HIP(hipMemcpyAsync(res.data(), out, m * sizeof(T), hipMemcpyDeviceToHost, st));
+    GT_HIP(hipStreamSynchronize(st));
+    return GTARS_OK;
+}
+
+gtars_status setops_neighbor_distances(const SetCols &a, uint32_t n_rank, std::vector<int64_t> &out) {
+    return neighbors<false>(a, n_rank, out);
+}
+
+gtars_status setops_nearest_neighbors(const SetCols &a, uint32_t n_rank, std::vector<uint32_t> &out) {
+    return neighbors<true>(a, n_rank, out);
+}
+
+gtars_status setops_distribution(const SetCols &a, uint32_t n_rank, uint32_t n_bins, uint32_t bin_size, bool with_sizes,
+                                 const std::vector<uint32_t> &limit, std::vector<uint32_t> &rank, std::vector<uint32_t> &rid,
+                                 std::vector<uint32_t> &count) {
+    GT_TRY(check_sizes(a.n, n_rank + 1));
+    rank.clear();
+    rid.clear();
+    count.clear();
+    if (!bin_size || (with_sizes && !n_bins) || limit.size() != n_rank) return fail(GTARS_ERR_INTERNAL, "distribution: bad bin layout");
+    if (!a.n) return GTARS_OK;
+    hipStream_t st = nullptr;
+    StreamFrame fr(st);
+    const u32 n = (u32)a.n;
+    u32 *seg, *start, *end, *d_limit, *krank, *krid, *perm, *head;
+    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    GT_TRY(fr.upload(&d_limit, limit.data(), std::max<u32>(n_rank, 1), st));
+    GT_TRY(fr.alloc(&krank, n));
+    GT_TRY(fr.alloc(&krid, n));
+    hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(n)), dim3(256), 0, st, seg, start, end, n, n_rank, n_bins, bin_size, (int)with_sizes,
+                       d_limit, krank, krid);
+    GT_TRY(sort_rows(krank, krid, nullptr, n, n_rank + 1, fr, st, &perm));
+    GT_TRY(fr.alloc(&head, n));
+    hipLaunchKernelGGL(k_rle_heads, dim3(grid_for(n)), dim3(256), 0, st, perm, krank, krid, n, n_rank, head);
+    u64 *off, m = 0;
+    GT_TRY(scan_counts(head, n, &off, &m, fr, st));
+    if (!m) return GTARS_OK;
+    u32 *orank, *orid, *pos, *cnt;
+    GT_TRY(fr.alloc(&orank, m));
+    GT_TRY(fr.alloc(&orid, m));
+    GT_TRY(fr.alloc(&pos, m + 1));
+    GT_TRY(fr.alloc(&cnt, m));
+    hipLaunchKernelGGL(k_rle_write, dim3(grid_for(n)), dim3(256), 0, st, perm, krank, krid, head, off, n, n_rank, (u32)m, orank, orid, pos);
+    hipLaunchKernelGGL(k_rle_counts, dim3(grid_for(m)), dim3(256), 0, st, pos, (u32)m, cnt);
+    GT_HIP(hipGetLastError());
+    rank.resize(m);
+    rid.resize(m);
+    count.resize(m);
+    GT_TRY(download_u32(rank.data(), orank, m, st));
+    GT_TRY(download_u32(rid.data(), orid, m, st));
+    GT_TRY(download_u32(count.data(), cnt, m, st));
+    GT_HIP(hipStreamSynchronize(st));
+    return GTARS_OK;
+}
+
+gtars_status setops_chrom_stats(const SetCols &a, uint32_t n_rank, std::vector<ChromStat> &out) {
+    GT_TRY(check_sizes(a.n, n_rank));
+    out.assign(n_rank, ChromStat{0, 0, 0, 0, 0, 0.0, 0.0});
+    if (!a.n) return GTARS_OK;
+    hipStream_t st = nullptr;
+    StreamFrame fr(st);
+    const u32 n = (u32)a.n, nr = std::max<u32>(n_rank, 1);
+    u32 *seg, *start, *end, *w, *perm, *sseg, *ss, *se, *sw, *off, *min_s, *max_e, *cnt, *min_w, *max_w;
+    u64 *wsum;
+    double *mean, *median;
+    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    GT_TRY(fr.alloc(&w, n));
+    hipLaunchKernelGGL(k_widths, dim3(grid_for(n)), dim3(256), 0, st, start, end, n, w);
+    GT_TRY(sort_rows(seg, w, nullptr, n, n_rank, fr, st, &perm));  // (rank, width)
+    GT_TRY(fr.alloc(&sseg, n));
+    GT_TRY(fr.alloc(&ss, n));
+    GT_TRY(fr.alloc(&se, n));
+    GT_TRY(fr.alloc(&sw, n));
+    hipLaunchKernelGGL(k_gather_widths, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, sseg, ss, se, sw);
+    GT_TRY(fr.alloc(&off, (size_t)nr + 1));
+    hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)n + 1)), dim3(256), 0, st, sseg, n, n_rank, off);
+    GT_TRY(fr.alloc(&min_s, nr));
+    GT_TRY(fr.alloc(&max_e, nr));
+    GT_TRY(fr.alloc(&wsum, nr));
+    GT_HIP(hipMemsetAsync(min_s, 0xFF, (size_t)nr * 4, st));
+    GT_HIP(hipMemsetAsync(max_e, 0, (size_t)nr * 4, st));
+    GT_HIP(hipMemsetAsync(wsum, 0, (size_t)nr * 8, st));
+    hipLaunchKernelGGL(k_stat_bounds, dim3(grid_for((n + 63) / 64)), dim3(256), 0, st, sseg, ss, se, n, min_s, max_e, wsum);
+    GT_TRY(fr.alloc(&cnt, nr));
+    GT_TRY(fr.alloc(&min_w, nr));
+    GT_TRY(fr.alloc(&max_w, nr));
+    GT_TRY(fr.alloc(&mean, nr));
+    GT_TRY(fr.alloc(&median, nr));
+    hipLaunchKernelGGL(k_stat_finish, dim3(grid_for(n_rank)), dim3(256), 0, st, off, sw, wsum, n_rank, cnt, min_w, max_w, mean, median);
+    GT_HIP(hipGetLastError());
+    std::vector<u32> h_cnt(nr), h_min_s(nr), h_max_e(nr), h_min_w(nr), h_max_w(nr);
+    std::vector<double> h_mean(nr), h_median(nr);
+    GT_TRY(download_u32(h_cnt.data(), cnt, n_rank, st));
+    GT_TRY(download_u32(h_min_s.data(), min_s, n_rank, st));
+    GT_TRY(download_u32(h_max_e.data(), max_e, n_rank, st));
+    GT_TRY(download_u32(h_min_w.data(), min_w, n_rank, st));
+    GT_TRY(download_u32(h_max_w.data(), max_w, n_rank, st));
+    GT_HIP(hipMemcpyAsync(h_mean.data(), mean, (size_t)n_rank * 8, hipMemcpyDeviceToHost, st));
+    GT_HIP(hipMemcpyAsync(h_median.data(), median, (size_t)n_rank * 8, hipMemcpyDeviceToHost, st));
+    GT_HIP(hipStreamSynchronize(st));
+    for (u32 r = 0; r < n_rank; ++r)
+        if (h_cnt[r]) out[r] = ChromStat{h_cnt[r], h_min_s[r], h_max_e[r], h_min_w[r], h_max_w[r], h_mean[r], h_median[r]};
     return GTARS_OK;
 }
 

@@ -13,12 +13,19 @@ overlap_coefficient, closest, cluster) and ``RegionSetList.pairwise_jaccard`` (r
 on the GPU (csrc/setops.hip); results are bit-exact against the reference's semantics, ``closest`` with
 one pinned choice the reference leaves open (the walk starts at the first of several ``other`` regions that
 share the query's start).
+
+The structural operations and statistics of region_set.rs:288-531 are here too: ``disjoin``, ``gaps``,
+``neighbor_distances``, ``nearest_neighbors``, ``distribution`` and ``chromosome_statistics`` (returning
+``ChromosomeStatistics``) run on the GPU (csrc/setops.hip, K9); ``trim``, ``promoters``, ``pintersect``, ``concat``,
+``widths`` / ``region_widths``, ``mean_region_width`` and ``get_max_end_per_chr`` are elementwise host arithmetic.
+``gaps`` pins the order the reference leaves open among names that share a karyotype key (start, then name bytewise).
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -263,6 +270,179 @@ class RegionSet:
         out = np.zeros(len(self), dtype=np.uint32)
         check(lib.gtars_regionset_cluster(self._h, int(max_gap), ptr(out)))
         return out.tolist()
+
+    # -- structural operations and statistics (gtars-python/src/models/region_set.rs:288-531) ----------------------
+    # disjoin / gaps / neighbor_distances / nearest_neighbors / distribution / chromosome_statistics run on the GPU
+    # (csrc/setops.hip, K9); the elementwise ones below are O(n) numpy over the host columns.
+    def disjoin(self) -> "RegionSet":
+        """every boundary a boundary of the result: the covered pieces, sorted by (chr, start), strand "*" """
+        return self._result(lib.gtars_regionset_disjoin)
+
+    def gaps(self, chrom_sizes: Dict[str, int]) -> "RegionSet":
+        """the uncovered stretches of the chromosomes in chrom_sizes, in karyotypic order (region_set.rs:786-878)"""
+        arr, sizes, _keep, n = _sizes(chrom_sizes)
+        return self._result(lib.gtars_regionset_gaps, C.cast(arr, C.c_void_p), ptr(sizes), n)
+
+    def neighbor_distances(self) -> List[int]:
+        p, n = C.c_void_p(), C.c_uint64()
+        check(lib.gtars_regionset_neighbor_distances(self._h, C.byref(p), C.byref(n)))
+        return _take(p, C.c_int64, n.value)
+
+    def nearest_neighbors(self) -> List[int]:
+        p, n = C.c_void_p(), C.c_uint64()
+        check(lib.gtars_regionset_nearest_neighbors(self._h, C.byref(p), C.byref(n)))
+        return _take(p, C.c_uint32, n.value)
+
+    def distribution(self, n_bins: int = 250, chrom_sizes: Optional[Dict[str, int]] = None) -> List[dict]:
+        """regions per bin of their midpoint: dicts {chr, start, end, n, rid} sorted by (chr, start)"""
+        n_bins = _u32(n_bins, "n_bins")
+        if chrom_sizes is None:
+            arr, sizes, _keep, n, has = None, np.zeros(0, dtype=np.uint32), None, 0, 0
+        else:
+            (arr, sizes, _keep, n), has = _sizes(chrom_sizes), 1
+        p, m = C.c_void_p(), C.c_uint64()
+        check(lib.gtars_regionset_distribution(self._h, n_bins, has, C.cast(arr, C.c_void_p) if arr is not None else None,
+                                               ptr(sizes), n, C.byref(p), C.byref(m)))
+        rows = _take(p, C.c_uint32, 5 * m.value)
+        names = self.chrom_names
+        return [{"chr": names[rows[k]], "start": rows[k + 1], "end": rows[k + 2], "n": rows[k + 3], "rid": rows[k + 4]}
+                for k in range(0, len(rows), 5)]
+
+    def chromosome_statistics(self) -> Dict[str, "ChromosomeStatistics"]:
+        pr, pf, m = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        check(lib.gtars_regionset_chromosome_statistics(self._h, C.byref(pr), C.byref(pf), C.byref(m)))
+        rows, f = _take(pr, C.c_uint32, 6 * m.value), _take(pf, C.c_double, 2 * m.value)
+        names = self.chrom_names
+        out: Dict[str, ChromosomeStatistics] = {}
+        for k in range(m.value):
+            c, cnt, lo, hi, wmin, wmax = rows[6 * k:6 * k + 6]
+            out[names[c]] = ChromosomeStatistics(names[c], cnt, lo, hi, wmin, wmax, f[2 * k], f[2 * k + 1])
+        return out
+
+    def trim(self, chrom_sizes: Dict[str, int]) -> "RegionSet":
+        """regions clamped to their chromosome's size; unsized chromosomes and clamped start > end dropped; strand lost"""
+        names, ids = self.chrom_names, self.chrom_ids
+        size = np.array([_u32(chrom_sizes.get(nm, 0), "chromosome size") for nm in names], dtype=np.uint32)
+        known = np.array([nm in chrom_sizes for nm in names], dtype=bool)
+        cs = size[ids] if len(ids) else np.zeros(0, dtype=np.uint32)
+        s, e = np.minimum(self.starts, cs), np.minimum(self.ends, cs)
+        keep = (known[ids] if len(ids) else np.zeros(0, dtype=bool)) & (s <= e)
+        return RegionSet.from_vectors([names[i] for i in ids[keep]], s[keep], e[keep])
+
+    def promoters(self, upstream: int, downstream: int) -> "RegionSet":
+        """[start - upstream, start + downstream), saturating in u32; strand kept"""
+        up, down = _u32(upstream, "upstream"), _u32(downstream, "downstream")
+        s = self.starts.astype(np.int64)
+        names, ids = self.chrom_names, self.chrom_ids
+        return RegionSet._from_columns([names[i] for i in ids], np.maximum(s - up, 0), np.minimum(s + down, _U32_MAX), None,
+                                       self.strands)
+
+    def pintersect(self, other: "RegionSet") -> "RegionSet":
+        """pairwise by position over the shorter length: [max start, min end), empty at max start when the two do not
+        overlap, at self's start when the chromosomes differ; self's strands"""
+        n = min(len(self), len(other))
+        an, bn = self.chrom_names, other.chrom_names
+        ac = [an[i] for i in self.chrom_ids[:n]]
+        bc = [bn[i] for i in other.chrom_ids[:n]]
+        a_s, a_e, b_s, b_e = self.starts[:n], self.ends[:n], other.starts[:n], other.ends[:n]
+        same = np.array([x == y for x, y in zip(ac, bc)], dtype=bool)
+        s = np.maximum(a_s, b_s)
+        e = np.minimum(a_e, b_e)
+        e = np.where(s >= e, s, e)
+        s, e = np.where(same, s, a_s), np.where(same, e, a_s)
+        return RegionSet._from_columns(ac, s, e, None, self.strands)
+
+    def concat(self, other: "RegionSet") -> "RegionSet":
+        """self's regions then other's, rest kept, strand lists concatenated"""
+        regs = self.regions + other.regions
+        return RegionSet._from_columns([r.chr for r in regs], [r.start for r in regs], [r.end for r in regs],
+                                       [r.rest for r in regs], self.strands + other.strands)
+
+    def widths(self) -> List[int]:
+        return ((self.ends - self.starts).astype(np.uint32)).tolist()
+
+    def region_widths(self) -> List[int]:
+        return self.widths()
+
+    def mean_region_width(self) -> float:
+        """wrapping u32 sum of the widths / count, rounded to 2 decimals (half away from zero); nan when empty"""
+        n = len(self)
+        if n == 0:
+            return float("nan")
+        v = (self.get_nucleotide_length() / n) * 100.0
+        r = math.floor(v)
+        return (r + 1.0 if v - r >= 0.5 else float(r)) / 100.0
+
+    def get_max_end_per_chr(self) -> Dict[str, int]:
+        """per chromosome, the largest end of its LAST contiguous run in set order (region_set.rs:584-606)"""
+        n = len(self)
+        if n == 0:
+            raise ValueError("get_max_end_per_chr: empty region set")
+        ids, e = self.chrom_ids, self.ends
+        heads = np.flatnonzero(np.r_[True, ids[1:] != ids[:-1]])
+        run_max = np.maximum.reduceat(e, heads)
+        names = self.chrom_names
+        return {names[int(ids[h])]: int(m) for h, m in zip(heads, run_max)}
+
+
+class ChromosomeStatistics:
+    """gtars.models.ChromosomeStatistics -- one chromosome's entry of ``RegionSet.chromosome_statistics()``, read-only
+    (gtars-python/src/models/region_set.rs:13-24, 531-573)."""
+
+    __slots__ = ("_v",)
+    _FIELDS = ("chromosome", "number_of_regions", "start_nucleotide_position", "end_nucleotide_position",
+               "minimum_region_length", "maximum_region_length", "mean_region_length", "median_region_length")
+
+    def __init__(self, chromosome, number_of_regions, start_nucleotide_position, end_nucleotide_position,
+                 minimum_region_length, maximum_region_length, mean_region_length, median_region_length):
+        object.__setattr__(self, "_v", (str(chromosome), int(number_of_regions), int(start_nucleotide_position),
+                                        int(end_nucleotide_position), int(minimum_region_length),
+                                        int(maximum_region_length), float(mean_region_length),
+                                        float(median_region_length)))
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"attribute '{name}' of 'ChromosomeStatistics' objects is not writable")
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, ChromosomeStatistics) and self._v == other._v
+
+    def __hash__(self):
+        return hash(self._v)
+
+    def __repr__(self) -> str:
+        return "ChromosomeStatistics(" + ", ".join(f"{k}={v!r}" for k, v in zip(self._FIELDS, self._v)) + ")"
+
+
+def _field(i):
+    return property(lambda self: self._v[i])
+
+
+for _i, _name in enumerate(ChromosomeStatistics._FIELDS):
+    setattr(ChromosomeStatistics, _name, _field(_i))
+del _i, _name
+
+
+def _u32(x, what: str) -> int:
+    if not 0 <= int(x) <= _U32_MAX:
+        raise OverflowError(f"{what} must fit in u32")
+    return int(x)
+
+
+def _sizes(chrom_sizes) -> Tuple[object, np.ndarray, list, int]:
+    """chrom_sizes (a dict name -> u32) as the parallel arrays the C ABI takes"""
+    names = [str(k) for k in chrom_sizes]
+    sizes = np.array([_u32(chrom_sizes[k], "chromosome size") for k in chrom_sizes], dtype=np.uint32)
+    arr, keep = cstr_array(names)
+    return arr, sizes, keep, len(names)
+
+
+def _take(p: C.c_void_p, ctype, n: int) -> list:
+    """a library-allocated array as a list, freed"""
+    try:
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(n,)).tolist() if n else []
+    finally:
+        if p.value:
+            lib.gtars_free(p)
 
 
 class RegionSetList:

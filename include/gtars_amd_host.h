@@ -103,6 +103,49 @@ gtars_status gtars_regionset_cluster(const gtars_regionset_t *rs, uint32_t max_g
 gtars_status gtars_regionset_pairwise_jaccard(const gtars_regionset_t *const *sets, uint64_t n, double *out);
 
 /* ------------------------------------------------------------------------
+ * Structural operations and region-set statistics (gtars-core region_set.rs,
+ * gtars-genomicdist/src/{consensus,statistics}.rs; gtars-python/src/models/
+ * region_set.rs:288-531, genomic_distributions/tools.rs:157-190), on the
+ * current device.  chrom_sizes are parallel arrays names[n_sizes] /
+ * sizes[n_sizes]; a later entry of a name replaces an earlier one.  Arrays
+ * returned through pointers: gtars_free each.
+ * ---------------------------------------------------------------------- */
+/* disjoin (region_set.rs:1051-1090): the pieces between consecutive boundaries (every start and end) of a chromosome that
+ * some region with start <= piece.start and piece.end <= end covers (inverted and zero-width regions add boundaries, never
+ * coverage); sorted by (chr, start).  Up to 2n boundaries: more than the device set operations' limit is an error. */
+gtars_status gtars_regionset_disjoin(const gtars_regionset_t *rs, gtars_regionset_t **out);
+/* gaps (region_set.rs:786-878): leading, inter-run and trailing gaps of reduce(rs), clipped to the chromosome size, and
+ * [0, size) for a sized chromosome without regions; nothing for size 0 or unsized chromosomes.  Ordered by
+ * chrom_karyotype_key (gtars-core/src/utils.rs:359-370), start, then name bytewise (the reference leaves names that share
+ * a key in hash-map order). */
+gtars_status gtars_regionset_gaps(const gtars_regionset_t *rs, const char *const *names, const uint32_t *sizes,
+                                  uint64_t n_sizes, gtars_regionset_t **out);
+/* consensus (consensus.rs:29-68): *out_union = reduce(concat(sets)); (*out_count)[i] = the number of sets with a region
+ * that AIList any_overlaps reports for union region i (start < u.end && u.start < end) */
+gtars_status gtars_regionset_consensus(const gtars_regionset_t *const *sets, uint64_t n, gtars_regionset_t **out_union,
+                                       uint32_t **out_count);
+/* calc_neighbor_distances (statistics.rs:258-285): chromosomes in order of first appearance (region_set.rs:399-407),
+ * regions sorted by (start, end), every next.start - prev.end > 0 as i64; chromosomes with < 2 regions skipped */
+gtars_status gtars_regionset_neighbor_distances(const gtars_regionset_t *rs, int64_t **out, uint64_t *out_n);
+/* calc_nearest_neighbors (statistics.rs:287-316): the same walk, one value per region: min of the gaps to its left and
+ * right neighbours, each clamped at 0 */
+gtars_status gtars_regionset_nearest_neighbors(const gtars_regionset_t *rs, uint32_t **out, uint64_t *out_n);
+/* distribution (statistics.rs:143-256, region_set.rs:322-349): regions counted per bin of their midpoint
+ * start + (u32)(end - start) / 2.  has_sizes == 0: bin_size = max(max_end / n_bins, 1) from get_max_end_per_chr
+ * (region_set.rs:584-606: the last contiguous run of a chromosome), bins end at min(start + bin_size, that end).
+ * has_sizes: regions on unsized chromosomes or with midpoint >= size skipped, rid clamped to n_bins - 1, the last bin
+ * ends at the size, n_bins == 0 gives nothing.  *out_rows: *out_n rows of 5 u32 (chromosome id of rs, start, end, n,
+ * rid), sorted by (chr, start). */
+gtars_status gtars_regionset_distribution(const gtars_regionset_t *rs, uint32_t n_bins, int has_sizes,
+                                          const char *const *names, const uint32_t *sizes, uint64_t n_sizes,
+                                          uint32_t **out_rows, uint64_t *out_n);
+/* chromosome_statistics (statistics.rs:88-141): one entry per chromosome of rs, names bytewise.  *out_rows: rows of 6
+ * u32 (chromosome id of rs, number of regions, min start, max end, min width, max width); *out_f64: rows of 2 (mean
+ * width = u64 sum / count, median width; an even count adds the two middle widths in wrapping u32 first). */
+gtars_status gtars_regionset_chromosome_statistics(const gtars_regionset_t *rs, uint32_t **out_rows, double **out_f64,
+                                                   uint64_t *out_n);
+
+/* ------------------------------------------------------------------------
  * Tokenizer  (gtars-tokenizers/src/tokenizer.rs:36-279, universe/mod.rs,
  * config.rs, utils/mod.rs:34-99, utils/special_tokens.rs)
  * ---------------------------------------------------------------------- */
