@@ -166,6 +166,13 @@ _HOST_SIG = {
     "gtars_regionset_nearest_neighbors": (C.c_int, [vp, pp, pu64]),
     "gtars_regionset_distribution": (C.c_int, [vp, u32, C.c_int, vp, vp, u64, pp, pu64]),
     "gtars_regionset_chromosome_statistics": (C.c_int, [vp, pp, pp, pu64]),
+    "gtars_gtf_read": (C.c_int, [cstr, C.c_int, C.c_int, pp, pp, pp]),
+    "gtars_regionset_stranded_reduce": (C.c_int, [vp, vp, vp, pp, pp]),
+    "gtars_tss_index_from_regionset": (C.c_int, [vp, pp]),
+    "gtars_tss_index_free": (None, [vp]),
+    "gtars_tss_index_len": (u64, [vp]),
+    "gtars_tss_index_device": (C.c_int, [vp]),
+    "gtars_tss_index_distances": (C.c_int, [vp, vp, vp, vp]),
     "gtars_tokenizer_from_auto": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_config": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_bed": (C.c_int, [cstr, pp]),

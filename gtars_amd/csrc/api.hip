@@ -239,25 +239,6 @@ void prof_note_fact(const char *name) {
     if (g_prof_on) g_prof_entries[prof_entry(name)].launches += 1;
 }
 
-// the calling thread's current device for the scope: `want`, and what it was before again afterwards
-struct DeviceScope {
-    int before = -1;
-    bool switched = false;
-    gtars_status st = GTARS_OK;
-    explicit DeviceScope(int want) {
-        if (want < 0) return;
-        hipError_t e = hipGetDevice(&before);
-        if (e == hipSuccess && before != want) {
-            e = hipSetDevice(want);
-            switched = e == hipSuccess;
-        }
-        if (e != hipSuccess) st = hip_fail(e, "select the handle's device", __FILE__, __LINE__);
-    }
-    ~DeviceScope() {
-        if (switched) (void)hipSetDevice(before);
-    }
-};
-
 // Device affinity of a handle (round 6: every entry point that takes one).  A handle's device memory -- and everything built
 // lazily on it later -- lives on the device that was current when it was built.
 //  * host-buffer entry points run ON that device whatever the calling thread's current device is, and put the caller's device

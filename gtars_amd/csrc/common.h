@@ -40,6 +40,25 @@ gtars_status hip_fail(hipError_t e, const char *what, const char *file, int line
 
 gtars_status require_device();
 
+// the calling thread's current device for the scope: `want`, and what it was before again afterwards
+struct DeviceScope {
+    int before = -1;
+    bool switched = false;
+    gtars_status st = GTARS_OK;
+    explicit DeviceScope(int want) {
+        if (want < 0) return;
+        hipError_t e = hipGetDevice(&before);
+        if (e == hipSuccess && before != want) {
+            e = hipSetDevice(want);
+            switched = e == hipSuccess;
+        }
+        if (e != hipSuccess) st = hip_fail(e, "select the handle's device", __FILE__, __LINE__);
+    }
+    ~DeviceScope() {
+        if (switched) (void)hipSetDevice(before);
+    }
+};
+
 // ---- owning device memory -----------------------------------------------------
 // n elements of T on the current device, freed with the buffer; move-only.  Every allocation is at least
 // max(n, 1) * sizeof(T) + 32 bytes and never fewer than 256: kernels stage whole 16-byte vectors, so the last vector

@@ -36,6 +36,7 @@
 #include "frag_device.h"
 #include "inflate_fast.h"
 #include "setops.h"
+#include "annot.h"
 
 namespace gtars {
 gtars_status fail(gtars_status st, const std::string &msg);
@@ -1391,6 +1392,310 @@ gtars_status gtars_regionset_chromosome_statistics(const gtars_regionset_t *rs, 
         *out_f64 = pf;
         *out_n = rows.size() / 6;
         return GTARS_OK;
+    });
+}
+
+}  // extern "C"
+
+// ================================================== Gene models and TSS / feature distances (K10)
+// GeneModel::from_gtf's reader (gtars-genomicdist/src/partitions.rs:123-250) on host threads, the stranded reduce of
+// stranded_region_set.rs:84-135 as K8's device reduce with the strand folded into the segment key, and the TssIndex handle
+// whose distances annot.hip computes (models.rs:516-690).
+
+struct gtars_tss_index {
+    std::vector<std::string> names;  // the index set's chromosome names (dictionary order)
+    std::unordered_map<std::string, uint32_t> id;
+    std::vector<uint32_t> chrom, start, end;  // the snapshot, dropped once the device index exists
+    uint64_t n = 0;
+    std::mutex mu;  // guards the lazy build
+    gtars::TssDevice *dev = nullptr;
+    ~gtars_tss_index() { gtars::tss_free(dev); }
+};
+
+namespace {
+
+// std::str::from_utf8's rules: no overlong forms, no surrogates, nothing above U+10FFFF
+bool valid_utf8(const unsigned char *p, size_t n) {
+    size_t i = 0;
+    while (i < n) {
+        if (p[i] < 0x80) {
+            ++i;
+            continue;
+        }
+        const unsigned c = p[i];
+        size_t k;
+        unsigned lo = 0x80, hi = 0xBF;
+        if (c >= 0xC2 && c <= 0xDF) k = 1;
+        else if (c == 0xE0) k = 2, lo = 0xA0;
+        else if (c >= 0xE1 && c <= 0xEC) k = 2;
+        else if (c == 0xED) k = 2, hi = 0x9F;
+        else if (c >= 0xEE && c <= 0xEF) k = 2;
+        else if (c == 0xF0) k = 3, lo = 0x90;
+        else if (c >= 0xF1 && c <= 0xF3) k = 3;
+        else if (c == 0xF4) k = 3, hi = 0x8F;
+        else return false;
+        if (i + k >= n) return false;
+        if (p[i + 1] < lo || p[i + 1] > hi) return false;
+        for (size_t j = 2; j <= k; ++j)
+            if (p[i + j] < 0x80 || p[i + j] > 0xBF) return false;
+        i += k + 1;
+    }
+    return true;
+}
+
+// <u32 as FromStr>::from_str: an optional '+', then ASCII digits; the first fault in reading order decides the error
+const char *rust_parse_u32(const char *p, size_t n, uint32_t &out) {
+    if (n == 0) return "cannot parse integer from empty string";
+    size_t i = p[0] == '+' ? 1 : 0;
+    if (i == n) return "invalid digit found in string";
+    uint64_t v = 0;
+    for (; i < n; ++i) {
+        const unsigned d = (unsigned char)p[i] - '0';
+        if (d > 9) return "invalid digit found in string";
+        v = v * 10 + d;
+        if (v > 0xFFFFFFFFull) return "number too large to fit in target type";
+    }
+    out = (uint32_t)v;
+    return nullptr;
+}
+
+struct GtfChunk {
+    std::vector<std::string> names;  // chunk-local dictionary, first-seen order
+    std::unordered_map<std::string, uint32_t> ids;
+    std::vector<uint32_t> chrom, start, end;
+    std::vector<uint8_t> strand, feature;
+    std::string err;  // the chunk's first error (rows after it are never read)
+};
+
+// the lines of text[b, e) (e is a line start or the end of the text)
+void gtf_scan(const std::string &text, size_t b, size_t e, bool filter_pc, bool convert, GtfChunk &c) {
+    static const char *const kFeatures[] = {"gene", "exon", "three_prime_utr", "five_prime_utr", "UTR", "CDS"};
+    const char *s = text.data();
+    std::string name;
+    while (b < e) {
+        const char *nl = (const char *)memchr(s + b, '\n', e - b);
+        const size_t le = nl ? (size_t)(nl - s) : e;  // BufRead::lines: "\n" or "\r\n" stripped
+        size_t ce = le;
+        if (nl && ce > b && s[ce - 1] == '\r') --ce;
+        const size_t lb = b;
+        b = nl ? le + 1 : e;
+        if (!valid_utf8((const unsigned char *)s + lb, le - lb)) {
+            c.err = "stream did not contain valid UTF-8";
+            return;
+        }
+        if (ce > lb && s[lb] == '#') continue;
+        size_t fb[10], fe[10];  // the first 9 fields
+        int nf = 0;
+        size_t p = lb;
+        for (;;) {
+            const char *t = (const char *)memchr(s + p, '\t', ce - p);
+            const size_t q = t ? (size_t)(t - s) : ce;
+            if (nf < 9) fb[nf] = p, fe[nf] = q;
+            ++nf;
+            if (!t || nf >= 9) break;
+            p = q + 1;
+        }
+        if (nf < 9) continue;
+        const std::string_view ft(s + fb[2], fe[2] - fb[2]);
+        int f = -1;
+        for (int k = 0; k < 6; ++k)
+            if (ft == kFeatures[k]) f = k;
+        if (f < 0) continue;
+        if (filter_pc) {
+            const std::string_view at(s + fb[8], fe[8] - fb[8]);
+            if (at.find("gene_biotype \"protein_coding\"") == std::string_view::npos &&
+                at.find("gene_type \"protein_coding\"") == std::string_view::npos)
+                continue;
+        }
+        uint32_t st, en;
+        if (const char *m = rust_parse_u32(s + fb[3], fe[3] - fb[3], st)) {
+            c.err = std::string("Parsing GTF start: ") + m;
+            return;
+        }
+        if (const char *m = rust_parse_u32(s + fb[4], fe[4] - fb[4], en)) {
+            c.err = std::string("Parsing GTF end: ") + m;
+            return;
+        }
+        name.assign(s + fb[0], fe[0] - fb[0]);
+        if (convert && name.compare(0, 3, "chr") != 0) name.insert(0, "chr");
+        auto it = c.ids.find(name);
+        if (it == c.ids.end()) {
+            it = c.ids.emplace(name, (uint32_t)c.names.size()).first;
+            c.names.push_back(name);
+        }
+        c.chrom.push_back(it->second);
+        c.start.push_back(st ? st - 1 : 0);
+        c.end.push_back(en);
+        const char sc = fe[6] > fb[6] ? s[fb[6]] : '.';
+        c.strand.push_back(sc == '+' ? 0 : sc == '-' ? 1 : 2);
+        c.feature.push_back((uint8_t)f);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+gtars_status gtars_gtf_read(const char *path, int filter_protein_coding, int convert_ensembl_ucsc, gtars_regionset_t **out_rows,
+                            uint8_t **out_strand, uint8_t **out_feature) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!path || !out_rows || !out_strand || !out_feature) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_rows = nullptr;
+        *out_strand = *out_feature = nullptr;
+        const std::string p(path);
+        if (!is_regular_file(p)) return fail(GTARS_ERR_IO, "No such file or directory (os error 2): " + p);
+        std::string text, err;
+        if (ends_with(p, ".gz")) {
+            // MultiGzDecoder: gzip members only
+            std::string raw;
+            size_t n_raw = 0;
+            if (!read_file_padded(p, raw, n_raw)) return fail(GTARS_ERR_IO, "Failed to open file: \"" + p + "\": " + strerror(errno));
+            if (n_raw && (n_raw < 2 || (unsigned char)raw[0] != 0x1f || (unsigned char)raw[1] != 0x8b))
+                return fail(GTARS_ERR_IO, "invalid gzip header");
+        }
+        if (!read_all(p, text, err)) return fail(GTARS_ERR_IO, err);
+        // cut at line starts into up to 16 chunks of >= 1 MiB
+        const size_t n = text.size();
+        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_thread_budget(16), n >> 20));
+        std::vector<size_t> cut{0};
+        for (unsigned k = 1; k < nt; ++k) {
+            size_t at = std::max(cut.back(), n / nt * k);
+            const char *nl = at < n ? (const char *)memchr(text.data() + at, '\n', n - at) : nullptr;
+            at = nl ? (size_t)(nl - text.data()) + 1 : n;
+            cut.push_back(at);
+        }
+        cut.push_back(n);
+        std::vector<GtfChunk> chunks(cut.size() - 1);
+        const bool pc = filter_protein_coding != 0, cv = convert_ensembl_ucsc != 0;
+        if (chunks.size() == 1) {
+            gtf_scan(text, 0, n, pc, cv, chunks[0]);
+        } else {
+            std::vector<std::thread> th;
+            for (size_t k = 0; k < chunks.size(); ++k)
+                th.emplace_back([&, k] { gtf_scan(text, cut[k], cut[k + 1], pc, cv, chunks[k]); });
+            for (std::thread &t : th) t.join();
+        }
+        for (const GtfChunk &c : chunks)
+            if (!c.err.empty()) return fail(GTARS_ERR_PARSE, c.err);  // the first in file order
+        auto rs = std::make_unique<gtars_regionset>();
+        std::vector<uint8_t> strand, feature;
+        size_t total = 0;
+        for (const GtfChunk &c : chunks) total += c.chrom.size();
+        rs->chrom_ids.reserve(total);
+        rs->starts.reserve(total);
+        rs->ends.reserve(total);
+        strand.reserve(total);
+        feature.reserve(total);
+        for (const GtfChunk &c : chunks) {
+            std::vector<uint32_t> map(c.names.size());
+            for (size_t k = 0; k < map.size(); ++k) map[k] = rs->chroms.get_or_add(c.names[k]);
+            for (uint32_t id : c.chrom) rs->chrom_ids.push_back(map[id]);
+            rs->starts.insert(rs->starts.end(), c.start.begin(), c.start.end());
+            rs->ends.insert(rs->ends.end(), c.end.begin(), c.end.end());
+            strand.insert(strand.end(), c.strand.begin(), c.strand.end());
+            feature.insert(feature.end(), c.feature.begin(), c.feature.end());
+        }
+        rs->rest_off.assign(total, 0);
+        rs->has_rest.assign(total, 0);
+        if (const gtars_status e = to_malloc(strand, out_strand)) return e;
+        if (const gtars_status e = to_malloc(feature, out_feature)) {
+            free(*out_strand);
+            *out_strand = nullptr;
+            return e;
+        }
+        *out_rows = rs.release();
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_regionset_stranded_reduce(const gtars_regionset_t *rs, const uint8_t *strand, const uint8_t *keep,
+                                             gtars_regionset_t **out, uint8_t **out_strand) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out || !out_strand || (!strand && rs->size())) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        *out_strand = nullptr;
+        RankSpace sp;
+        sp.build({rs});
+        if (sp.size() > 0x7FFFFFFFu / 3) return fail(GTARS_ERR_INVALID_ARG, "too many chromosomes");
+        const std::vector<uint32_t> r = sp.ranks_of(rs);
+        std::vector<uint32_t> seg, st, en;
+        for (size_t i = 0; i < rs->size(); ++i) {
+            if (keep && !keep[i]) continue;
+            if (strand[i] > 2) return fail(GTARS_ERR_INVALID_ARG, "strand code out of range");
+            seg.push_back(r[i] * 3 + strand[i]);  // (chr bytewise, strand_ord): one segment key
+            st.push_back(rs->starts[i]);
+            en.push_back(rs->ends[i]);
+        }
+        gtars::SetOut o;
+        if (const gtars_status e = gtars::setops_reduce(gtars::SetCols{seg.data(), st.data(), en.data(), (uint64_t)seg.size()},
+                                                        sp.size() * 3, o))
+            return e;
+        std::vector<uint8_t> ostrand(o.rank.size());
+        for (size_t i = 0; i < o.rank.size(); ++i) {
+            ostrand[i] = (uint8_t)(o.rank[i] % 3);
+            o.rank[i] /= 3;
+        }
+        if (const gtars_status e = to_malloc(ostrand, out_strand)) return e;
+        *out = regionset_from(sp, o);
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_tss_index_from_regionset(const gtars_regionset_t *rs, gtars_tss_index_t **out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        auto ix = std::make_unique<gtars_tss_index>();
+        ix->names = rs->chroms.names;
+        for (uint32_t k = 0; k < ix->names.size(); ++k) ix->id.emplace(ix->names[k], k);
+        ix->chrom = rs->chrom_ids;
+        ix->start = rs->starts;
+        ix->end = rs->ends;
+        ix->n = rs->size();
+        *out = ix.release();
+        return GTARS_OK;
+    });
+}
+
+void gtars_tss_index_free(gtars_tss_index_t *ix) { delete ix; }
+uint64_t gtars_tss_index_len(const gtars_tss_index_t *ix) { return ix ? ix->n : 0; }
+int gtars_tss_index_device(const gtars_tss_index_t *ix) {
+    if (!ix) return -1;
+    std::lock_guard<std::mutex> lk(const_cast<gtars_tss_index_t *>(ix)->mu);
+    return gtars::tss_device(ix->dev);
+}
+
+gtars_status gtars_tss_index_distances(gtars_tss_index_t *ix, const gtars_regionset_t *query, uint32_t *out_abs,
+                                       int64_t *out_signed) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!ix || !query || ((!out_abs || !out_signed) && query->size())) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        gtars::TssDevice *dev;
+        {
+            std::lock_guard<std::mutex> lk(ix->mu);
+            if (!ix->dev) {
+                if (const gtars_status e = gtars::tss_build(ix->chrom.data(), ix->start.data(), ix->end.data(), ix->n,
+                                                            (uint32_t)ix->names.size(), &ix->dev))
+                    return e;
+                std::vector<uint32_t>().swap(ix->chrom);
+                std::vector<uint32_t>().swap(ix->start);
+                std::vector<uint32_t>().swap(ix->end);
+            }
+            dev = ix->dev;
+        }
+        // iter_chroms: chromosomes ranked by first appearance in the query
+        std::vector<uint32_t> fa(query->chroms.names.size(), GTARS_UNKNOWN_CHROM), rank(query->size()), seg_of;
+        bool grouped = true;
+        for (size_t i = 0; i < query->size(); ++i) {
+            uint32_t &f = fa[query->chrom_ids[i]];
+            if (f == GTARS_UNKNOWN_CHROM) {
+                f = (uint32_t)seg_of.size();
+                auto it = ix->id.find(query->chroms.names[query->chrom_ids[i]]);
+                seg_of.push_back(it == ix->id.end() ? GTARS_UNKNOWN_CHROM : it->second);
+            }
+            rank[i] = f;
+            grouped = grouped && (i == 0 || f >= rank[i - 1]);
+        }
+        return gtars::tss_distances(dev, rank.data(), query->starts.data(), query->ends.data(), query->size(), seg_of, grouped,
+                                    out_abs, out_signed);
     });
 }
 

@@ -19,6 +19,12 @@ The structural operations and statistics of region_set.rs:288-531 are here too: 
 ``ChromosomeStatistics``) run on the GPU (csrc/setops.hip, K9); ``trim``, ``promoters``, ``pintersect``, ``concat``,
 ``widths`` / ``region_widths``, ``mean_region_width`` and ``get_max_end_per_chr`` are elementwise host arithmetic.
 ``gaps`` pins the order the reference leaves open among names that share a karyotype key (start, then name bytewise).
+
+The annotation side of the reference's ``gtars.models`` (gtars-python/src/models/{tss_index,gene_model,gda}.rs) is here
+too: ``TssIndex`` (distances to the nearest TSS / feature midpoint on the GPU, csrc/annot.hip, K10), ``GeneModel`` and
+``GenomicDistAnnotation`` (a GTF read by host threads, genes and exons merged by a strand-aware reduce on the GPU).
+``PartitionList``, ``GenomicDistAnnotation.partition_list`` / ``load_bin``, ``GenomeAssembly``, ``BinaryGenomeAssembly``
+and ``SignalMatrix`` are not provided.
 """
 from __future__ import annotations
 
@@ -481,3 +487,182 @@ class RegionSetList:
         handles = (C.c_void_p * max(n, 1))(*[s._h for s in self._sets])
         check(lib.gtars_regionset_pairwise_jaccard(C.cast(handles, C.c_void_p), n, ptr(out)))
         return out.tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# TSS / feature distances and gene models (gtars-genomicdist/src/models.rs:516-690, partitions.rs:123-340,
+# stranded_region_set.rs:84-135; gtars-python/src/models/{tss_index,gene_model,gda}.rs)
+_I64_MAX = (1 << 63) - 1
+_GTF_GENE, _GTF_EXON = 0, 1  # feature codes of gtars_gtf_read
+_MINUS = 1  # strand codes: 0 '+', 1 '-', 2 unstranded
+
+
+class TssIndex:
+    """gtars.models.TssIndex -- the midpoints start + width / 2 (wrapping u32) of a region set, sorted per chromosome.
+
+    Construction and ``len`` stay on the host; the device index is built at the first distance call, on the device
+    current then, and every later call runs there.  Both distance calls return one value per query region, chromosomes
+    in order of first appearance in the query and set order within one (for a set read from a BED file: set order)."""
+
+    def __init__(self, path):
+        try:
+            rs = RegionSet(str(path))
+        except Exception:
+            # TssIndex::try_from(path) maps every read error to TSSContentError, whose message drops the cause
+            raise ValueError("No TSS's found for region. Double-check your index!") from None
+        self._h = None
+        self._attach(rs)
+
+    @staticmethod
+    def from_regionset(rs: RegionSet) -> "TssIndex":
+        self = TssIndex.__new__(TssIndex)
+        self._h = None
+        self._attach(rs)
+        return self
+
+    def _attach(self, rs: RegionSet) -> None:
+        h = C.c_void_p()
+        check(lib.gtars_tss_index_from_regionset(rs._h, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                lib.gtars_tss_index_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(lib.gtars_tss_index_len(self._h))
+
+    def __repr__(self) -> str:
+        return f"RegionSet with {len(self)} regions."
+
+    __str__ = __repr__
+
+    def _distances(self, rs: RegionSet) -> Tuple[np.ndarray, np.ndarray]:
+        n = len(rs)
+        out_abs = np.empty(n, dtype=np.uint32)
+        out_signed = np.empty(n, dtype=np.int64)
+        check(lib.gtars_tss_index_distances(self._h, rs._h, ptr(out_abs), ptr(out_signed)))
+        return out_abs, out_signed
+
+    def calc_tss_distances(self, rs: RegionSet) -> List[int]:
+        """distance to the nearest midpoint (0 on an exact hit); 4294967295 on a chromosome the index lacks"""
+        return self._distances(rs)[0].tolist()
+
+    def feature_distances(self, rs: RegionSet) -> List[Optional[float]]:
+        """nearest midpoint - query midpoint as a float, the upstream one on a tie; None on a chromosome the index lacks"""
+        d = self._distances(rs)[1]
+        missing = d == _I64_MAX
+        vals = d.astype(np.float64).tolist()
+        if missing.any():
+            for k in np.flatnonzero(missing).tolist():
+                vals[k] = None
+        return vals
+
+
+class _Stranded:
+    """a strand-aware reduced region set: (chr bytewise, strand, start) order, strand codes 0 '+', 1 '-', 2 other"""
+
+    __slots__ = ("regions", "strands")
+
+    def __init__(self, regions: RegionSet, strands: np.ndarray):
+        self.regions = regions
+        self.strands = strands
+
+    def __len__(self) -> int:
+        return len(self.strands)
+
+
+def _stranded_reduce(rows: RegionSet, strand: np.ndarray, keep: np.ndarray) -> _Stranded:
+    h, p = C.c_void_p(), C.c_void_p()
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    check(lib.gtars_regionset_stranded_reduce(rows._h, ptr(strand), ptr(keep), C.byref(h), C.byref(p)))
+    out = RegionSet._from_handle(h)
+    try:
+        n = len(out)
+        s = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n,)).copy() if n else np.zeros(0, np.uint8)
+    finally:
+        if p.value:
+            lib.gtars_free(p)
+    return _Stranded(out, s)
+
+
+def _read_gtf(path, filter_protein_coding: bool, convert_ensembl_ucsc: bool):
+    h, ps, pf = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    st = lib.gtars_gtf_read(str(path).encode(), int(bool(filter_protein_coding)), int(bool(convert_ensembl_ucsc)),
+                            C.byref(h), C.byref(ps), C.byref(pf))
+    if st != 0:
+        raise ValueError(_lib.last_error())  # GeneModel::from_gtf: every error is a ValueError (gene_model.rs)
+    rows = RegionSet._from_handle(h)
+    n = len(rows)
+    cols = []
+    for p in (ps, pf):
+        try:
+            cols.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n,)).copy() if n else np.zeros(0, np.uint8))
+        finally:
+            if p.value:
+                lib.gtars_free(p)
+    return rows, cols[0], cols[1]
+
+
+class GeneModel:
+    """gtars.models.GeneModel -- genes and exons of a GTF, each merged by a strand-aware reduce.
+
+    ``from_gtf`` reads the GTF on host threads (a malformed number or a line that is not UTF-8 raises ``ValueError``
+    before any device work) and reduces on the GPU.  The reader keeps UTR and CDS rows too, but they only feed the
+    reference's partitions (its ``PendingUtr`` / exon-minus-CDS UTR derivation), which are not provided here."""
+
+    def __init__(self, *args, **kwargs):
+        raise TypeError("No constructor defined for GeneModel")
+
+    @staticmethod
+    def from_gtf(path: str, filter_protein_coding: bool = True, convert_ensembl_ucsc: bool = True) -> "GeneModel":
+        rows, strand, feature = _read_gtf(path, filter_protein_coding, convert_ensembl_ucsc)
+        self = GeneModel.__new__(GeneModel)
+        self._genes = _stranded_reduce(rows, strand, feature == _GTF_GENE)
+        self._exons = _stranded_reduce(rows, strand, feature == _GTF_EXON)
+        return self
+
+    @property
+    def n_genes(self) -> int:
+        return len(self._genes)
+
+    @property
+    def n_exons(self) -> int:
+        return len(self._exons)
+
+    def __repr__(self) -> str:
+        return f"GeneModel(n_genes={self.n_genes}, n_exons={self.n_exons})"
+
+
+class GenomicDistAnnotation:
+    """gtars.models.GenomicDistAnnotation -- a GeneModel and the TSS index of its genes."""
+
+    def __init__(self, *args, **kwargs):
+        raise TypeError("No constructor defined for GenomicDistAnnotation")
+
+    @staticmethod
+    def from_gtf(path: str, filter_protein_coding: bool = True, convert_ensembl_ucsc: bool = True) -> "GenomicDistAnnotation":
+        self = GenomicDistAnnotation.__new__(GenomicDistAnnotation)
+        self._model = GeneModel.from_gtf(path, filter_protein_coding, convert_ensembl_ucsc)
+        return self
+
+    def gene_model(self) -> GeneModel:
+        return self._model
+
+    def tss_index(self) -> TssIndex:
+        """one TSS per reduced gene: [end - 1, end) (saturating) on the minus strand, [start, start + 1) otherwise"""
+        g = self._model._genes
+        rs = g.regions
+        s, e = rs.starts, rs.ends
+        p = np.where(g.strands == _MINUS, np.maximum(e, 1) - 1, s).astype(np.uint32)
+        names = np.array(rs.chrom_names, dtype=object)
+        ids = rs.chrom_ids
+        chrs = names[ids].tolist() if len(ids) else []
+        return TssIndex.from_regionset(RegionSet.from_vectors(chrs, p, p + np.uint32(1)))
+
+    def __repr__(self) -> str:
+        return f"GenomicDistAnnotation(n_genes={self._model.n_genes}, n_exons={self._model.n_exons})"

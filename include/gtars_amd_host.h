@@ -146,6 +146,43 @@ gtars_status gtars_regionset_chromosome_statistics(const gtars_regionset_t *rs, 
                                                    uint64_t *out_n);
 
 /* ------------------------------------------------------------------------
+ * Gene models and TSS / feature distances (gtars-genomicdist/src/
+ * {models.rs:516-690, partitions.rs:123-340, stranded_region_set.rs:84-135};
+ * gtars-python/src/models/{tss_index,gene_model,gda}.rs).  Strands are
+ * coded 0 = '+', 1 = '-', 2 = unstranded (the reference's strand_ord).
+ * ---------------------------------------------------------------------- */
+/* GeneModel::from_gtf's reader (partitions.rs:123-250): plain text, or gzip (several members) when the path ends in ".gz".
+ * Every line must be UTF-8; lines starting with '#' and rows of fewer than 9 TAB-separated fields are skipped; only the
+ * feature types gene, exon, three_prime_utr, five_prime_utr, UTR and CDS are kept, and with filter_protein_coding only rows
+ * whose 9th field contains `gene_biotype "protein_coding"` or `gene_type "protein_coding"`; convert_ensembl_ucsc prefixes
+ * "chr" to names without it; start = (u32 parse of field 4).saturating_sub(1), end = u32 parse of field 5 (GTARS_ERR_PARSE
+ * "Parsing GTF start: ..." / "Parsing GTF end: ..."); strand from the first character of field 7.  Host only.
+ * *out_rows: the kept rows in file order (no rest); *out_strand and *out_feature (gtars_free each): one code per row,
+ * features 0 gene, 1 exon, 2 three_prime_utr, 3 five_prime_utr, 4 UTR, 5 CDS. */
+gtars_status gtars_gtf_read(const char *path, int filter_protein_coding, int convert_ensembl_ucsc, gtars_regionset_t **out_rows,
+                            uint8_t **out_strand, uint8_t **out_feature);
+/* StrandedRegionSet::reduce (stranded_region_set.rs:84-135) of the rows i of rs with keep[i] != 0 (keep NULL: all), on the
+ * current device: stable sort by (chr bytewise, strand, start), merge while same chr and strand and start <= current end.
+ * *out (sorted that way, no rest) and *out_strand (gtars_free) */
+gtars_status gtars_regionset_stranded_reduce(const gtars_regionset_t *rs, const uint8_t *strand, const uint8_t *keep,
+                                             gtars_regionset_t **out, uint8_t **out_strand);
+
+typedef struct gtars_tss_index gtars_tss_index_t;
+/* TssIndex::try_from(RegionSet) (models.rs:525-549): a snapshot of rs; host only -- the device index (midpoints
+ * start + (u32)(end - start) / 2 sorted per chromosome, duplicates kept) is built at the first distance call, on the
+ * device current then, which the handle keeps (scope-or-refuse: later calls run there) */
+gtars_status gtars_tss_index_from_regionset(const gtars_regionset_t *rs, gtars_tss_index_t **out);
+void gtars_tss_index_free(gtars_tss_index_t *ix);
+uint64_t gtars_tss_index_len(const gtars_tss_index_t *ix); /* regions the index was built from */
+int gtars_tss_index_device(const gtars_tss_index_t *ix);   /* -1 until the first distance call */
+/* calc_tss_distances and calc_feature_distances (models.rs:588-690) of query, in one device pass.  Results come by
+ * chromosome in order of first appearance in query (iter_chroms), set order within one.  out_abs[len(query)]: distance
+ * to the nearest midpoint, 0 on an exact hit, UINT32_MAX on a chromosome the index lacks; out_signed[len(query)]:
+ * nearest midpoint - query midpoint, the left neighbour on a tie, INT64_MAX on a chromosome the index lacks. */
+gtars_status gtars_tss_index_distances(gtars_tss_index_t *ix, const gtars_regionset_t *query, uint32_t *out_abs,
+                                       int64_t *out_signed);
+
+/* ------------------------------------------------------------------------
  * Tokenizer  (gtars-tokenizers/src/tokenizer.rs:36-279, universe/mod.rs,
  * config.rs, utils/mod.rs:34-99, utils/special_tokens.rs)
  * ---------------------------------------------------------------------- */
