@@ -251,6 +251,9 @@ _DEBUG_SIG = {
     "gtars_debug_reload_env": (None, []),
     "gtars_debug_set_handle_device": (C.c_int, [vp, C.c_int, C.c_int]),
     "gtars_debug_inflate_streams": (C.c_int, [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+    "gtars_debug_sort_perm": (C.c_int, [vp, vp, vp, u64, u32, vp]),
+    "gtars_debug_scan_u32": (C.c_int, [vp, u64, vp]),
+    "gtars_debug_seg_max": (C.c_int, [vp, vp, vp, u64, u32, C.c_int, vp]),
 }
 
 # every symbol the headers declare must resolve -- fail loudly otherwise (GTARS_AMD_LIB_OLDER=1, A/B tooling only: an older
@@ -335,3 +338,35 @@ def reload_env() -> None:
     """The library reads its GTARS_* switches ONCE, into a snapshot taken at first use; a process that changes one afterwards
     (tests, A/B harnesses) calls this to make the library take a new snapshot.  No library call may be in flight."""
     lib.gtars_debug_reload_env()
+
+
+# -- the device primitives through their test entries (include/gtars_amd_debug.h) --------------------------------------
+def debug_sort_perm(chrom, k1, k2, n_chrom: int) -> np.ndarray:
+    """perm such that (chrom, k1, [k2], input row) ascends, from the device radix sort"""
+    chrom, k1 = as_u32(chrom), as_u32(k1)
+    k2 = None if k2 is None else as_u32(k2)
+    if len(k1) != len(chrom) or (k2 is not None and len(k2) != len(chrom)):
+        raise ValueError("key columns must have the same length")
+    perm = np.zeros(len(chrom), dtype=np.uint32)
+    check(lib.gtars_debug_sort_perm(ptr(chrom), ptr(k1), ptr(k2) if k2 is not None else None, len(chrom), int(n_chrom), ptr(perm)))
+    return perm
+
+
+def debug_scan_u32(counts) -> np.ndarray:
+    """n + 1 exclusive u64 offsets of n u32 counts, from the device's three-phase scan"""
+    counts = as_u32(counts)
+    out = np.zeros(len(counts) + 1, dtype=np.uint64)
+    check(lib.gtars_debug_scan_u32(ptr(counts), len(counts), ptr(out)))
+    return out
+
+
+def debug_seg_max(seg, val, start=None, gap: int = 0, inclusive: bool = True) -> np.ndarray:
+    """the segmented max-scan: the running maximum since the segment head (inclusive), or the run-opening flags"""
+    seg, val = as_u32(seg), as_u32(val)
+    start = None if start is None else as_u32(start)
+    if len(val) != len(seg) or (start is not None and len(start) != len(seg)):
+        raise ValueError("columns must have the same length")
+    out = np.zeros(len(seg), dtype=np.uint32)
+    check(lib.gtars_debug_seg_max(ptr(seg), ptr(val), ptr(start) if start is not None else None, len(seg), int(gap),
+                                  1 if inclusive else 0, ptr(out)))
+    return out

@@ -269,18 +269,6 @@ static gtars_status require_handle_device(int handle_device) {
 
 using namespace gtars;
 
-// runs f(), turning C++ exceptions into a status (nothing may unwind through the extern "C" boundary)
-template <class F>
-static gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
-
 // K1 policy: large builds are ordered by the device radix sort, small ones by std::stable_sort
 // (identical results; GTARS_DEVICE_SORT=0/1 forces one path, used by the tests)
 static bool use_device_sort(u64 n) {

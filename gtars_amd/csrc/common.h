@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -39,6 +40,18 @@ gtars_status hip_fail(hipError_t e, const char *what, const char *file, int line
     } while (0)
 
 gtars_status require_device();
+
+// runs f(), turning C++ exceptions into a status (nothing may unwind through the extern "C" boundary)
+template <class F>
+inline gtars_status guarded(F &&f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    } catch (const std::exception &e) {
+        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
+    }
+}
 
 // the calling thread's current device for the scope: `want`, and what it was before again afterwards
 struct DeviceScope {

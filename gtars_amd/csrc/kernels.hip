@@ -20,6 +20,7 @@
 //   min-overlap filter  gtars-overlaprs/src/multi_chrom_overlapper.rs:483-563
 //   IGD hit rule        gtars-igd/src/igd.rs:504-540, 753-847
 #include "common.h"
+#include "../../include/gtars_amd_debug.h"
 #include "scan.h"
 
 namespace gtars {
@@ -171,20 +172,41 @@ __global__ void __launch_bounds__(1024) k_scan_partials(u64 *__restrict__ partia
     if (threadIdx.x == 0) partials[np] = carry_s;
 }
 
+// Exclusive scan across the workgroup of one value < 2^35 per thread (the sum of SCAN_IPT u32 counts), exact in u64: a tile of
+// large counts sums past 2^32, so a u32 prefix would wrap inside the tile while the tile bases stay right.  The low 24 bits and
+// the bits above them are scanned per wave as two u32 on the DPP path (64 x 2^24 and 64 x 2^11 stay below 2^32) and the wave
+// totals are added in u64.  lds: 2 * TPB/64.
+__device__ __forceinline__ u64 scan_tile_exclusive_u64(u64 x, u32 *lds) {
+    constexpr int NW = SCAN_TPB / 64;
+    static_assert(SCAN_IPT <= 8 && SCAN_TPB <= 256, "per-thread sums must stay below 2^35 and the 24-bit halves below 2^32");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 lo = (u32)x & 0xFFFFFFu, hi = (u32)(x >> 24);
+    const u32 ilo = wave_inclusive_scan_u32(lo, lane), ihi = wave_inclusive_scan_u32(hi, lane);
+    if (lane == 63) {
+        lds[wave] = ilo;
+        lds[NW + wave] = ihi;
+    }
+    __syncthreads();
+    u64 base = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w)
+        if (w < wave) base += (u64)lds[w] + ((u64)lds[NW + w] << 24);
+    return base + (u64)(ilo - lo) + ((u64)(ihi - hi) << 24);
+}
+
 __global__ void __launch_bounds__(SCAN_TPB)
 k_scan_apply(const u32 *__restrict__ counts, u64 n, const u64 *__restrict__ partials, u64 np,
              u64 *__restrict__ offsets) {
-    __shared__ u32 lds[4];
+    __shared__ u32 lds[2 * (SCAN_TPB / 64)];
     const u64 base = (u64)blockIdx.x * SCAN_TILE + (u64)threadIdx.x * SCAN_IPT;
     u32 c[SCAN_IPT];
-    u32 s = 0;
+    u64 s = 0;
 #pragma unroll
     for (int j = 0; j < SCAN_IPT; ++j) {
         c[j] = (base + j < n) ? counts[base + j] : 0;
         s += c[j];
     }
-    u32 total;
-    u32 ex = block_exclusive_scan<SCAN_TPB>(s, lds, total);
+    const u64 ex = scan_tile_exclusive_u64(s, lds);
     u64 run = partials[blockIdx.x] + ex;
 #pragma unroll
     for (int j = 0; j < SCAN_IPT; ++j) {
@@ -1098,3 +1120,26 @@ gtars_status launch_lola_contingency(const u64 *user_hits, const u64 *universe_h
 }
 
 }  // namespace gtars
+
+// test entry (include/gtars_amd_debug.h): host buffers in and out around launch_scan_u32_to_u64
+extern "C" gtars_status gtars_debug_scan_u32(const uint32_t *counts, uint64_t n, uint64_t *offsets_out) {
+    using namespace gtars;
+    return guarded([&]() -> gtars_status {
+        if (!offsets_out || (n && !counts)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (n > 0xFFFFF000ull) return fail(GTARS_ERR_INVALID_ARG, "too many counts for one scan");
+        GT_TRY(require_device());
+        hipStream_t st = nullptr;
+        StreamFrame fr(st);
+        u32 *d_cnt;
+        u64 *d_off;
+        u8 *ws;
+        const size_t wsb = scan_ws_bytes(n);
+        GT_TRY(fr.upload(&d_cnt, counts, (size_t)n, st));
+        GT_TRY(fr.alloc(&d_off, (size_t)n + 1));
+        GT_TRY(fr.alloc(&ws, wsb));
+        GT_TRY(launch_scan_u32_to_u64(d_cnt, n, d_off, ws, wsb, st));
+        GT_HIP(hipMemcpyAsync(offsets_out, d_off, ((size_t)n + 1) * sizeof(u64), hipMemcpyDeviceToHost, st));
+        GT_HIP(hipStreamSynchronize(st));
+        return GTARS_OK;
+    });
+}

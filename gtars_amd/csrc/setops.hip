@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/gtars_amd_debug.h"
 #include "scan.h"
 #include "setops.h"
 
@@ -1364,3 +1365,25 @@ gtars_status setops_chrom_stats(const SetCols &a, uint32_t n_rank, std::vector<C
 }
 
 }  // namespace gtars
+
+// test entry (include/gtars_amd_debug.h): host buffers in and out around seg_max_pass, both forms
+extern "C" gtars_status gtars_debug_seg_max(const uint32_t *seg, const uint32_t *val, const uint32_t *start, uint64_t n, uint32_t gap,
+                                            int inclusive, uint32_t *out) {
+    using namespace gtars;
+    return guarded([&]() -> gtars_status {
+        if (n && (!seg || !val || !out || (!inclusive && !start))) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        GT_TRY(check_sizes(n, 0));
+        if (!n) return GTARS_OK;
+        hipStream_t st = nullptr;
+        StreamFrame fr(st);
+        u32 *d_seg, *d_val, *d_start = nullptr, *d_out;
+        GT_TRY(fr.upload(&d_seg, seg, (size_t)n, st));
+        GT_TRY(fr.upload(&d_val, val, (size_t)n, st));
+        if (!inclusive) GT_TRY(fr.upload(&d_start, start, (size_t)n, st));
+        GT_TRY(fr.alloc(&d_out, (size_t)n));
+        GT_TRY(seg_max_pass(inclusive != 0, d_seg, d_val, d_start, (u32)n, gap, d_out, fr, st));
+        GT_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        GT_HIP(hipStreamSynchronize(st));
+        return GTARS_OK;
+    });
+}

@@ -17,6 +17,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "../../include/gtars_amd_debug.h"
 #include "scan.h"
 
 namespace gtars {
@@ -767,3 +768,30 @@ gtars_status device_sort_perm(const u32 *d_chrom, const u32 *d_k1, const u32 *d_
 }
 
 }  // namespace gtars
+
+// test entry (include/gtars_amd_debug.h): host columns in, the permutation of device_sort_perm_ws out
+extern "C" gtars_status gtars_debug_sort_perm(const uint32_t *chrom, const uint32_t *k1, const uint32_t *k2, uint64_t n, uint32_t n_chrom,
+                                              uint32_t *perm_out) {
+    using namespace gtars;
+    return guarded([&]() -> gtars_status {
+        if (n && (!chrom || !k1 || !perm_out)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (n > 0xFFFFF000ull) return fail(GTARS_ERR_INVALID_ARG, "too many elements for one sort");
+        if (n_chrom > 0x7FFFFFFFu) return fail(GTARS_ERR_INVALID_ARG, "too many chromosomes");
+        GT_TRY(require_device());
+        if (!n) return GTARS_OK;
+        hipStream_t st = nullptr;
+        StreamFrame fr(st);
+        u32 *dc, *d1, *d2 = nullptr, *perm;
+        u8 *scratch;
+        GT_TRY(fr.upload(&dc, chrom, (size_t)n, st));
+        GT_TRY(fr.upload(&d1, k1, (size_t)n, st));
+        if (k2) GT_TRY(fr.upload(&d2, k2, (size_t)n, st));
+        GT_TRY(fr.alloc(&perm, (size_t)n));
+        const size_t sb = device_sort_perm_ws_bytes((u32)n);
+        GT_TRY(fr.alloc(&scratch, sb));
+        GT_TRY(device_sort_perm_ws(dc, d1, d2, (u32)n, n_chrom, perm, scratch, sb, st));
+        GT_HIP(hipMemcpyAsync(perm_out, perm, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        GT_HIP(hipStreamSynchronize(st));
+        return GTARS_OK;
+    });
+}

@@ -41,6 +41,26 @@ int gtars_debug_inflate_streams(const void *comp, const uint64_t *in_off, const 
                                 const uint32_t *out_cap, uint32_t n_streams, uint32_t *out_len, uint32_t *consumed, uint32_t *status,
                                 void *stream);
 
+/* Test entries of the three device primitives under every index build and set operation (tests/test_gpu_primitives.py).  All
+ * pointers are HOST memory; the calls run on the current device's null stream and return when the result is in the caller's
+ * buffer.  GTARS_ERR_NO_DEVICE without a device.
+ *
+ * gtars_debug_sort_perm: the stable radix sort as the index builds and set operations use it (csrc/sort.hip,
+ * device_sort_perm_ws).  perm_out[p] = input row of sorted position p, ordered by (chrom, k1, k2, input row) ascending; k2 may
+ * be NULL.  Every chrom[i] < n_chrom <= 2^31 - 1: only the bytes that n_chrom - 1 occupies take part in the order.
+ *
+ * gtars_debug_scan_u32: offsets_out[i] = counts[0] + ... + counts[i - 1] in u64 for i in [0, n] (csrc/kernels.hip,
+ * launch_scan_u32_to_u64); offsets_out holds n + 1 values.
+ *
+ * gtars_debug_seg_max: the segmented max-scan of csrc/setops.hip (seg_max_pass).  A segment head is element 0 and every i with
+ * seg[i] != seg[i - 1].  inclusive != 0: out[i] = max of val over [head of i's segment, i]; start is not read and may be NULL.
+ * inclusive == 0: out[i] = 1 where i is a head or start[i] > min(max of val over [head, i) + gap, 2^32 - 1), else 0. */
+gtars_status gtars_debug_sort_perm(const uint32_t *chrom, const uint32_t *k1, const uint32_t *k2, uint64_t n, uint32_t n_chrom,
+                                   uint32_t *perm_out);
+gtars_status gtars_debug_scan_u32(const uint32_t *counts, uint64_t n, uint64_t *offsets_out);
+gtars_status gtars_debug_seg_max(const uint32_t *seg, const uint32_t *val, const uint32_t *start, uint64_t n, uint32_t gap,
+                                 int inclusive, uint32_t *out);
+
 /* (Stamp builds -- tools/build_variant.sh with -DGTARS_TOK_STAMPS=1 / -DIGD_STAMPS=1 -- additionally export
  * gtars_debug_tok_stamps / gtars_debug_route_stamps / gtars_debug_sweep_stamps: s_memtime at the phase boundaries of the tile
  * loops, read by tools/r03_tok_stamps.py, tools/r03_sweep_stamps.py, tools/r05_rank_stamps.py.  The shipped library has none.) */

@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import annot_ref as A  # noqa: E402
+import edge_layouts as E  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -177,3 +178,24 @@ def test_gene_model_synthetic_200k_rows(tmp_path):
     p.write_bytes(gzip.compress(data[:half]) + gzip.compress(data[half:]))
     for pc in (True, False):
         _check_model(str(p), pc, True, rng)
+
+
+@pytest.mark.parametrize("n_index,boundary", E.edge_cases())
+def test_index_sizes_around_the_staged_sample(n_index, boundary):
+    """index sizes on the edges of a lane, a wave, a workgroup and the 2048 sampled keys a workgroup stages, on one
+    chromosome and on two whose second begins at index 2048 resp. 2047 of the (chromosome, midpoint) order; 50 000
+    queries with exact hits on the first and the last midpoint of every chromosome"""
+    rng = np.random.default_rng(6000 + n_index)
+    ic, is_, ie = _random_regs(rng, n_index, ["chr10"], 3_000_000, (0, 3))
+    index = _tuples(ic, is_, ie)
+    if boundary is not None:
+        index = E.split_at(index, boundary, key=lambda r: A.midpoint(r[1], r[2]))
+        assert sum(1 for r in index if r[0] == "chr10") == boundary
+        first = next(i for i, r in enumerate(index) if r[0] == "chr10")
+        index[0], index[first] = index[first], index[0]  # "chr10" also appears first: it is the first chromosome either way
+    qc, qs, qe = _random_regs(rng, 50_000, ["chr10", "chr2", "chr3"], 3_000_100, (0, 50))
+    q = _tuples(qc, qs, qe)
+    for name in sorted({c for c, _, _ in index}):
+        mids = sorted(A.midpoint(s, e) for c, s, e in index if c == name)
+        q += [(name, mids[0], mids[0] + 1), (name, mids[-1], mids[-1] + 1), (name, mids[0], mids[0]), (name, mids[-1], mids[-1])]
+    _check(index, q)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import edge_layouts as E  # noqa: E402
 import genomicdist_ref as G  # noqa: E402
 import setops_ref as R  # noqa: E402
 
@@ -170,3 +171,71 @@ def test_consensus_of_64_sets_against_reduce_and_any_overlaps():
     for s in sets:
         hits += np.asarray(union.any_overlaps(s), dtype=np.int64)
     assert [x["count"] for x in got] == hits.tolist()
+
+
+# ---- sizes on the edges of a lane, a wave, a workgroup and a 2048-element tile ------------------------------------------
+@pytest.mark.parametrize("n,boundary", E.edge_cases())
+def test_every_operation_at_tile_edge_sizes(n, boundary):
+    from gtars.genomic_distributions import consensus
+
+    rng = np.random.default_rng(4000 + n)
+    # (_random_set returns its n regions and their extras shuffled together: a random n of them)
+    a = _random_set(rng, n, names=["chr10"])[:n]
+    b = _random_set(rng, n, names=["chr10"], inverted=False)[:n]
+    if boundary is not None:
+        a, b = E.split_at(a, boundary), E.split_at(b, boundary)
+    assert len(a) == n and len(b) == n
+    A = _rs(a)
+    assert _tuples(A.disjoin()) == G.disjoin(a)
+    assert _tuples(A.gaps(SIZES)) == G.gaps(a, SIZES)
+    assert A.neighbor_distances() == G.neighbor_distances(a)
+    assert A.nearest_neighbors() == G.nearest_neighbors(a)
+    for n_bins in (250, 7):
+        assert A.distribution(n_bins) == G.distribution(a, n_bins)
+        assert A.distribution(n_bins, SIZES) == G.distribution(a, n_bins, SIZES)
+    assert _stats(A) == G.chromosome_statistics(a)
+    want = [{"chr": c, "start": s, "end": e, "count": k} for c, s, e, k in G.consensus([a, b, a])]
+    assert consensus([A, _rs(b), A]) == want
+
+
+# ---- structured layouts whose carries cross two 1024-tile chunk seams ----------------------------------------------------
+def test_disjoin_under_one_region_covering_two_chunk_seams():
+    lay = E.covering(E.N_SEAMS, seed=21)
+    d = E.layout_set(lay).disjoin()
+    assert d.chrom_names == lay.names and len(d) == len(lay.disjoin[1])
+    assert np.array_equal(d.starts, lay.disjoin[1]) and np.array_equal(d.ends, lay.disjoin[2])
+
+
+def test_neighbors_statistics_and_distribution_of_disjoint_regions_over_two_chunk_seams():
+    lay = E.disjoint(E.N_SEAMS, seed=22)
+    A = E.layout_set(lay)
+    assert np.array_equal(np.asarray(A.neighbor_distances(), dtype=np.int64), lay.neighbor_distances)
+    assert _stats(A) == lay.chromosome_statistics
+    for n_bins in (250, 7):
+        assert A.distribution(n_bins, lay.sizes) == lay.distribution(n_bins)
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_neighbor_distances_with_chromosome_heads_on_tile_firsts_and_lasts(shift):
+    lay = E.disjoint(E.N_SEAMS, seed=23 + shift, per_chrom=2048, shift=shift)
+    A = E.layout_set(lay)
+    assert np.array_equal(np.asarray(A.neighbor_distances(), dtype=np.int64), lay.neighbor_distances)
+    assert _stats(A) == lay.chromosome_statistics
+
+
+# ---- chromosome keys of three bytes in the sort ---------------------------------------------------------------------------
+def test_statistics_of_seventy_thousand_chromosomes():
+    a = E.wide_set(61, 70_000)
+    assert len({r[0] for r in a}) == 70_000 > 65_536
+    A = _rs(a)
+    assert _stats(A) == G.chromosome_statistics(a)
+    assert _tuples(A.disjoin()) == G.disjoin(a)
+    assert A.neighbor_distances() == G.neighbor_distances(a)
+
+
+def test_consensus_with_more_than_65536_set_chromosome_segments():
+    from gtars.genomic_distributions import consensus
+
+    regs = [E.wide_set(70 + k, 2000) for k in range(40)]
+    want = [{"chr": c, "start": s, "end": e, "count": k} for c, s, e, k in G.consensus(regs)]
+    assert consensus([_rs(r) for r in regs]) == want

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import edge_layouts as E  # noqa: E402
 import setops_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -66,11 +67,7 @@ def _check_result_set(rs):
 CASES = [(seed, inv) for seed in range(3) for inv in (None, "chr10", "all")]
 
 
-@pytest.mark.parametrize("seed,inverted", CASES)
-def test_every_operation_against_the_restatement(seed, inverted):
-    rng = np.random.default_rng(1000 + seed)
-    a = _random_set(rng, 3000, NAMES_A, inverted)
-    b = _random_set(rng, 2000, NAMES_B, inverted)
+def _check_every_operation(a, b):
     A, B = _rs(a), _rs(b)
     for got, want in ((A.reduce(), R.reduce(a)), (A.union(B), R.union(a, b)), (A.setdiff(B), R.setdiff(a, b)),
                       (B.setdiff(A), R.setdiff(b, a)), (A.intersect_all(B), R.intersect(a, b)),
@@ -91,6 +88,39 @@ def test_every_operation_against_the_restatement(seed, inverted):
     from gtars.models import RegionSetList
 
     assert _tuples(A.union(B)) == _tuples(RegionSetList([A, B]).concat().reduce())
+    return A, B
+
+
+@pytest.mark.parametrize("seed,inverted", CASES)
+def test_every_operation_against_the_restatement(seed, inverted):
+    rng = np.random.default_rng(1000 + seed)
+    a = _random_set(rng, 3000, NAMES_A, inverted)
+    b = _random_set(rng, 2000, NAMES_B, inverted)
+    _check_every_operation(a, b)
+
+
+# ---- sizes on the edges of a lane, a wave, a workgroup and a 2048-element tile of the sort and the scans ----------------
+def _exactly(rng, n, names, inverted):
+    """_random_set returns its n regions and their touching / duplicate / nested extras shuffled together: a random n of them"""
+    regs = _random_set(rng, n, names, inverted)
+    assert len(regs) >= n
+    return regs[:n]
+
+
+@pytest.mark.parametrize("n,boundary", E.edge_cases())
+def test_every_operation_at_tile_edge_sizes(n, boundary):
+    from gtars.models import RegionSetList
+
+    rng = np.random.default_rng(3000 + n)
+    a = _exactly(rng, n, ["chr10"], "all")
+    b = _exactly(rng, n, ["chr10"], None)
+    if boundary is not None:
+        a, b = E.split_at(a, boundary), E.split_at(b, boundary)
+        srt = sorted(a, key=lambda r: (r[0].encode(), r[1]))
+        assert srt[boundary - 1][0] == "chr10" and srt[boundary][0] == "chr2"
+    assert len(a) == n and len(b) == n
+    A, B = _check_every_operation(a, b)
+    assert RegionSetList([A, B, A]).pairwise_jaccard() == R.pairwise_jaccard([a, b, a])
 
 
 def test_reduce_start_only_key_and_bytewise_names():
@@ -231,3 +261,67 @@ def test_pairwise_jaccard_64_synthetic_sets():
             assert M[i][j] == want, (i, j)
     for i, j in ((0, 1), (5, 63), (40, 7)):
         assert M[i][j] == sets[i].reduce().jaccard(sets[j].reduce())
+
+
+# ---- structured layouts whose carries cross two 1024-tile chunk seams ----------------------------------------------------
+def _assert_cols(rs, names, want):
+    """a result set against (chromosome index into names, start, end) columns"""
+    index = {nm: i for i, nm in enumerate(names)}
+    res_names = np.array([index[nm] for nm in rs.chrom_names], dtype=np.uint32)
+    assert len(rs) == len(want[0])
+    assert np.array_equal(res_names[rs.chrom_ids] if len(rs) else np.zeros(0, dtype=np.uint32), want[0])
+    assert np.array_equal(rs.starts, want[1]) and np.array_equal(rs.ends, want[2])
+
+
+def test_one_region_covering_two_chunk_seams_of_others():
+    """no run opens after the first region: the max-scan carries one value through every tile and both chunk seams"""
+    lay = E.covering(E.N_SEAMS, seed=21)
+    A = E.layout_set(lay)
+    _assert_cols(A.reduce(), lay.names, lay.reduce)
+    assert np.array_equal(np.asarray(A.cluster(0), dtype=np.uint32), lay.cluster0)
+
+
+def _check_disjoint_layout(lay, restatement):
+    A = E.layout_set(lay)
+    red = A.reduce()
+    _assert_cols(red, lay.names, lay.reduce)
+    assert np.array_equal(np.asarray(A.cluster(0), dtype=np.uint32), lay.cluster0)
+    assert len(A.setdiff(A)) == 0
+    _assert_cols(A.intersect_all(A), lay.names, lay.reduce)
+    assert A.jaccard(A) == 1.0
+    if restatement:
+        regs = [(lay.names[c], s, e) for c, s, e in zip(lay.chrom.tolist(), lay.start.tolist(), lay.end.tolist())]
+        assert _tuples(red) == R.reduce(regs)
+        assert A.cluster(0) == R.cluster(regs, 0)
+
+
+def test_disjoint_regions_over_two_chunk_seams():
+    """every region opens a run: reduce is the sorted input and cluster(0) the rank in sorted order"""
+    _check_disjoint_layout(E.disjoint(E.N_SEAMS, seed=22), restatement=False)
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_chromosome_heads_on_tile_firsts_and_lasts(shift):
+    """a new chromosome at every 2048-th sorted region: the segment heads sit on the first (shift 0) or the last (shift 1)
+    slot of the tiles.  The shift 1 layout also runs against the Python restatement in full."""
+    _check_disjoint_layout(E.disjoint(E.N_SEAMS, seed=23 + shift, per_chrom=2048, shift=shift), restatement=shift == 1)
+
+
+# ---- chromosome keys of three bytes in the sort ---------------------------------------------------------------------------
+def test_seventy_thousand_chromosomes():
+    a, b = E.wide_set(61, 70_000), E.wide_set(62, 70_000)
+    assert len({r[0] for r in a}) == 70_000 > 65_536
+    A, B = _rs(a), _rs(b)
+    assert _tuples(A.reduce()) == R.reduce(a)
+    for gap in (0, 100):
+        assert A.cluster(gap) == R.cluster(a, gap)
+    assert A.closest(B) == R.closest(a, b)
+    assert _tuples(A.union(B)) == R.union(a, b)
+
+
+def test_pairwise_jaccard_with_more_than_65536_set_chromosome_segments():
+    from gtars.models import RegionSetList
+
+    regs = [E.wide_set(70 + k, 2000) for k in range(40)]
+    assert 40 * len({r[0] for s in regs for r in s}) > 65_536
+    assert RegionSetList([_rs(r) for r in regs]).pairwise_jaccard() == R.pairwise_jaccard(regs)

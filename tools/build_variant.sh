@@ -9,7 +9,8 @@ cd "$(dirname "$0")/.."
 name=$1; flags=$2; shift 2 || true
 mkdir -p build/variants build/vobj/$name
 objs=""
-for src in host.cpp lola_stats.cpp api.hip kernels.hip sort.hip igd_sweep.hip tokenize_lds.hip fragparse.hip inflate_dev.hip; do
+# every translation unit under gtars_amd/csrc, as the regular build takes them
+for src in $(cd gtars_amd/csrc && ls *.cpp *.hip); do
   o=build/obj/$src.o
   if [ $# -eq 0 ] || echo " $* " | grep -q " $src "; then
     o=build/vobj/$name/$src.o
