@@ -173,6 +173,14 @@ _HOST_SIG = {
     "gtars_tss_index_len": (u64, [vp]),
     "gtars_tss_index_device": (C.c_int, [vp]),
     "gtars_tss_index_distances": (C.c_int, [vp, vp, vp, vp]),
+    "gtars_uniwig_counts": (C.c_int, [vp, vp, u64, u32, u32, C.c_int, u64, pu64, pp, pu64]),
+    "gtars_uniwig_extent": (C.c_int, [vp, vp, u64, u32, u32, C.c_int, pu64, pu64]),
+    "gtars_uniwig_counts_device": (C.c_int, [vp, vp, u64, u32, C.c_int, u64, u64, vp, vp]),
+    "gtars_uniwig_runs": (C.c_int, [vp, vp, u64, u32, u32, C.c_int, u32, pp, pp, pp, pu64]),
+    "gtars_uniwig_nonzero": (C.c_int, [vp, vp, u64, u32, u32, C.c_int, u32, pp, pp, pu64]),
+    "gtars_uniwig_format_counts": (C.c_int, [vp, u64, pp, pu64]),
+    "gtars_uniwig_format_pairs": (C.c_int, [vp, vp, u64, pp, pu64]),
+    "gtars_uniwig_format_bedgraph": (C.c_int, [cstr, vp, vp, vp, u64, pp, pu64]),
     "gtars_tokenizer_from_auto": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_config": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_bed": (C.c_int, [cstr, pp]),

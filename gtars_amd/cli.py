@@ -8,6 +8,10 @@
   python -m gtars_amd igd search --database DB.igd --query Q.bed[.gz]
       gtars-cli/src/igd/handlers.rs:11-98: the legacy TSV  index / number of regions / number of hits / File_name  for
       the files with hits, then  Total: N.
+  python -m gtars_amd uniwig --file F.bed[.gz] --chromref G.chrom.sizes --smoothsize M --stepsize 1 --fileheader PREFIX
+                             [--outputtype wig|bedGraph|npy] [--counttype all|start|end|core] [--wigstep fixed|variable]
+      gtars-cli/src/uniwig/cli.rs:38-178, handlers.rs:48-160 for BED input: the coverage tracks of gtars_amd.uniwig.  BAM
+      input (--filetype bam) and bigWig output (--outputtype bw) are not provided and exit with a message.
 
 Same rules as the reference: fields are split on TAB only, coordinates must parse as u32 (``+5`` is accepted, blanks and
 signs are not), every line counts (no header skipping in overlaprs).  The whole query file is ONE batch on the device.
@@ -145,6 +149,30 @@ def run_igd_search(database: str, query: str, out: TextIO = sys.stdout) -> int:
     return total
 
 
+COUNT_TYPES = {"start": ("start",), "end": ("end",), "core": ("core",)}  # anything else: all three (handlers.rs:93-113)
+
+
+def run_uniwig(a) -> int:
+    """handlers.rs:48-160 for the BED path.  -> exit status"""
+    if a.filetype.lower() == "bam":
+        sys.stderr.write("uniwig: --filetype bam is not provided by gtars_amd (BED and narrowPeak input only)\n")
+        return 2
+    if a.outputtype in ("bw", "bigwig", "bigWig"):
+        sys.stderr.write("uniwig: --outputtype bw is not provided by gtars_amd (write bedGraph and convert it)\n")
+        return 2
+    if a.filetype.lower() not in ("bed", "narrowpeak"):
+        sys.stderr.write(f"uniwig: unknown file type {a.filetype!r}\n")
+        return 2
+    if a.counttype == "shift":
+        sys.stderr.write("uniwig: --counttype shift belongs to the BAM workflow, which is not provided by gtars_amd\n")
+        return 2
+    from .uniwig import uniwig
+
+    uniwig(a.file, a.chromref, a.smoothsize, stepsize=a.stepsize, count_types=COUNT_TYPES.get(a.counttype, ("start", "end", "core")),
+           output_prefix=a.fileheader, output_type=a.outputtype, wig_variable=a.wigstep == "variable", score=a.score)
+    return 0
+
+
 def main(argv: Sequence[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m gtars_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -161,7 +189,20 @@ def main(argv: Sequence[str] = None) -> int:
     s = gs.add_parser("search")
     s.add_argument("--database", "-d", required=True)
     s.add_argument("--query", "-q", required=True)
+    w = sub.add_parser("uniwig", help="Create accumulation files from a BED file")
+    w.add_argument("--file", "-f", required=True, help="Path to the combined bed file we want to transform")
+    w.add_argument("--filetype", "-t", default="bed", help="Input file type, 'bed' or 'narrowpeak'")
+    w.add_argument("--chromref", "-c", required=True, help="Path to chromreference")
+    w.add_argument("--smoothsize", "-m", type=int, required=True, help="Integer value for smoothing")
+    w.add_argument("--stepsize", "-s", type=int, required=True, help="Integer value for stepsize")
+    w.add_argument("--fileheader", "-l", required=True, help="Name of the file")
+    w.add_argument("--outputtype", "-y", default="wig", help="Output as wig, bedGraph or npy")
+    w.add_argument("--counttype", "-u", default="all", help="Select to only output start, end, or core. Defaults to all.")
+    w.add_argument("--score", "-o", action="store_true", help="Count via score (not provided)")
+    w.add_argument("--wigstep", "-w", default="fixed", help="'fixed' (every position) or 'variable' (non-zero only)")
     a = ap.parse_args(argv)
+    if a.cmd == "uniwig":
+        return run_uniwig(a)
     if a.cmd == "overlaprs":
         run_overlaprs(a.universe, a.query, a.backend)
     elif a.igd_cmd == "create":

@@ -37,6 +37,7 @@
 #include "inflate_fast.h"
 #include "setops.h"
 #include "annot.h"
+#include "uniwig.h"
 
 namespace gtars {
 gtars_status fail(gtars_status st, const std::string &msg);
@@ -4229,6 +4230,117 @@ gtars_status gtars_format_hit_lines(const char *const *chrom_names, const uint32
         *out_text = p;
         *out_len = text.size();
         return GTARS_OK;
+    });
+}
+
+// ---- coverage tracks (gtars-uniwig, BED input): the device work is uniwig.hip's, the writers' text is made here ----------
+gtars_status gtars_uniwig_counts(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                                 uint32_t smoothsize, int kind, uint64_t max_device_bytes, uint64_t *first, uint32_t **counts,
+                                 uint64_t *n_counts) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!first || !counts || !n_counts) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        return gtars::uniwig_counts(opens, closes, n, chrom_size, smoothsize, kind, max_device_bytes, first, counts, n_counts);
+    });
+}
+
+gtars_status gtars_uniwig_extent(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                                 uint32_t smoothsize, int kind, uint64_t *first, uint64_t *n_counts) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!first || !n_counts) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        return gtars::uniwig_extent(opens, closes, n, chrom_size, smoothsize, kind, first, n_counts);
+    });
+}
+
+gtars_status gtars_uniwig_counts_device(const uint32_t *d_opens, const uint32_t *d_closes, uint64_t n, uint32_t smoothsize,
+                                        int kind, uint64_t window_first, uint64_t window_len, uint32_t *d_counts, void *stream) {
+    return gtars::guarded([&]() -> gtars_status {
+        return gtars::uniwig_counts_device(d_opens, d_closes, n, smoothsize, kind, window_first, window_len, d_counts, stream);
+    });
+}
+
+gtars_status gtars_uniwig_runs(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                               uint32_t smoothsize, int kind, uint32_t start_position, uint32_t **run_start,
+                               uint32_t **run_end, uint32_t **run_count, uint64_t *n_runs) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!run_start || !run_end || !run_count || !n_runs) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        return gtars::uniwig_runs(opens, closes, n, chrom_size, smoothsize, kind, start_position, run_start, run_end, run_count,
+                                  n_runs);
+    });
+}
+
+gtars_status gtars_uniwig_nonzero(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                                  uint32_t smoothsize, int kind, uint32_t start_position, uint32_t **position,
+                                  uint32_t **count, uint64_t *n_out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!position || !count || !n_out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        return gtars::uniwig_nonzero(opens, closes, n, chrom_size, smoothsize, kind, start_position, position, count, n_out);
+    });
+}
+
+namespace {
+inline void put_u32(std::string &text, uint32_t v) {
+    char buf[16];
+    int k = 0;
+    do { buf[k++] = (char)('0' + v % 10); v /= 10; } while (v);
+    while (k) text.push_back(buf[--k]);
+}
+gtars_status give_text(const std::string &text, char **out_text, uint64_t *out_len) {
+    char *p = (char *)malloc(text.size() + 1);
+    if (!p) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    memcpy(p, text.data(), text.size());
+    p[text.size()] = 0;
+    *out_text = p;
+    *out_len = text.size();
+    return GTARS_OK;
+}
+}  // namespace
+
+gtars_status gtars_uniwig_format_counts(const uint32_t *counts, uint64_t n, char **out_text, uint64_t *out_len) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out_text || !out_len || (n && !counts)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        std::string text;
+        text.reserve((size_t)n * 3);
+        for (uint64_t i = 0; i < n; ++i) {
+            put_u32(text, counts[i]);
+            text.push_back('\n');
+        }
+        return give_text(text, out_text, out_len);
+    });
+}
+
+gtars_status gtars_uniwig_format_pairs(const uint32_t *a, const uint32_t *b, uint64_t n, char **out_text, uint64_t *out_len) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out_text || !out_len || (n && (!a || !b))) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        std::string text;
+        text.reserve((size_t)n * 14);
+        for (uint64_t i = 0; i < n; ++i) {
+            put_u32(text, a[i]);
+            text.push_back('\t');
+            put_u32(text, b[i]);
+            text.push_back('\n');
+        }
+        return give_text(text, out_text, out_len);
+    });
+}
+
+gtars_status gtars_uniwig_format_bedgraph(const char *chrom, const uint32_t *run_start, const uint32_t *run_end,
+                                          const uint32_t *run_count, uint64_t n, char **out_text, uint64_t *out_len) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out_text || !out_len || !chrom || (n && (!run_start || !run_end || !run_count)))
+            return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        std::string text;
+        text.reserve((size_t)n * (strlen(chrom) + 28));
+        for (uint64_t i = 0; i < n; ++i) {
+            text += chrom;
+            text.push_back('\t');
+            put_u32(text, run_start[i]);
+            text.push_back('\t');
+            put_u32(text, run_end[i]);
+            text.push_back('\t');
+            put_u32(text, run_count[i]);
+            text.push_back('\n');
+        }
+        return give_text(text, out_text, out_len);
     });
 }
 

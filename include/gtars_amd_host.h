@@ -183,6 +183,52 @@ gtars_status gtars_tss_index_distances(gtars_tss_index_t *ix, const gtars_region
                                        int64_t *out_signed);
 
 /* ------------------------------------------------------------------------
+ * Coverage tracks  (gtars-uniwig, BED input: counting.rs:32-290, utils.rs:31-81, writing.rs:113-214)
+ *
+ * One chromosome per call.  A track is given by columns of n u32 (any order, each is sorted on the device):
+ *   GTARS_UNIWIG_START / _END (start_end_counts): opens = start + 1 (resp. end) of every row, closes NULL; a position
+ *       p opens a window at max(1, p - smoothsize) and closes it at p + smoothsize + 1
+ *   GTARS_UNIWIG_CORE (core_counts): opens = start + 1, closes = end of every row; smoothsize is ignored
+ * With a the sorted opens and e the sorted closes, entry k of the track is the count at position first + k:
+ *   #{a <= pos} - #{e <= pos},  first = a_0,  last = max(chrom_size, a_{n-1} - 1)   (n == 0: an empty track)
+ * which is what the reference's sweeps give for unit scores and step 1.  Outside that domain they give something
+ * else, so a core-track row with closes[i] < opens[i] (a zero-length or inverted row) is GTARS_ERR_INVALID_ARG, as is
+ * anything that does not fit the reference's i32.
+ * ---------------------------------------------------------------------- */
+#define GTARS_UNIWIG_START 0
+#define GTARS_UNIWIG_END 1
+#define GTARS_UNIWIG_CORE 2
+/* the whole track: *first, *counts (gtars_free) and *n_counts.  The device holds at most max_device_bytes of counts at a
+ * time (0: the library's default, 1 GiB); a longer track is produced in position windows. */
+gtars_status gtars_uniwig_counts(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                                 uint32_t smoothsize, int kind, uint64_t max_device_bytes, uint64_t *first, uint32_t **counts,
+                                 uint64_t *n_counts);
+/* first and length of that track without computing it (host only; same argument checks) */
+gtars_status gtars_uniwig_extent(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                                 uint32_t smoothsize, int kind, uint64_t *first, uint64_t *n_counts);
+/* positions window_first .. window_first + window_len - 1 of the track into d_counts (device memory, 16-byte aligned),
+ * queued on `stream` (a hipStream_t); nothing is synchronised.  d_opens / d_closes: device columns that ASCEND. */
+gtars_status gtars_uniwig_counts_device(const uint32_t *d_opens, const uint32_t *d_closes, uint64_t n, uint32_t smoothsize,
+                                        int kind, uint64_t window_first, uint64_t window_len, uint32_t *d_counts, void *stream);
+/* compress_counts (utils.rs:40-81) of the track: runs (start, end, count) that begin at start_position and advance by
+ * one per ENTRY, the closing run always emitted; three columns (gtars_free each) of *n_runs.  Only the runs leave the
+ * device.  GTARS_ERR_EMPTY for a track without entries (the reference reads entry 0). */
+gtars_status gtars_uniwig_runs(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                               uint32_t smoothsize, int kind, uint32_t start_position, uint32_t **run_start,
+                               uint32_t **run_end, uint32_t **run_count, uint64_t *n_runs);
+/* the non-zero entries among the first chrom_size ENTRIES of the track as (start_position + k, count)
+ * (write_to_wig_file_variable, writing.rs:149-179): two columns (gtars_free each) of *n_out */
+gtars_status gtars_uniwig_nonzero(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size,
+                                  uint32_t smoothsize, int kind, uint32_t start_position, uint32_t **position,
+                                  uint32_t **count, uint64_t *n_out);
+/* the writers' lines (writing.rs:141-144, 172-177, 205-212) as one malloc'ed text (gtars_free), *out_len bytes:
+ * "count\n" per entry; "a\tb\n" per pair; "chrom\tstart\tend\tcount\n" per run */
+gtars_status gtars_uniwig_format_counts(const uint32_t *counts, uint64_t n, char **out_text, uint64_t *out_len);
+gtars_status gtars_uniwig_format_pairs(const uint32_t *a, const uint32_t *b, uint64_t n, char **out_text, uint64_t *out_len);
+gtars_status gtars_uniwig_format_bedgraph(const char *chrom, const uint32_t *run_start, const uint32_t *run_end,
+                                          const uint32_t *run_count, uint64_t n, char **out_text, uint64_t *out_len);
+
+/* ------------------------------------------------------------------------
  * Tokenizer  (gtars-tokenizers/src/tokenizer.rs:36-279, universe/mod.rs,
  * config.rs, utils/mod.rs:34-99, utils/special_tokens.rs)
  * ---------------------------------------------------------------------- */
