@@ -21,6 +21,7 @@
 
 #include "annot.h"
 #include "common.h"
+#include "pipeline.h"
 
 namespace gtars {
 
@@ -43,17 +44,6 @@ __global__ void k_midpoints(const u32 *__restrict__ start, const u32 *__restrict
         const u32 s = start[i];
         mid[i] = s + (end[i] - s) / 2;
     }
-}
-
-// first position p in [lo, hi) with x[p] >= key, hi if none
-template <class P>
-__device__ __forceinline__ u32 lower_bound(P x, u32 lo, u32 hi, u32 key) {
-    while (lo < hi) {
-        const u32 m = lo + ((hi - lo) >> 1);
-        if (x[m] >= key) hi = m;
-        else lo = m + 1;
-    }
-    return lo;
 }
 
 template <bool LDS>
@@ -81,11 +71,11 @@ k_tss_dist(const u32 *__restrict__ qc, const u32 *__restrict__ qs, const u32 *__
                 // before it (< mid) from below: at most 2^shift - 1 keys are left for global memory
                 const u32 klo = (u32)(((u64)lo + (1ull << shift) - 1) >> shift);
                 const u32 khi = (u32)(((u64)hi + (1ull << shift) - 1) >> shift);
-                const u32 kk = lower_bound(samp, klo, khi, mid);
+                const u32 kk = first_ge(samp, klo, khi, mid);
                 if (kk > klo) wlo = ((kk - 1) << shift) + 1;
                 if (kk < khi) whi = kk << shift;
             }
-            const u32 p = lower_bound(mids, wlo, whi, mid);
+            const u32 p = first_ge(mids, wlo, whi, mid);
             const u32 r = p < hi ? mids[p] : 0u;
             if (p < hi && r == mid) {
                 a = 0;
@@ -105,10 +95,6 @@ k_tss_dist(const u32 *__restrict__ qc, const u32 *__restrict__ qs, const u32 *__
         oabs[j] = a;
         osig[j] = sg;
     }
-}
-
-inline unsigned blocks_for(u64 n, u32 cap) {
-    return (unsigned)std::min<u64>(std::max<u64>(1, (n + TSS_TPB - 1) / TSS_TPB), cap);
 }
 
 // the LDS-staged search unless GTARS_TSS_GLOBAL_SEARCH (A/B switch) asks for the global one
@@ -134,22 +120,17 @@ gtars_status tss_build(const uint32_t *chrom, const uint32_t *start, const uint3
     GT_TRY(t->off.upload(off));
     GT_TRY(t->mids.alloc(n));
     if (n) {
-        hipStream_t st = nullptr;
-        StreamFrame fr(st);
+        StreamFrame fr(nullptr);
         u32 *dc, *ds, *de, *mid, *perm;
-        u8 *scratch;
-        GT_TRY(fr.upload(&dc, chrom, n, st));
-        GT_TRY(fr.upload(&ds, start, n, st));
-        GT_TRY(fr.upload(&de, end, n, st));
+        GT_TRY(fr.upload(&dc, chrom, n));
+        GT_TRY(fr.upload(&ds, start, n));
+        GT_TRY(fr.upload(&de, end, n));
         GT_TRY(fr.alloc(&mid, n));
-        GT_TRY(fr.alloc(&perm, n));
-        hipLaunchKernelGGL(k_midpoints, dim3(blocks_for(n, 1u << 16)), dim3(TSS_TPB), 0, st, ds, de, (u32)n, mid);
-        const size_t sb = device_sort_perm_ws_bytes((u32)n);
-        GT_TRY(fr.alloc(&scratch, sb));
-        GT_TRY(device_sort_perm_ws(dc, mid, nullptr, (u32)n, n_chrom, perm, scratch, sb, st));  // (chromosome, midpoint)
-        GT_TRY(device_gather_u32(mid, perm, (u32)n, t->mids.p, st));
+        hipLaunchKernelGGL(k_midpoints, dim3(grid_for(n, TSS_TPB)), dim3(TSS_TPB), 0, fr.st, ds, de, (u32)n, mid);
+        GT_TRY(sort_perm(fr, dc, mid, nullptr, (u32)n, n_chrom, &perm));  // (chromosome, midpoint)
+        GT_TRY(device_gather_u32(mid, perm, (u32)n, t->mids.p, fr.st));
         GT_HIP(hipGetLastError());
-        GT_HIP(hipStreamSynchronize(st));
+        GT_TRY(fr.drain());
     }
     *out = t.release();
     return GTARS_OK;
@@ -175,25 +156,19 @@ gtars_status tss_distances(const TssDevice *t, const uint32_t *q_chrom, const ui
     if (!nq) return GTARS_OK;
     DeviceScope on(t->device);
     GT_TRY(on.st);
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     const u32 n = (u32)nq;
     u32 *qc, *qs, *qe, *d_seg, *perm = nullptr, *oabs;
     i64 *osig;
-    GT_TRY(fr.upload(&qc, q_chrom, nq, st));
-    GT_TRY(fr.upload(&qs, q_start, nq, st));
-    GT_TRY(fr.upload(&qe, q_end, nq, st));
-    GT_TRY(fr.upload(&d_seg, seg_of.data(), seg_of.size(), st));
+    GT_TRY(fr.upload(&qc, q_chrom, nq));
+    GT_TRY(fr.upload(&qs, q_start, nq));
+    GT_TRY(fr.upload(&qe, q_end, nq));
+    GT_TRY(fr.upload(&d_seg, seg_of.data(), seg_of.size()));
     GT_TRY(fr.alloc(&oabs, nq));
     GT_TRY(fr.alloc(&osig, nq));
-    if (!grouped) {
-        // stable by chromosome id alone (one 32-bit key, no chromosome pass)
-        u8 *scratch;
-        const size_t sb = device_sort_perm_ws_bytes(n);
-        GT_TRY(fr.alloc(&perm, nq));
-        GT_TRY(fr.alloc(&scratch, sb));
-        GT_TRY(device_sort_perm_ws(qc, qc, nullptr, n, 1, perm, scratch, sb, st));
-    }
+    // stable by chromosome id alone (one 32-bit key, no chromosome pass)
+    if (!grouped) GT_TRY(sort_perm(fr, qc, qc, nullptr, n, 1, &perm));
     // the LDS table: every 2^shift-th key of the index, at most TSS_LDS_KEYS of them
     u32 shift = 0;
     while (((u64)t->n + (1ull << shift) - 1) >> shift > TSS_LDS_KEYS) ++shift;
@@ -201,17 +176,16 @@ gtars_status tss_distances(const TssDevice *t, const uint32_t *q_chrom, const ui
     {
         ProfScope ps("tss_distance_kernel", st);
         if (lds_search() && t->n)
-            hipLaunchKernelGGL(k_tss_dist<true>, dim3(blocks_for(nq, TSS_MAX_BLOCKS)), dim3(TSS_TPB), 0, st, qc, qs, qe, perm, n, d_seg,
-                               t->off.p, t->mids.p, n_keys, shift, oabs, osig);
+            hipLaunchKernelGGL(k_tss_dist<true>, dim3(grid_for(nq, TSS_TPB, TSS_MAX_BLOCKS)), dim3(TSS_TPB), 0, st, qc, qs, qe, perm, n,
+                               d_seg, t->off.p, t->mids.p, n_keys, shift, oabs, osig);
         else
-            hipLaunchKernelGGL(k_tss_dist<false>, dim3(blocks_for(nq, TSS_MAX_BLOCKS)), dim3(TSS_TPB), 0, st, qc, qs, qe, perm, n, d_seg,
-                               t->off.p, t->mids.p, 0u, 0u, oabs, osig);
+            hipLaunchKernelGGL(k_tss_dist<false>, dim3(grid_for(nq, TSS_TPB, TSS_MAX_BLOCKS)), dim3(TSS_TPB), 0, st, qc, qs, qe, perm, n,
+                               d_seg, t->off.p, t->mids.p, 0u, 0u, oabs, osig);
         GT_HIP(hipGetLastError());
     }
-    GT_HIP(hipMemcpyAsync(out_abs, oabs, nq * sizeof(u32), hipMemcpyDeviceToHost, st));
-    GT_HIP(hipMemcpyAsync(out_signed, osig, nq * sizeof(i64), hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
-    return GTARS_OK;
+    GT_TRY(fr.download(out_abs, oabs, nq));
+    GT_TRY(fr.download(out_signed, osig, nq));
+    return fr.drain();
 }
 
 }  // namespace gtars

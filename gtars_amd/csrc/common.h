@@ -145,11 +145,32 @@ struct StreamFrame {
         *out = (T *)bufs.back().p;
         return GTARS_OK;
     }
+    // the copies below are queued on the frame's stream and skip n == 0; host memory must stay valid until drain()
     template <class T>
-    gtars_status upload(T **out, const T *h, size_t n, hipStream_t s) {
+    gtars_status upload(T **out, const T *h, size_t n) {
         bufs.emplace_back();
-        GT_TRY(bufs.back().upload((const u8 *)h, n * sizeof(T), s));
+        GT_TRY(bufs.back().upload((const u8 *)h, n * sizeof(T), st));
         *out = (T *)bufs.back().p;
+        return GTARS_OK;
+    }
+    template <class T>
+    gtars_status upload_to(T *d, const T *h, size_t n) {
+        if (n) GT_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return GTARS_OK;
+    }
+    template <class T>
+    gtars_status download(T *h, const T *d, size_t n) {
+        if (n) GT_HIP(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st));
+        return GTARS_OK;
+    }
+    template <class T>
+    gtars_status download(std::vector<T> &h, const T *d, size_t n) {
+        h.resize(n);
+        return download(h.data(), d, n);
+    }
+    // waits for everything queued so far: downloaded values may be read afterwards
+    gtars_status drain() {
+        GT_HIP(hipStreamSynchronize(st));
         return GTARS_OK;
     }
     // host memory for the stream's copies (pinned when the pool has it); null: out of host memory

@@ -1134,7 +1134,7 @@ extern "C" gtars_status gtars_debug_scan_u32(const uint32_t *counts, uint64_t n,
         u64 *d_off;
         u8 *ws;
         const size_t wsb = scan_ws_bytes(n);
-        GT_TRY(fr.upload(&d_cnt, counts, (size_t)n, st));
+        GT_TRY(fr.upload(&d_cnt, counts, (size_t)n));
         GT_TRY(fr.alloc(&d_off, (size_t)n + 1));
         GT_TRY(fr.alloc(&ws, wsb));
         GT_TRY(launch_scan_u32_to_u64(d_cnt, n, d_off, ws, wsb, st));

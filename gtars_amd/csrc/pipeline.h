@@ -1,0 +1,42 @@
+// pipeline.h -- the steps the region-set pipelines (setops.hip, annot.hip, uniwig.hip) share.  The host-side ones queue
+// their work on a StreamFrame's stream and leave what they allocate with the frame.
+#pragma once
+
+#include "common.h"
+
+namespace gtars {
+
+// workgroups of `per` elements that cover n, at least one and at most `cap` (grid-stride kernels)
+inline unsigned grid_for(u64 n, u32 per = 256, u32 cap = 1u << 16) {
+    return (unsigned)std::min<u64>(std::max<u64>(1, (n + per - 1) / per), cap);
+}
+
+// first position p in [lo, hi) with x[p] >= key (first_gt: > key), hi if none; x ascends.  P: any indexable, global or LDS
+template <class P>
+__device__ __forceinline__ u32 first_ge(P x, u32 lo, u32 hi, u32 key) {
+    while (lo < hi) {
+        const u32 m = lo + ((hi - lo) >> 1);
+        if (x[m] >= key) hi = m;
+        else lo = m + 1;
+    }
+    return lo;
+}
+template <class P>
+__device__ __forceinline__ u32 first_gt(P x, u32 lo, u32 hi, u32 key) {
+    while (lo < hi) {
+        const u32 m = lo + ((hi - lo) >> 1);
+        if (x[m] > key) hi = m;
+        else lo = m + 1;
+    }
+    return lo;
+}
+
+// *perm: the permutation that stably sorts n device rows by (seg, k1[, k2]), seg < n_seg (k2 may be null; a single
+// 32-bit key x sorts as (x, x) with n_seg == 1).  The permutation and the sort's scratch belong to the frame.
+gtars_status sort_perm(StreamFrame &fr, const u32 *seg, const u32 *k1, const u32 *k2, u32 n, u32 n_seg, u32 **perm);
+
+// (*off)[0 .. n]: the exclusive scan of n u32 counts; *total = (*off)[n], on the host when the call returns (the
+// stream is drained)
+gtars_status scan_total(StreamFrame &fr, const u32 *cnt, u64 n, u64 **off, u64 *total);
+
+}  // namespace gtars

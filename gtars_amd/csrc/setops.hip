@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "../../include/gtars_amd_debug.h"
+#include "pipeline.h"
 #include "scan.h"
 #include "setops.h"
 
@@ -38,8 +39,6 @@ constexpr u32 SO_TILE = SO_TPB * SO_IPT;
 constexpr u32 SO_PAIR_CHUNK = 2048;  // regions of the smaller set per work item of the pairwise kernel
 constexpr u32 SO_MAX_N = 0xFFFFF000u;
 enum { SWEEP_SETDIFF = 0, SWEEP_INTERSECT = 1 };
-
-inline unsigned grid_for(u64 n, u32 per = 256) { return (unsigned)std::min<u64>(std::max<u64>(1, (n + per - 1) / per), 1u << 16); }
 
 // ---------------------------------------------------------------------------------------------- segmented max-scan
 struct SM {
@@ -126,9 +125,9 @@ k_sm_apply(const u32 *__restrict__ seg, const u32 *__restrict__ val, const u32 *
     }
 }
 
-gtars_status seg_max_pass(bool incl, const u32 *seg, const u32 *val, const u32 *start, u32 n, u32 gap, u32 *out, StreamFrame &fr,
-                          hipStream_t st) {
+gtars_status seg_max_pass(StreamFrame &fr, bool incl, const u32 *seg, const u32 *val, const u32 *start, u32 n, u32 gap, u32 *out) {
     if (!n) return GTARS_OK;
+    hipStream_t st = fr.st;
     const u32 tiles = (n + SO_TILE - 1) / SO_TILE;
     u64 *agg = nullptr;
     GT_TRY(fr.alloc(&agg, tiles));
@@ -139,18 +138,6 @@ gtars_status seg_max_pass(bool incl, const u32 *seg, const u32 *val, const u32 *
     else
         hipLaunchKernelGGL(k_sm_apply<false>, dim3(tiles), dim3(SO_TPB), 0, st, seg, val, start, n, agg, gap, out);
     GT_HIP(hipGetLastError());
-    return GTARS_OK;
-}
-
-// exclusive scan of u32 flags / counts; returns the total
-gtars_status scan_counts(const u32 *cnt, u32 n, u64 **off, u64 *total, StreamFrame &fr, hipStream_t st) {
-    GT_TRY(fr.alloc(off, (size_t)n + 1));
-    void *ws = nullptr;
-    const size_t wsb = scan_ws_bytes(n);
-    GT_TRY(fr.alloc((u8 **)&ws, wsb));
-    GT_TRY(launch_scan_u32_to_u64(cnt, n, *off, ws, wsb, st));
-    GT_HIP(hipMemcpyAsync(total, *off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
     return GTARS_OK;
 }
 
@@ -211,23 +198,6 @@ __global__ void k_widths(const u32 *__restrict__ start, const u32 *__restrict__ 
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) w[i] = end[i] - start[i];
 }
 
-__device__ __forceinline__ u32 first_gt(const u32 *__restrict__ x, u32 lo, u32 hi, u32 key) {
-    while (lo < hi) {
-        const u32 m = lo + ((hi - lo) >> 1);
-        if (x[m] > key) hi = m;
-        else lo = m + 1;
-    }
-    return lo;
-}
-__device__ __forceinline__ u32 first_ge(const u32 *__restrict__ x, u32 lo, u32 hi, u32 key) {
-    while (lo < hi) {
-        const u32 m = lo + ((hi - lo) >> 1);
-        if (x[m] >= key) hi = m;
-        else lo = m + 1;
-    }
-    return lo;
-}
-
 // ------------------------------------------------------------------------------------------------------- reduce
 struct DevSet {
     u32 *seg = nullptr, *start = nullptr, *end = nullptr;
@@ -240,57 +210,80 @@ struct ReduceWork {
     u32 *perm = nullptr, *sseg = nullptr, *sstart = nullptr, *send = nullptr, *rid = nullptr;
 };
 
-// reduce() of n device regions (unsorted) whose segment keys are < n_seg
-gtars_status dev_reduce(const u32 *seg, const u32 *start, const u32 *end, u32 n, u32 n_seg, StreamFrame &fr, hipStream_t st, DevSet &out,
-                        ReduceWork *work = nullptr) {
-    out = DevSet();
-    if (work) *work = ReduceWork();
-    if (!n) return GTARS_OK;
-    u32 *perm, *sseg, *sstart, *send, *flag, *rid, *rmax;
-    GT_TRY(fr.alloc(&perm, n));
-    const size_t sb = device_sort_perm_ws_bytes(n);
-    u8 *scratch;
-    GT_TRY(fr.alloc(&scratch, sb));
-    GT_TRY(device_sort_perm_ws(seg, start, nullptr, n, n_seg, perm, scratch, sb, st));  // (segment, start), ties in input order
-    GT_TRY(fr.alloc(&sseg, n));
-    GT_TRY(fr.alloc(&sstart, n));
-    GT_TRY(fr.alloc(&send, n));
-    hipLaunchKernelGGL(k_gather3, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, sseg, sstart, send);
-    GT_TRY(fr.alloc(&flag, n));
-    GT_TRY(seg_max_pass(false, sseg, send, sstart, n, 0, flag, fr, st));
-    u64 *off, m = 0;
-    GT_TRY(scan_counts(flag, n, &off, &m, fr, st));
-    GT_TRY(fr.alloc(&rid, n));
-    hipLaunchKernelGGL(k_run_ids, dim3(grid_for(n)), dim3(256), 0, st, flag, off, n, rid);
-    GT_TRY(fr.alloc(&rmax, n));
-    GT_TRY(seg_max_pass(true, rid, send, nullptr, n, 0, rmax, fr, st));
-    out.n = (u32)m;
-    GT_TRY(fr.alloc(&out.seg, m));
-    GT_TRY(fr.alloc(&out.start, m));
-    GT_TRY(fr.alloc(&out.end, m));
-    hipLaunchKernelGGL(k_reduce_write, dim3(grid_for(n)), dim3(256), 0, st, sseg, sstart, flag, rid, rmax, n, out.seg, out.start,
-                       out.end);
-    GT_HIP(hipGetLastError());
-    if (work) *work = ReduceWork{perm, sseg, sstart, send, rid};
+// a set of n rows whose three columns belong to the frame
+gtars_status alloc_set(StreamFrame &fr, u64 n, DevSet &s) {
+    s.n = (u32)n;
+    GT_TRY(fr.alloc(&s.seg, n));
+    GT_TRY(fr.alloc(&s.start, n));
+    return fr.alloc(&s.end, n);
+}
+
+gtars_status upload_set(StreamFrame &fr, const SetCols &a, DevSet &s) {
+    s.n = (u32)a.n;
+    GT_TRY(fr.upload(&s.seg, a.rank, a.n));
+    GT_TRY(fr.upload(&s.start, a.start, a.n));
+    return fr.upload(&s.end, a.end, a.n);
+}
+
+// the rows of n_sets host sets one after the other in one device set
+gtars_status upload_concat(StreamFrame &fr, const SetCols *sets, size_t n_sets, DevSet &out) {
+    u64 n = 0;
+    for (size_t k = 0; k < n_sets; ++k) n += sets[k].n;
+    GT_TRY(alloc_set(fr, n, out));
+    u64 at = 0;
+    for (size_t k = 0; k < n_sets; ++k) {
+        const SetCols &s = sets[k];
+        GT_TRY(fr.upload_to(out.seg + at, s.rank, s.n));
+        GT_TRY(fr.upload_to(out.start + at, s.start, s.n));
+        GT_TRY(fr.upload_to(out.end + at, s.end, s.n));
+        at += s.n;
+    }
     return GTARS_OK;
 }
 
-gtars_status upload_set(const SetCols &a, StreamFrame &fr, hipStream_t st, u32 **seg, u32 **start, u32 **end) {
-    GT_TRY(fr.upload(seg, a.rank, a.n, st));
-    GT_TRY(fr.upload(start, a.start, a.n, st));
-    return fr.upload(end, a.end, a.n, st);
+// queued, not drained: `out` holds the rows after fr.drain()
+gtars_status download(StreamFrame &fr, const DevSet &d, SetOut &out) {
+    GT_TRY(fr.download(out.rank, d.seg, d.n));
+    GT_TRY(fr.download(out.start, d.start, d.n));
+    return fr.download(out.end, d.end, d.n);
 }
 
-gtars_status download(const DevSet &d, hipStream_t st, SetOut &out) {
-    out.rank.resize(d.n);
-    out.start.resize(d.n);
-    out.end.resize(d.n);
-    if (d.n) {
-        GT_HIP(hipMemcpyAsync(out.rank.data(), d.seg, (size_t)d.n * 4, hipMemcpyDeviceToHost, st));
-        GT_HIP(hipMemcpyAsync(out.start.data(), d.start, (size_t)d.n * 4, hipMemcpyDeviceToHost, st));
-        GT_HIP(hipMemcpyAsync(out.end.data(), d.end, (size_t)d.n * 4, hipMemcpyDeviceToHost, st));
-    }
-    GT_HIP(hipStreamSynchronize(st));
+// the rows of `in` stably sorted by (key_seg, start[, key2]) and gathered, key_seg < n_seg; *perm (optional): the order
+gtars_status sorted_set(StreamFrame &fr, const DevSet &in, const u32 *key_seg, const u32 *key2, u32 n_seg, DevSet &out,
+                        u32 **perm = nullptr) {
+    u32 *p;
+    GT_TRY(sort_perm(fr, key_seg, in.start, key2, in.n, n_seg, &p));
+    GT_TRY(alloc_set(fr, in.n, out));
+    hipLaunchKernelGGL(k_gather3, dim3(grid_for(in.n)), dim3(256), 0, fr.st, p, in.n, in.seg, in.start, in.end, out.seg, out.start,
+                       out.end);
+    GT_HIP(hipGetLastError());
+    if (perm) *perm = p;
+    return GTARS_OK;
+}
+
+// reduce() of the device regions `in` (unsorted) whose segment keys are < n_seg
+gtars_status dev_reduce(StreamFrame &fr, const DevSet &in, u32 n_seg, DevSet &out, ReduceWork *work = nullptr) {
+    out = DevSet();
+    if (work) *work = ReduceWork();
+    const u32 n = in.n;
+    if (!n) return GTARS_OK;
+    hipStream_t st = fr.st;
+    DevSet S;
+    u32 *perm, *flag, *rid, *rmax;
+    GT_TRY(sorted_set(fr, in, in.seg, nullptr, n_seg, S, &perm));  // (segment, start), ties in input order
+    GT_TRY(fr.alloc(&flag, n));
+    GT_TRY(seg_max_pass(fr, false, S.seg, S.end, S.start, n, 0, flag));
+    u64 *off, m = 0;
+    GT_TRY(scan_total(fr, flag, n, &off, &m));
+    GT_TRY(fr.alloc(&rid, n));
+    hipLaunchKernelGGL(k_run_ids, dim3(grid_for(n)), dim3(256), 0, st, flag, off, n, rid);
+    GT_TRY(fr.alloc(&rmax, n));
+    GT_TRY(seg_max_pass(fr, true, rid, S.end, nullptr, n, 0, rmax));
+    GT_TRY(alloc_set(fr, m, out));
+    hipLaunchKernelGGL(k_reduce_write, dim3(grid_for(n)), dim3(256), 0, st, S.seg, S.start, flag, rid, rmax, n, out.seg, out.start,
+                       out.end);
+    GT_HIP(hipGetLastError());
+    if (work) *work = ReduceWork{perm, S.seg, S.start, S.end, rid};
     return GTARS_OK;
 }
 
@@ -300,10 +293,10 @@ gtars_status check_sizes(u64 n, u32 n_rank) {
     return require_device();
 }
 
-gtars_status reduce_cols(const SetCols &a, u32 n_rank, StreamFrame &fr, hipStream_t st, DevSet &out) {
-    u32 *seg, *start, *end;
-    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
-    return dev_reduce(seg, start, end, (u32)a.n, n_rank, fr, st, out);
+gtars_status reduce_cols(StreamFrame &fr, const SetCols &a, u32 n_rank, DevSet &out) {
+    DevSet in;
+    GT_TRY(upload_set(fr, a, in));
+    return dev_reduce(fr, in, n_rank, out);
 }
 
 // ------------------------------------------------------------------------------------------- setdiff / intersect
@@ -381,9 +374,10 @@ __global__ void k_sweep_seq(const u32 *__restrict__ as, const u32 *__restrict__ 
 }
 
 template <int MODE>
-gtars_status dev_sweep(const DevSet &A, const DevSet &B, u32 n_rank, StreamFrame &fr, hipStream_t st, DevSet &out) {
+gtars_status dev_sweep(StreamFrame &fr, const DevSet &A, const DevSet &B, u32 n_rank, DevSet &out) {
     out = DevSet();
     if (!A.n) return GTARS_OK;
+    hipStream_t st = fr.st;
     u32 *aoff, *boff, *dirty, *cnt;
     GT_TRY(fr.alloc(&aoff, (size_t)n_rank + 1));
     GT_TRY(fr.alloc(&boff, (size_t)n_rank + 1));
@@ -399,12 +393,9 @@ gtars_status dev_sweep(const DevSet &A, const DevSet &B, u32 n_rank, StreamFrame
     hipLaunchKernelGGL((k_sweep_seq<MODE, false>), dim3(grid_for(n_rank, 64)), dim3(64), 0, st, A.start, A.end, aoff, B.start, B.end,
                        boff, n_rank, dirty, cnt, nullptr, nullptr, nullptr, nullptr);
     u64 *off, m = 0;
-    GT_TRY(scan_counts(cnt, A.n, &off, &m, fr, st));
+    GT_TRY(scan_total(fr, cnt, A.n, &off, &m));
     if (m > SO_MAX_N) return fail(GTARS_ERR_CAPACITY, "set operation result too large: need " + std::to_string(m));
-    out.n = (u32)m;
-    GT_TRY(fr.alloc(&out.seg, m));
-    GT_TRY(fr.alloc(&out.start, m));
-    GT_TRY(fr.alloc(&out.end, m));
+    GT_TRY(alloc_set(fr, m, out));
     hipLaunchKernelGGL((k_sweep_par<MODE, true>), dim3(grid_for(A.n)), dim3(256), 0, st, A.seg, A.start, A.end, A.n, B.start, B.end,
                        boff, dirty, nullptr, off, out.seg, out.start, out.end);
     hipLaunchKernelGGL((k_sweep_seq<MODE, true>), dim3(grid_for(n_rank, 64)), dim3(64), 0, st, A.start, A.end, aoff, B.start, B.end,
@@ -416,13 +407,13 @@ gtars_status dev_sweep(const DevSet &A, const DevSet &B, u32 n_rank, StreamFrame
 template <int MODE>
 gtars_status two_set(const SetCols &a, const SetCols &b, u32 n_rank, SetOut &res) {
     GT_TRY(check_sizes(a.n + b.n, n_rank));
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
     DevSet A, B, R;
-    GT_TRY(reduce_cols(a, n_rank, fr, st, A));
-    GT_TRY(reduce_cols(b, n_rank, fr, st, B));
-    GT_TRY(dev_sweep<MODE>(A, B, n_rank, fr, st, R));
-    return download(R, st, res);
+    GT_TRY(reduce_cols(fr, a, n_rank, A));
+    GT_TRY(reduce_cols(fr, b, n_rank, B));
+    GT_TRY(dev_sweep<MODE>(fr, A, B, n_rank, R));
+    GT_TRY(download(fr, R, res));
+    return fr.drain();
 }
 
 // ------------------------------------------------------------------------------------------------------ closest
@@ -571,11 +562,11 @@ double jaccard_of(const SetTotals &t) {
 // ======================================================================================================= entries
 gtars_status setops_reduce(const SetCols &a, uint32_t n_rank, SetOut &res) {
     GT_TRY(check_sizes(a.n, n_rank));
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
     DevSet R;
-    GT_TRY(reduce_cols(a, n_rank, fr, st, R));
-    return download(R, st, res);
+    GT_TRY(reduce_cols(fr, a, n_rank, R));
+    GT_TRY(download(fr, R, res));
+    return fr.drain();
 }
 
 gtars_status setops_setdiff(const SetCols &a, const SetCols &b, uint32_t n_rank, SetOut &res) {
@@ -588,29 +579,16 @@ gtars_status setops_intersect(const SetCols &a, const SetCols &b, uint32_t n_ran
 
 gtars_status setops_totals(const SetCols &a, const SetCols &b, uint32_t n_rank, bool want_diff, SetTotals &out) {
     GT_TRY(check_sizes(a.n + b.n, n_rank));
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     // a and b side by side: reduce(a), reduce(b) and reduce(concat(a, b)) from the same columns
-    const u64 n = a.n + b.n;
-    u32 *seg, *start, *end;
-    GT_TRY(fr.alloc(&seg, n));
-    GT_TRY(fr.alloc(&start, n));
-    GT_TRY(fr.alloc(&end, n));
-    const SetCols *parts[2] = {&a, &b};
-    u64 at = 0;
-    for (const SetCols *p : parts) {
-        if (p->n) {
-            GT_HIP(hipMemcpyAsync(seg + at, p->rank, p->n * 4, hipMemcpyHostToDevice, st));
-            GT_HIP(hipMemcpyAsync(start + at, p->start, p->n * 4, hipMemcpyHostToDevice, st));
-            GT_HIP(hipMemcpyAsync(end + at, p->end, p->n * 4, hipMemcpyHostToDevice, st));
-        }
-        at += p->n;
-    }
-    DevSet A, B, U, D;
-    GT_TRY(dev_reduce(seg, start, end, (u32)a.n, n_rank, fr, st, A));
-    GT_TRY(dev_reduce(seg + a.n, start + a.n, end + a.n, (u32)b.n, n_rank, fr, st, B));
-    GT_TRY(dev_reduce(seg, start, end, (u32)n, n_rank, fr, st, U));
-    if (want_diff) GT_TRY(dev_sweep<SWEEP_SETDIFF>(A, B, n_rank, fr, st, D));
+    const SetCols parts[2] = {a, b};
+    DevSet C, A, B, U, D;
+    GT_TRY(upload_concat(fr, parts, 2, C));
+    GT_TRY(dev_reduce(fr, DevSet{C.seg, C.start, C.end, (u32)a.n}, n_rank, A));
+    GT_TRY(dev_reduce(fr, DevSet{C.seg + a.n, C.start + a.n, C.end + a.n, (u32)b.n}, n_rank, B));
+    GT_TRY(dev_reduce(fr, C, n_rank, U));
+    if (want_diff) GT_TRY(dev_sweep<SWEEP_SETDIFF>(fr, A, B, n_rank, D));
     u64 *acc;
     GT_TRY(fr.alloc(&acc, 4));
     GT_HIP(hipMemsetAsync(acc, 0, 4 * sizeof(u64), st));
@@ -621,8 +599,8 @@ gtars_status setops_totals(const SetCols &a, const SetCols &b, uint32_t n_rank, 
                                sets[k]->n, acc + k);
     GT_HIP(hipGetLastError());
     u64 h[4];
-    GT_HIP(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
+    GT_TRY(fr.download(h, acc, 4));
+    GT_TRY(fr.drain());
     out.a_bp = (u32)h[0];
     out.b_bp = (u32)h[1];
     out.union_bp = (u32)h[2];
@@ -637,36 +615,30 @@ gtars_status setops_closest(const SetCols &a, const SetCols &other, uint32_t n_r
     dist.clear();
     GT_TRY(check_sizes(std::max(a.n, other.n), n_rank));
     if (!other.n || !a.n) return GTARS_OK;
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     const u32 no = (u32)other.n, nq = (u32)a.n;
     // candidates: `other` stably sorted by (chromosome, start)
-    u32 *oseg, *ostart, *oend, *perm, *cseg, *cs, *ce, *coff, *maxw;
-    GT_TRY(upload_set(other, fr, st, &oseg, &ostart, &oend));
-    GT_TRY(fr.alloc(&perm, no));
-    const size_t sb = device_sort_perm_ws_bytes(no);
-    u8 *scratch;
-    GT_TRY(fr.alloc(&scratch, sb));
-    GT_TRY(device_sort_perm_ws(oseg, ostart, nullptr, no, n_rank, perm, scratch, sb, st));
-    GT_TRY(fr.alloc(&cseg, no));
-    GT_TRY(fr.alloc(&cs, no));
-    GT_TRY(fr.alloc(&ce, no));
-    hipLaunchKernelGGL(k_gather3, dim3(grid_for(no)), dim3(256), 0, st, perm, no, oseg, ostart, oend, cseg, cs, ce);
+    DevSet O, C, Q;
+    u32 *perm, *coff, *maxw;
+    GT_TRY(upload_set(fr, other, O));
+    GT_TRY(sorted_set(fr, O, O.seg, nullptr, n_rank, C, &perm));
     GT_TRY(fr.alloc(&coff, (size_t)n_rank + 1));
-    hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)no + 1)), dim3(256), 0, st, cseg, no, n_rank, coff);
+    hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)no + 1)), dim3(256), 0, st, C.seg, no, n_rank, coff);
     GT_TRY(fr.alloc(&maxw, n_rank));
     GT_HIP(hipMemsetAsync(maxw, 0, (size_t)std::max<u32>(n_rank, 1) * 4, st));
-    hipLaunchKernelGGL(k_max_width, dim3(grid_for((no + 63) / 64)), dim3(256), 0, st, cseg, cs, ce, no, maxw);
-    u32 *qr, *qs, *qe, *found, *bidx;
+    hipLaunchKernelGGL(k_max_width, dim3(grid_for((no + 63) / 64)), dim3(256), 0, st, C.seg, C.start, C.end, no, maxw);
+    u32 *found, *bidx;
     i64 *bd;
-    GT_TRY(upload_set(a, fr, st, &qr, &qs, &qe));
+    GT_TRY(upload_set(fr, a, Q));
     GT_TRY(fr.alloc(&found, nq));
     GT_TRY(fr.alloc(&bidx, nq));
     GT_TRY(fr.alloc(&bd, nq));
-    hipLaunchKernelGGL(k_closest, dim3(grid_for(nq)), dim3(256), 0, st, qr, qs, qe, nq, cs, ce, perm, coff, maxw, n_rank, found, bidx, bd);
+    hipLaunchKernelGGL(k_closest, dim3(grid_for(nq)), dim3(256), 0, st, Q.seg, Q.start, Q.end, nq, C.start, C.end, perm, coff, maxw, n_rank,
+                       found, bidx, bd);
     GT_HIP(hipGetLastError());
     u64 *off, m = 0;
-    GT_TRY(scan_counts(found, nq, &off, &m, fr, st));
+    GT_TRY(scan_total(fr, found, nq, &off, &m));
     u32 *o_self, *o_other;
     i64 *o_d;
     GT_TRY(fr.alloc(&o_self, m));
@@ -674,45 +646,30 @@ gtars_status setops_closest(const SetCols &a, const SetCols &other, uint32_t n_r
     GT_TRY(fr.alloc(&o_d, m));
     hipLaunchKernelGGL(k_closest_compact, dim3(grid_for(nq)), dim3(256), 0, st, found, off, bidx, bd, nq, o_self, o_other, o_d);
     GT_HIP(hipGetLastError());
-    self_idx.resize(m);
-    other_idx.resize(m);
-    dist.resize(m);
-    if (m) {
-        GT_HIP(hipMemcpyAsync(self_idx.data(), o_self, m * 4, hipMemcpyDeviceToHost, st));
-        GT_HIP(hipMemcpyAsync(other_idx.data(), o_other, m * 4, hipMemcpyDeviceToHost, st));
-        GT_HIP(hipMemcpyAsync(dist.data(), o_d, m * 8, hipMemcpyDeviceToHost, st));
-    }
-    GT_HIP(hipStreamSynchronize(st));
-    return GTARS_OK;
+    GT_TRY(fr.download(self_idx, o_self, m));
+    GT_TRY(fr.download(other_idx, o_other, m));
+    GT_TRY(fr.download(dist, o_d, m));
+    return fr.drain();
 }
 
 gtars_status setops_cluster(const SetCols &a, uint32_t n_rank, uint32_t max_gap, uint32_t *ids) {
     GT_TRY(check_sizes(a.n, n_rank));
     if (!a.n) return GTARS_OK;
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
     const u32 n = (u32)a.n;
-    u32 *seg, *start, *end, *perm, *sseg, *sstart, *send, *flag, *d_ids;
-    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
-    GT_TRY(fr.alloc(&perm, n));
-    const size_t sb = device_sort_perm_ws_bytes(n);
-    u8 *scratch;
-    GT_TRY(fr.alloc(&scratch, sb));
-    GT_TRY(device_sort_perm_ws(seg, start, end, n, n_rank, perm, scratch, sb, st));  // (chromosome, start, end)
-    GT_TRY(fr.alloc(&sseg, n));
-    GT_TRY(fr.alloc(&sstart, n));
-    GT_TRY(fr.alloc(&send, n));
-    hipLaunchKernelGGL(k_gather3, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, sseg, sstart, send);
+    DevSet A, S;
+    u32 *perm, *flag, *d_ids;
+    GT_TRY(upload_set(fr, a, A));
+    GT_TRY(sorted_set(fr, A, A.seg, A.end, n_rank, S, &perm));  // (chromosome, start, end)
     GT_TRY(fr.alloc(&flag, n));
-    GT_TRY(seg_max_pass(false, sseg, send, sstart, n, max_gap, flag, fr, st));
+    GT_TRY(seg_max_pass(fr, false, S.seg, S.end, S.start, n, max_gap, flag));
     u64 *off, m = 0;
-    GT_TRY(scan_counts(flag, n, &off, &m, fr, st));
+    GT_TRY(scan_total(fr, flag, n, &off, &m));
     GT_TRY(fr.alloc(&d_ids, n));
-    hipLaunchKernelGGL(k_cluster_scatter, dim3(grid_for(n)), dim3(256), 0, st, perm, flag, off, n, d_ids);
+    hipLaunchKernelGGL(k_cluster_scatter, dim3(grid_for(n)), dim3(256), 0, fr.st, perm, flag, off, n, d_ids);
     GT_HIP(hipGetLastError());
-    GT_HIP(hipMemcpyAsync(ids, d_ids, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
-    return GTARS_OK;
+    GT_TRY(fr.download(ids, d_ids, n));
+    return fr.drain();
 }
 
 gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t n_rank, double *out) {
@@ -727,26 +684,24 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
     for (u64 i = 0; i < n_sets; ++i)
         for (u64 j = 0; j < n_sets; ++j) out[i * n_sets + j] = i == j ? 1.0 : 0.0;
     if (!n) return GTARS_OK;  // every off-diagonal pair has union 0
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
-    // every set reduced in one pass: segment = set * n_rank + chromosome rank
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
+    // every set reduced in one pass: segment = set * n_rank + chromosome rank, built set by set between the copies
     std::vector<u32> hseg(n);
-    u32 *seg, *start, *end;
-    GT_TRY(fr.alloc(&start, n));
-    GT_TRY(fr.alloc(&end, n));
+    DevSet C, R;
+    C.n = (u32)n;
+    GT_TRY(fr.alloc(&C.start, n));
+    GT_TRY(fr.alloc(&C.end, n));
     u64 at = 0;
     for (u64 k = 0; k < n_sets; ++k) {
         const SetCols &s = sets[k];
         for (u64 i = 0; i < s.n; ++i) hseg[at + i] = (u32)k * nr + s.rank[i];
-        if (s.n) {
-            GT_HIP(hipMemcpyAsync(start + at, s.start, s.n * 4, hipMemcpyHostToDevice, st));
-            GT_HIP(hipMemcpyAsync(end + at, s.end, s.n * 4, hipMemcpyHostToDevice, st));
-        }
+        GT_TRY(fr.upload_to(C.start + at, s.start, s.n));
+        GT_TRY(fr.upload_to(C.end + at, s.end, s.n));
         at += s.n;
     }
-    GT_TRY(fr.upload(&seg, hseg.data(), n, st));
-    DevSet R;
-    GT_TRY(dev_reduce(seg, start, end, (u32)n, n_seg, fr, st, R));
+    GT_TRY(fr.upload(&C.seg, hseg.data(), n));
+    GT_TRY(dev_reduce(fr, C, n_seg, R));
     u32 *seg_off, *dirty, *w, *d_set_off;
     GT_TRY(fr.alloc(&seg_off, (size_t)n_seg + 1));
     hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)R.n + 1)), dim3(256), 0, st, R.seg, R.n, n_seg, seg_off);
@@ -756,13 +711,13 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
     GT_TRY(fr.alloc(&w, R.n));
     hipLaunchKernelGGL(k_widths, dim3(grid_for(R.n)), dim3(256), 0, st, R.start, R.end, R.n, w);
     u64 *P, total = 0;
-    GT_TRY(scan_counts(w, R.n, &P, &total, fr, st));
-    std::vector<u32> h_seg_off((size_t)n_seg + 1), h_dirty(n_sets), set_off(n_sets + 1);
-    GT_HIP(hipMemcpyAsync(h_seg_off.data(), seg_off, h_seg_off.size() * 4, hipMemcpyDeviceToHost, st));
-    GT_HIP(hipMemcpyAsync(h_dirty.data(), dirty, n_sets * 4, hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
+    GT_TRY(scan_total(fr, w, R.n, &P, &total));
+    std::vector<u32> h_seg_off, h_dirty, set_off(n_sets + 1);
+    GT_TRY(fr.download(h_seg_off, seg_off, (size_t)n_seg + 1));
+    GT_TRY(fr.download(h_dirty, dirty, n_sets));
+    GT_TRY(fr.drain());
     for (u64 k = 0; k <= n_sets; ++k) set_off[k] = h_seg_off[k * nr];
-    GT_TRY(fr.upload(&d_set_off, set_off.data(), set_off.size(), st));
+    GT_TRY(fr.upload(&d_set_off, set_off.data(), set_off.size()));
     // work list over the pairs of clean sets (no inverted region after reduce)
     std::vector<uint2> pairs;
     std::vector<uint4> items;
@@ -784,11 +739,11 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
         uint4 *d_items;
         u64 *inter;
         double *dM;
-        GT_TRY(fr.upload(&d_pairs, pairs.data(), pairs.size(), st));
+        GT_TRY(fr.upload(&d_pairs, pairs.data(), pairs.size()));
         GT_TRY(fr.alloc(&inter, pairs.size()));
         GT_HIP(hipMemsetAsync(inter, 0, pairs.size() * 8, st));
         if (!items.empty()) {
-            GT_TRY(fr.upload(&d_items, items.data(), items.size(), st));
+            GT_TRY(fr.upload(&d_items, items.data(), items.size()));
             for (size_t b = 0; b < items.size(); b += (1u << 20)) {  // grids of at most 2^20 workgroups
                 const size_t nb = std::min<size_t>(items.size() - b, 1u << 20);
                 hipLaunchKernelGGL(k_pair_inter, dim3((unsigned)nb), dim3(256), 0, st, d_items + b, R.seg, R.start, R.end, P, d_set_off,
@@ -796,17 +751,18 @@ gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t 
             }
         }
         GT_TRY(fr.alloc(&dM, n_sets * n_sets));
-        GT_HIP(hipMemcpyAsync(dM, out, n_sets * n_sets * 8, hipMemcpyHostToDevice, st));
+        GT_TRY(fr.upload_to(dM, out, n_sets * n_sets));
         hipLaunchKernelGGL(k_pair_finish, dim3(grid_for(pairs.size())), dim3(256), 0, st, d_pairs, (u32)pairs.size(), inter, P, d_set_off,
                            (u32)n_sets, dM);
         GT_HIP(hipGetLastError());
-        GT_HIP(hipMemcpyAsync(out, dM, n_sets * n_sets * 8, hipMemcpyDeviceToHost, st));
-        GT_HIP(hipStreamSynchronize(st));
+        GT_TRY(fr.download(out, dM, n_sets * n_sets));
+        GT_TRY(fr.drain());
     }
     if (!dirty_pairs.empty()) {
         // a set that keeps an inverted region: the two-set path on the reduced sets, both orders
         SetOut h;
-        GT_TRY(download(R, st, h));
+        GT_TRY(download(fr, R, h));
+        GT_TRY(fr.drain());
         for (u32 k = 0; k < R.n; ++k) h.rank[k] %= nr;
         auto cols = [&](u32 k) { return SetCols{h.rank.data() + set_off[k], h.start.data() + set_off[k], h.end.data() + set_off[k],
                                                 (u64)(set_off[k + 1] - set_off[k])}; };
@@ -835,20 +791,6 @@ __global__ void k_fill(u32 *__restrict__ p, u32 n, u32 v) {
 // out[i] = table[idx[i]]
 __global__ void k_lookup(const u32 *__restrict__ idx, u32 n, const u32 *__restrict__ table, u32 *__restrict__ out) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) out[i] = table[idx[i]];
-}
-
-gtars_status download_u32(u32 *h, const u32 *d, u64 n, hipStream_t st) {
-    if (n) GT_HIP(hipMemcpyAsync(h, d, n * 4, hipMemcpyDeviceToHost, st));
-    return GTARS_OK;
-}
-
-// stable sort of n device rows by (seg, k1[, k2]); returns the permutation
-gtars_status sort_rows(const u32 *seg, const u32 *k1, const u32 *k2, u32 n, u32 n_seg, StreamFrame &fr, hipStream_t st, u32 **perm) {
-    GT_TRY(fr.alloc(perm, n));
-    const size_t sb = device_sort_perm_ws_bytes(n);
-    u8 *scratch;
-    GT_TRY(fr.alloc(&scratch, sb));
-    return device_sort_perm_ws(seg, k1, k2, n, n_seg, *perm, scratch, sb, st);
 }
 
 // ------------------------------------------------------------------------------------------------------- disjoin
@@ -1082,57 +1024,41 @@ __global__ void k_gather_widths(const u32 *__restrict__ perm, u32 n, const u32 *
     }
 }
 
-// rows of `a` sorted by (rank, start[, end]), gathered
-gtars_status sorted_cols(const SetCols &a, u32 n_rank, bool by_end, StreamFrame &fr, hipStream_t st, DevSet &out) {
-    const u32 n = (u32)a.n;
-    u32 *seg, *start, *end, *perm;
-    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
-    GT_TRY(sort_rows(seg, start, by_end ? end : nullptr, n, n_rank, fr, st, &perm));
-    out.n = n;
-    GT_TRY(fr.alloc(&out.seg, n));
-    GT_TRY(fr.alloc(&out.start, n));
-    GT_TRY(fr.alloc(&out.end, n));
-    hipLaunchKernelGGL(k_gather3, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, out.seg, out.start, out.end);
-    GT_HIP(hipGetLastError());
-    return GTARS_OK;
-}
-
 }  // namespace
 
 gtars_status setops_disjoin(const SetCols &a, uint32_t n_rank, SetOut &res) {
     GT_TRY(check_sizes(2 * a.n, n_rank));
     res = SetOut();
     if (!a.n) return GTARS_OK;
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     const u32 n = (u32)a.n, m = 2 * n;
-    u32 *seg, *start, *end, *ev_rank, *ev_pos, *perm, *srank, *spos, *opens, *closes, *keep;
-    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    DevSet A, R;
+    u32 *ev_rank, *ev_pos, *perm, *srank, *spos, *opens, *closes, *keep;
+    GT_TRY(upload_set(fr, a, A));
     GT_TRY(fr.alloc(&ev_rank, m));
     GT_TRY(fr.alloc(&ev_pos, m));
-    hipLaunchKernelGGL(k_dj_events, dim3(grid_for(n)), dim3(256), 0, st, seg, start, end, n, ev_rank, ev_pos);
-    GT_TRY(sort_rows(ev_rank, ev_pos, nullptr, m, n_rank, fr, st, &perm));
+    hipLaunchKernelGGL(k_dj_events, dim3(grid_for(n)), dim3(256), 0, st, A.seg, A.start, A.end, n, ev_rank, ev_pos);
+    GT_TRY(sort_perm(fr, ev_rank, ev_pos, nullptr, m, n_rank, &perm));
     GT_TRY(fr.alloc(&srank, m));
     GT_TRY(fr.alloc(&spos, m));
     GT_TRY(fr.alloc(&opens, m));
     GT_TRY(fr.alloc(&closes, m));
-    hipLaunchKernelGGL(k_dj_gather, dim3(grid_for(m)), dim3(256), 0, st, perm, m, ev_rank, ev_pos, start, end, srank, spos, opens, closes);
+    hipLaunchKernelGGL(k_dj_gather, dim3(grid_for(m)), dim3(256), 0, st, perm, m, ev_rank, ev_pos, A.start, A.end, srank, spos, opens,
+                       closes);
     u64 *co, *cc, *off, t = 0, k = 0;
-    GT_TRY(scan_counts(opens, m, &co, &t, fr, st));
-    GT_TRY(scan_counts(closes, m, &cc, &t, fr, st));
+    GT_TRY(scan_total(fr, opens, m, &co, &t));
+    GT_TRY(scan_total(fr, closes, m, &cc, &t));
     GT_TRY(fr.alloc(&keep, m));
     hipLaunchKernelGGL(k_dj_pieces<false>, dim3(grid_for(m)), dim3(256), 0, st, srank, spos, co, cc, m, keep, nullptr, nullptr, nullptr,
                        nullptr);
-    GT_TRY(scan_counts(keep, m, &off, &k, fr, st));
-    DevSet R;
-    R.n = (u32)k;
-    GT_TRY(fr.alloc(&R.seg, k));
-    GT_TRY(fr.alloc(&R.start, k));
-    GT_TRY(fr.alloc(&R.end, k));
+    GT_TRY(scan_total(fr, keep, m, &off, &k));
+    GT_TRY(alloc_set(fr, k, R));
     hipLaunchKernelGGL(k_dj_pieces<true>, dim3(grid_for(m)), dim3(256), 0, st, srank, spos, co, cc, m, nullptr, off, R.seg, R.start,
                        R.end);
     GT_HIP(hipGetLastError());
-    return download(R, st, res);
+    GT_TRY(download(fr, R, res));
+    return fr.drain();
 }
 
 gtars_status setops_gaps(const SetCols &a, uint32_t n_rank, const std::vector<uint32_t> &size, const std::vector<uint32_t> &group,
@@ -1140,10 +1066,10 @@ gtars_status setops_gaps(const SetCols &a, uint32_t n_rank, const std::vector<ui
     GT_TRY(check_sizes(a.n + n_rank, n_rank));
     if (size.size() != n_rank || group.size() != n_rank) return fail(GTARS_ERR_INTERNAL, "gaps: per-rank tables of the wrong size");
     res = SetOut();
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     DevSet R;
-    GT_TRY(reduce_cols(a, n_rank, fr, st, R));
+    GT_TRY(reduce_cols(fr, a, n_rank, R));
     // full-chromosome gaps: ranks with a size that hold no region
     std::vector<u32> has(n_rank, 0);
     for (u64 i = 0; i < a.n; ++i) has[a.rank[i]] = 1;
@@ -1152,43 +1078,34 @@ gtars_status setops_gaps(const SetCols &a, uint32_t n_rank, const std::vector<ui
         if (size[r] && !has[r]) fr_rank.push_back(r), fr_end.push_back(size[r]);
     const u32 nf = (u32)fr_rank.size();
     u32 *d_size, *cnt = nullptr;
-    GT_TRY(fr.upload(&d_size, size.data(), n_rank, st));
+    GT_TRY(fr.upload(&d_size, size.data(), n_rank));
     u64 *off = nullptr, m = 0;
     if (R.n) {
         GT_TRY(fr.alloc(&cnt, R.n));
         hipLaunchKernelGGL(k_gaps<false>, dim3(grid_for(R.n)), dim3(256), 0, st, R.seg, R.start, R.end, R.n, d_size, cnt, nullptr, nullptr,
                            nullptr, nullptr);
-        GT_TRY(scan_counts(cnt, R.n, &off, &m, fr, st));
+        GT_TRY(scan_total(fr, cnt, R.n, &off, &m));
     }
     const u64 total = m + nf;
     if (total > SO_MAX_N) return fail(GTARS_ERR_CAPACITY, "gaps result too large: need " + std::to_string(total));
     if (!total) return GTARS_OK;
     const u32 g = (u32)total;
-    u32 *gseg, *gstart, *gend, *ggroup, *d_group, *perm;
-    GT_TRY(fr.alloc(&gseg, g));
-    GT_TRY(fr.alloc(&gstart, g));
-    GT_TRY(fr.alloc(&gend, g));
+    DevSet G, O;
+    u32 *ggroup, *d_group;
+    GT_TRY(alloc_set(fr, g, G));
     if (R.n)
-        hipLaunchKernelGGL(k_gaps<true>, dim3(grid_for(R.n)), dim3(256), 0, st, R.seg, R.start, R.end, R.n, d_size, nullptr, off, gseg,
-                           gstart, gend);
-    if (nf) {
-        GT_HIP(hipMemcpyAsync(gseg + m, fr_rank.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
-        GT_HIP(hipMemsetAsync(gstart + m, 0, (size_t)nf * 4, st));
-        GT_HIP(hipMemcpyAsync(gend + m, fr_end.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
-    }
+        hipLaunchKernelGGL(k_gaps<true>, dim3(grid_for(R.n)), dim3(256), 0, st, R.seg, R.start, R.end, R.n, d_size, nullptr, off, G.seg,
+                           G.start, G.end);
+    GT_TRY(fr.upload_to(G.seg + m, fr_rank.data(), nf));
+    if (nf) GT_HIP(hipMemsetAsync(G.start + m, 0, (size_t)nf * 4, st));
+    GT_TRY(fr.upload_to(G.end + m, fr_end.data(), nf));
     // karyotypic order: (key, start), names of one key bytewise (rank order)
-    GT_TRY(fr.upload(&d_group, group.data(), n_rank, st));
+    GT_TRY(fr.upload(&d_group, group.data(), n_rank));
     GT_TRY(fr.alloc(&ggroup, g));
-    hipLaunchKernelGGL(k_lookup, dim3(grid_for(g)), dim3(256), 0, st, gseg, g, d_group, ggroup);
-    GT_TRY(sort_rows(ggroup, gstart, gseg, g, std::max<u32>(n_group, 1), fr, st, &perm));
-    DevSet O;
-    O.n = g;
-    GT_TRY(fr.alloc(&O.seg, g));
-    GT_TRY(fr.alloc(&O.start, g));
-    GT_TRY(fr.alloc(&O.end, g));
-    hipLaunchKernelGGL(k_gather3, dim3(grid_for(g)), dim3(256), 0, st, perm, g, gseg, gstart, gend, O.seg, O.start, O.end);
-    GT_HIP(hipGetLastError());
-    return download(O, st, res);
+    hipLaunchKernelGGL(k_lookup, dim3(grid_for(g)), dim3(256), 0, st, G.seg, g, d_group, ggroup);
+    GT_TRY(sorted_set(fr, G, ggroup, G.seg, std::max<u32>(n_group, 1), O));
+    GT_TRY(download(fr, O, res));
+    return fr.drain();
 }
 
 gtars_status setops_consensus(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &uni, std::vector<uint32_t> &count) {
@@ -1200,41 +1117,33 @@ gtars_status setops_consensus(const std::vector<SetCols> &sets, uint32_t n_rank,
     if (sets.size() >= 0xFFFFFFFFull) return fail(GTARS_ERR_INVALID_ARG, "too many region sets");
     if (!n) return GTARS_OK;
     const u32 n_sets = (u32)sets.size();
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     // the concatenation, with each row's set
-    u32 *seg, *start, *end, *set;
-    GT_TRY(fr.alloc(&seg, n));
-    GT_TRY(fr.alloc(&start, n));
-    GT_TRY(fr.alloc(&end, n));
+    DevSet C, U;
+    u32 *set;
+    GT_TRY(upload_concat(fr, sets.data(), n_sets, C));
     GT_TRY(fr.alloc(&set, n));
     u64 at = 0;
     for (u32 k = 0; k < n_sets; ++k) {
-        const SetCols &s = sets[k];
-        if (s.n) {
-            GT_HIP(hipMemcpyAsync(seg + at, s.rank, s.n * 4, hipMemcpyHostToDevice, st));
-            GT_HIP(hipMemcpyAsync(start + at, s.start, s.n * 4, hipMemcpyHostToDevice, st));
-            GT_HIP(hipMemcpyAsync(end + at, s.end, s.n * 4, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_fill, dim3(grid_for(s.n)), dim3(256), 0, st, set + at, (u32)s.n, k);
-        }
-        at += s.n;
+        if (sets[k].n) hipLaunchKernelGGL(k_fill, dim3(grid_for(sets[k].n)), dim3(256), 0, st, set + at, (u32)sets[k].n, k);
+        at += sets[k].n;
     }
-    DevSet U;
     ReduceWork w;
-    GT_TRY(dev_reduce(seg, start, end, (u32)n, n_rank, fr, st, U, &w));
+    GT_TRY(dev_reduce(fr, C, n_rank, U, &w));
     // a region can only hit its own run: a later run starts past every end of the earlier ones
     u32 *hit_set, *perm, *d_count;
     GT_TRY(fr.alloc(&hit_set, n));
     hipLaunchKernelGGL(k_cons_hits, dim3(grid_for(n)), dim3(256), 0, st, w.perm, set, w.sstart, w.send, w.rid, U.start, U.end, (u32)n,
                        n_sets, hit_set);
-    GT_TRY(sort_rows(w.rid, hit_set, nullptr, (u32)n, U.n, fr, st, &perm));
+    GT_TRY(sort_perm(fr, w.rid, hit_set, nullptr, (u32)n, U.n, &perm));
     GT_TRY(fr.alloc(&d_count, U.n));
     GT_HIP(hipMemsetAsync(d_count, 0, (size_t)U.n * 4, st));
     hipLaunchKernelGGL(k_cons_count, dim3(grid_for(n)), dim3(256), 0, st, perm, w.rid, hit_set, (u32)n, n_sets, d_count);
     GT_HIP(hipGetLastError());
-    count.resize(U.n);
-    GT_TRY(download_u32(count.data(), d_count, U.n, st));
-    return download(U, st, uni);
+    GT_TRY(fr.download(count, d_count, U.n));
+    GT_TRY(download(fr, U, uni));
+    return fr.drain();
 }
 
 template <bool NEAREST, class T>
@@ -1242,25 +1151,24 @@ gtars_status neighbors(const SetCols &a, uint32_t n_rank, std::vector<T> &res) {
     GT_TRY(check_sizes(a.n, n_rank));
     res.clear();
     if (a.n < 2) return GTARS_OK;
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
-    DevSet S;
-    GT_TRY(sorted_cols(a, n_rank, true, fr, st, S));
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
+    DevSet A, S;
+    GT_TRY(upload_set(fr, a, A));
+    GT_TRY(sorted_set(fr, A, A.seg, A.end, n_rank, S));
     u32 *keep;
     GT_TRY(fr.alloc(&keep, S.n));
     hipLaunchKernelGGL((k_neighbors<NEAREST, false>), dim3(grid_for(S.n)), dim3(256), 0, st, S.seg, S.start, S.end, S.n, keep, nullptr,
                        nullptr, nullptr);
     u64 *off, m = 0;
-    GT_TRY(scan_counts(keep, S.n, &off, &m, fr, st));
+    GT_TRY(scan_total(fr, keep, S.n, &off, &m));
     T *out;
     GT_TRY(fr.alloc(&out, m));
     hipLaunchKernelGGL((k_neighbors<NEAREST, true>), dim3(grid_for(S.n)), dim3(256), 0, st, S.seg, S.start, S.end, S.n, nullptr, off,
                        (i64 *)out, (u32 *)out);
     GT_HIP(hipGetLastError());
-    res.resize(m);
-    if (m) GT_HIP(hipMemcpyAsync(res.data(), out, m * sizeof(T), hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
-    return GTARS_OK;
+    GT_TRY(fr.download(res, out, m));
+    return fr.drain();
 }
 
 gtars_status setops_neighbor_distances(const SetCols &a, uint32_t n_rank, std::vector<int64_t> &out) {
@@ -1280,21 +1188,22 @@ gtars_status setops_distribution(const SetCols &a, uint32_t n_rank, uint32_t n_b
     count.clear();
     if (!bin_size || (with_sizes && !n_bins) || limit.size() != n_rank) return fail(GTARS_ERR_INTERNAL, "distribution: bad bin layout");
     if (!a.n) return GTARS_OK;
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     const u32 n = (u32)a.n;
-    u32 *seg, *start, *end, *d_limit, *krank, *krid, *perm, *head;
-    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
-    GT_TRY(fr.upload(&d_limit, limit.data(), std::max<u32>(n_rank, 1), st));
+    DevSet A;
+    u32 *d_limit, *krank, *krid, *perm, *head;
+    GT_TRY(upload_set(fr, a, A));
+    GT_TRY(fr.upload(&d_limit, limit.data(), std::max<u32>(n_rank, 1)));
     GT_TRY(fr.alloc(&krank, n));
     GT_TRY(fr.alloc(&krid, n));
-    hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(n)), dim3(256), 0, st, seg, start, end, n, n_rank, n_bins, bin_size, (int)with_sizes,
-                       d_limit, krank, krid);
-    GT_TRY(sort_rows(krank, krid, nullptr, n, n_rank + 1, fr, st, &perm));
+    hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(n)), dim3(256), 0, st, A.seg, A.start, A.end, n, n_rank, n_bins, bin_size,
+                       (int)with_sizes, d_limit, krank, krid);
+    GT_TRY(sort_perm(fr, krank, krid, nullptr, n, n_rank + 1, &perm));
     GT_TRY(fr.alloc(&head, n));
     hipLaunchKernelGGL(k_rle_heads, dim3(grid_for(n)), dim3(256), 0, st, perm, krank, krid, n, n_rank, head);
     u64 *off, m = 0;
-    GT_TRY(scan_counts(head, n, &off, &m, fr, st));
+    GT_TRY(scan_total(fr, head, n, &off, &m));
     if (!m) return GTARS_OK;
     u32 *orank, *orid, *pos, *cnt;
     GT_TRY(fr.alloc(&orank, m));
@@ -1304,44 +1213,39 @@ gtars_status setops_distribution(const SetCols &a, uint32_t n_rank, uint32_t n_b
     hipLaunchKernelGGL(k_rle_write, dim3(grid_for(n)), dim3(256), 0, st, perm, krank, krid, head, off, n, n_rank, (u32)m, orank, orid, pos);
     hipLaunchKernelGGL(k_rle_counts, dim3(grid_for(m)), dim3(256), 0, st, pos, (u32)m, cnt);
     GT_HIP(hipGetLastError());
-    rank.resize(m);
-    rid.resize(m);
-    count.resize(m);
-    GT_TRY(download_u32(rank.data(), orank, m, st));
-    GT_TRY(download_u32(rid.data(), orid, m, st));
-    GT_TRY(download_u32(count.data(), cnt, m, st));
-    GT_HIP(hipStreamSynchronize(st));
-    return GTARS_OK;
+    GT_TRY(fr.download(rank, orank, m));
+    GT_TRY(fr.download(rid, orid, m));
+    GT_TRY(fr.download(count, cnt, m));
+    return fr.drain();
 }
 
 gtars_status setops_chrom_stats(const SetCols &a, uint32_t n_rank, std::vector<ChromStat> &out) {
     GT_TRY(check_sizes(a.n, n_rank));
     out.assign(n_rank, ChromStat{0, 0, 0, 0, 0, 0.0, 0.0});
     if (!a.n) return GTARS_OK;
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     const u32 n = (u32)a.n, nr = std::max<u32>(n_rank, 1);
-    u32 *seg, *start, *end, *w, *perm, *sseg, *ss, *se, *sw, *off, *min_s, *max_e, *cnt, *min_w, *max_w;
+    DevSet A, S;
+    u32 *w, *perm, *sw, *off, *min_s, *max_e, *cnt, *min_w, *max_w;
     u64 *wsum;
     double *mean, *median;
-    GT_TRY(upload_set(a, fr, st, &seg, &start, &end));
+    GT_TRY(upload_set(fr, a, A));
     GT_TRY(fr.alloc(&w, n));
-    hipLaunchKernelGGL(k_widths, dim3(grid_for(n)), dim3(256), 0, st, start, end, n, w);
-    GT_TRY(sort_rows(seg, w, nullptr, n, n_rank, fr, st, &perm));  // (rank, width)
-    GT_TRY(fr.alloc(&sseg, n));
-    GT_TRY(fr.alloc(&ss, n));
-    GT_TRY(fr.alloc(&se, n));
+    hipLaunchKernelGGL(k_widths, dim3(grid_for(n)), dim3(256), 0, st, A.start, A.end, n, w);
+    GT_TRY(sort_perm(fr, A.seg, w, nullptr, n, n_rank, &perm));  // (rank, width)
+    GT_TRY(alloc_set(fr, n, S));
     GT_TRY(fr.alloc(&sw, n));
-    hipLaunchKernelGGL(k_gather_widths, dim3(grid_for(n)), dim3(256), 0, st, perm, n, seg, start, end, sseg, ss, se, sw);
+    hipLaunchKernelGGL(k_gather_widths, dim3(grid_for(n)), dim3(256), 0, st, perm, n, A.seg, A.start, A.end, S.seg, S.start, S.end, sw);
     GT_TRY(fr.alloc(&off, (size_t)nr + 1));
-    hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)n + 1)), dim3(256), 0, st, sseg, n, n_rank, off);
+    hipLaunchKernelGGL(k_seg_offsets, dim3(grid_for((u64)n + 1)), dim3(256), 0, st, S.seg, n, n_rank, off);
     GT_TRY(fr.alloc(&min_s, nr));
     GT_TRY(fr.alloc(&max_e, nr));
     GT_TRY(fr.alloc(&wsum, nr));
     GT_HIP(hipMemsetAsync(min_s, 0xFF, (size_t)nr * 4, st));
     GT_HIP(hipMemsetAsync(max_e, 0, (size_t)nr * 4, st));
     GT_HIP(hipMemsetAsync(wsum, 0, (size_t)nr * 8, st));
-    hipLaunchKernelGGL(k_stat_bounds, dim3(grid_for((n + 63) / 64)), dim3(256), 0, st, sseg, ss, se, n, min_s, max_e, wsum);
+    hipLaunchKernelGGL(k_stat_bounds, dim3(grid_for((n + 63) / 64)), dim3(256), 0, st, S.seg, S.start, S.end, n, min_s, max_e, wsum);
     GT_TRY(fr.alloc(&cnt, nr));
     GT_TRY(fr.alloc(&min_w, nr));
     GT_TRY(fr.alloc(&max_w, nr));
@@ -1349,16 +1253,16 @@ gtars_status setops_chrom_stats(const SetCols &a, uint32_t n_rank, std::vector<C
     GT_TRY(fr.alloc(&median, nr));
     hipLaunchKernelGGL(k_stat_finish, dim3(grid_for(n_rank)), dim3(256), 0, st, off, sw, wsum, n_rank, cnt, min_w, max_w, mean, median);
     GT_HIP(hipGetLastError());
-    std::vector<u32> h_cnt(nr), h_min_s(nr), h_max_e(nr), h_min_w(nr), h_max_w(nr);
-    std::vector<double> h_mean(nr), h_median(nr);
-    GT_TRY(download_u32(h_cnt.data(), cnt, n_rank, st));
-    GT_TRY(download_u32(h_min_s.data(), min_s, n_rank, st));
-    GT_TRY(download_u32(h_max_e.data(), max_e, n_rank, st));
-    GT_TRY(download_u32(h_min_w.data(), min_w, n_rank, st));
-    GT_TRY(download_u32(h_max_w.data(), max_w, n_rank, st));
-    GT_HIP(hipMemcpyAsync(h_mean.data(), mean, (size_t)n_rank * 8, hipMemcpyDeviceToHost, st));
-    GT_HIP(hipMemcpyAsync(h_median.data(), median, (size_t)n_rank * 8, hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
+    std::vector<u32> h_cnt, h_min_s, h_max_e, h_min_w, h_max_w;
+    std::vector<double> h_mean, h_median;
+    GT_TRY(fr.download(h_cnt, cnt, n_rank));
+    GT_TRY(fr.download(h_min_s, min_s, n_rank));
+    GT_TRY(fr.download(h_max_e, max_e, n_rank));
+    GT_TRY(fr.download(h_min_w, min_w, n_rank));
+    GT_TRY(fr.download(h_max_w, max_w, n_rank));
+    GT_TRY(fr.download(h_mean, mean, n_rank));
+    GT_TRY(fr.download(h_median, median, n_rank));
+    GT_TRY(fr.drain());
     for (u32 r = 0; r < n_rank; ++r)
         if (h_cnt[r]) out[r] = ChromStat{h_cnt[r], h_min_s[r], h_max_e[r], h_min_w[r], h_max_w[r], h_mean[r], h_median[r]};
     return GTARS_OK;
@@ -1374,16 +1278,14 @@ extern "C" gtars_status gtars_debug_seg_max(const uint32_t *seg, const uint32_t 
         if (n && (!seg || !val || !out || (!inclusive && !start))) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
         GT_TRY(check_sizes(n, 0));
         if (!n) return GTARS_OK;
-        hipStream_t st = nullptr;
-        StreamFrame fr(st);
+        StreamFrame fr(nullptr);
         u32 *d_seg, *d_val, *d_start = nullptr, *d_out;
-        GT_TRY(fr.upload(&d_seg, seg, (size_t)n, st));
-        GT_TRY(fr.upload(&d_val, val, (size_t)n, st));
-        if (!inclusive) GT_TRY(fr.upload(&d_start, start, (size_t)n, st));
+        GT_TRY(fr.upload(&d_seg, seg, (size_t)n));
+        GT_TRY(fr.upload(&d_val, val, (size_t)n));
+        if (!inclusive) GT_TRY(fr.upload(&d_start, start, (size_t)n));
         GT_TRY(fr.alloc(&d_out, (size_t)n));
-        GT_TRY(seg_max_pass(inclusive != 0, d_seg, d_val, d_start, (u32)n, gap, d_out, fr, st));
-        GT_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        GT_HIP(hipStreamSynchronize(st));
-        return GTARS_OK;
+        GT_TRY(seg_max_pass(fr, inclusive != 0, d_seg, d_val, d_start, (u32)n, gap, d_out));
+        GT_TRY(fr.download(out, d_out, (size_t)n));
+        return fr.drain();
     });
 }

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "../../include/gtars_amd_debug.h"
+#include "pipeline.h"
 #include "scan.h"
 
 namespace gtars {
@@ -779,19 +780,13 @@ extern "C" gtars_status gtars_debug_sort_perm(const uint32_t *chrom, const uint3
         if (n_chrom > 0x7FFFFFFFu) return fail(GTARS_ERR_INVALID_ARG, "too many chromosomes");
         GT_TRY(require_device());
         if (!n) return GTARS_OK;
-        hipStream_t st = nullptr;
-        StreamFrame fr(st);
+        StreamFrame fr(nullptr);
         u32 *dc, *d1, *d2 = nullptr, *perm;
-        u8 *scratch;
-        GT_TRY(fr.upload(&dc, chrom, (size_t)n, st));
-        GT_TRY(fr.upload(&d1, k1, (size_t)n, st));
-        if (k2) GT_TRY(fr.upload(&d2, k2, (size_t)n, st));
-        GT_TRY(fr.alloc(&perm, (size_t)n));
-        const size_t sb = device_sort_perm_ws_bytes((u32)n);
-        GT_TRY(fr.alloc(&scratch, sb));
-        GT_TRY(device_sort_perm_ws(dc, d1, d2, (u32)n, n_chrom, perm, scratch, sb, st));
-        GT_HIP(hipMemcpyAsync(perm_out, perm, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        GT_HIP(hipStreamSynchronize(st));
-        return GTARS_OK;
+        GT_TRY(fr.upload(&dc, chrom, (size_t)n));
+        GT_TRY(fr.upload(&d1, k1, (size_t)n));
+        if (k2) GT_TRY(fr.upload(&d2, k2, (size_t)n));
+        GT_TRY(sort_perm(fr, dc, d1, d2, (u32)n, n_chrom, &perm));
+        GT_TRY(fr.download(perm_out, perm, (size_t)n));
+        return fr.drain();
     });
 }

@@ -25,6 +25,7 @@
 #include <memory>
 
 #include "common.h"
+#include "pipeline.h"
 #include "scan.h"
 #include "uniwig.h"
 
@@ -283,13 +284,9 @@ gtars_status launch_cov(const u32 *open, const u32 *close, u32 n, u32 sub_open, 
 // one column, ascending, on the device
 gtars_status sorted_column(StreamFrame &fr, const u32 *h, u32 n, DevBuf<u32> &out) {
     u32 *raw, *perm;
-    u8 *scratch;
-    const size_t sb = device_sort_perm_ws_bytes(n);
     GT_TRY(out.alloc(n));
-    GT_TRY(fr.upload(&raw, h, (size_t)n, fr.st));
-    GT_TRY(fr.alloc(&perm, (size_t)n));
-    GT_TRY(fr.alloc(&scratch, sb));
-    GT_TRY(device_sort_perm_ws(raw, raw, nullptr, n, 1, perm, scratch, sb, fr.st));
+    GT_TRY(fr.upload(&raw, h, (size_t)n));
+    GT_TRY(sort_perm(fr, raw, raw, nullptr, n, 1, &perm));
     return device_gather_u32(raw, perm, n, out.p, fr.st);
 }
 
@@ -306,8 +303,7 @@ gtars_status cov_prepare(const u32 *opens, const u32 *closes, u64 n, u32 chrom_s
         GT_TRY(sorted_column(fr, closes, t.n, t.e));
         t.close = t.e.p;
     }
-    GT_HIP(hipStreamSynchronize(fr.st));
-    return GTARS_OK;
+    return fr.drain();
 }
 
 template <class T>
@@ -336,26 +332,19 @@ gtars_status cov_compact(const u32 *d_counts, u64 len, u32 S, u32 **o0, u32 **o1
         *o1 = e1.release();
         return GTARS_OK;
     }
-    hipStream_t st = nullptr;
-    StreamFrame fr(st);
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
     const u64 nb = (len + CMP_TILE - 1) / CMP_TILE;
     if (nb > 0x7FFFFFFFull) return fail(GTARS_ERR_INVALID_ARG, "uniwig: track too long");
     u32 *bc;
-    u64 *off;
-    u8 *ws;
-    const size_t wsb = scan_ws_bytes(nb);
     GT_TRY(fr.alloc(&bc, (size_t)nb));
-    GT_TRY(fr.alloc(&off, (size_t)nb + 1));
-    GT_TRY(fr.alloc(&ws, wsb));
     {
         ProfScope ps("k_cov_flag_count", st);
         hipLaunchKernelGGL(k_cov_flag_count<MODE>, dim3((unsigned)nb), dim3(CMP_TPB), 0, st, d_counts, len, bc);
         GT_HIP(hipGetLastError());
     }
-    GT_TRY(launch_scan_u32_to_u64(bc, nb, off, ws, wsb, st));
-    u64 flagged = 0;
-    GT_HIP(hipMemcpyAsync(&flagged, off + nb, sizeof(u64), hipMemcpyDeviceToHost, st));
-    GT_HIP(hipStreamSynchronize(st));
+    u64 *off, flagged = 0;
+    GT_TRY(scan_total(fr, bc, nb, &off, &flagged));
     const u64 n = MODE == CMP_RUNS ? flagged + 1 : flagged;
     const int cols = MODE == CMP_RUNS ? 3 : 2;
     u32 *d_o[3] = {nullptr, nullptr, nullptr};
@@ -369,9 +358,9 @@ gtars_status cov_compact(const u32 *d_counts, u64 len, u32 S, u32 **o0, u32 **o1
     MallocArray<u32> h[3];
     for (int k = 0; k < cols; ++k) {
         if (!h[k].alloc(n)) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-        if (n) GT_HIP(hipMemcpyAsync(h[k].p, d_o[k], n * sizeof(u32), hipMemcpyDeviceToHost, st));
+        GT_TRY(fr.download(h[k].p, d_o[k], n));
     }
-    GT_HIP(hipStreamSynchronize(st));
+    GT_TRY(fr.drain());
     *o0 = h[0].release();
     *o1 = h[1].release();
     if (o2) *o2 = h[2].release();
@@ -433,16 +422,15 @@ gtars_status uniwig_counts(const uint32_t *opens, const uint32_t *closes, uint64
         // window after window: the count at a window's left edge comes from the same two searches as any span's
         u64 window = max_device_bytes ? std::max<u64>(max_device_bytes / sizeof(u32) / COV_TILE, 1) * COV_TILE : COV_DEFAULT_WINDOW;
         window = std::min(window, t.len);
-        hipStream_t st = nullptr;
-        StreamFrame fr(st);
+        StreamFrame fr(nullptr);
         u32 *d;
         GT_TRY(fr.alloc(&d, (size_t)window));
         for (u64 w = 0; w < t.len; w += window) {
             const u64 wl = std::min(window, t.len - w);
-            GT_TRY(launch_cov(t.open, t.close, t.n, t.sub_open, t.add_close, t.first + w, wl, d, st));
-            GT_HIP(hipMemcpyAsync(h.p + w, d, wl * sizeof(u32), hipMemcpyDeviceToHost, st));
+            GT_TRY(launch_cov(t.open, t.close, t.n, t.sub_open, t.add_close, t.first + w, wl, d, fr.st));
+            GT_TRY(fr.download(h.p + w, d, wl));
         }
-        GT_HIP(hipStreamSynchronize(st));
+        GT_TRY(fr.drain());
     }
     *first = t.first;
     *n_counts = t.len;
