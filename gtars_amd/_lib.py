@@ -181,6 +181,20 @@ _HOST_SIG = {
     "gtars_uniwig_format_counts": (C.c_int, [vp, u64, pp, pu64]),
     "gtars_uniwig_format_pairs": (C.c_int, [vp, vp, u64, pp, pu64]),
     "gtars_uniwig_format_bedgraph": (C.c_int, [cstr, vp, vp, vp, u64, pp, pu64]),
+    "gtars_assembly_from_fasta": (C.c_int, [cstr, pp]),
+    "gtars_assembly_from_fab": (C.c_int, [cstr, pp]),
+    "gtars_fab_write_from_fasta": (C.c_int, [cstr, cstr]),
+    "gtars_assembly_free": (None, [vp]),
+    "gtars_assembly_n_chrom": (u32, [vp]),
+    "gtars_assembly_chrom_name": (cstr, [vp, u32]),
+    "gtars_assembly_chrom_len": (u64, [vp, u32]),
+    "gtars_assembly_contains": (C.c_int, [vp, cstr]),
+    "gtars_assembly_sequence": (C.c_int, [vp, cstr, u64, u64, pp]),
+    "gtars_assembly_device": (C.c_int, [vp]),
+    "gtars_seqstats_piece_bytes": (u32, []),
+    "gtars_seqstats_counts_device": (C.c_int, [vp, vp, vp, vp, u64, C.c_int, vp, vp]),
+    "gtars_seqstats_gc": (C.c_int, [vp, vp, C.c_int, pp, pu64]),
+    "gtars_seqstats_dinucl": (C.c_int, [vp, vp, C.c_int, C.c_int, pp, pp, pu64]),
     "gtars_tokenizer_from_auto": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_config": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_bed": (C.c_int, [cstr, pp]),

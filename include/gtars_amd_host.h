@@ -229,6 +229,72 @@ gtars_status gtars_uniwig_format_bedgraph(const char *chrom, const uint32_t *run
                                           const uint32_t *run_count, uint64_t n, char **out_text, uint64_t *out_len);
 
 /* ------------------------------------------------------------------------
+ * Genome assemblies, GC content and dinucleotide frequencies  (gtars-genomicdist/src/models.rs:145-492,
+ * statistics.rs:331-483; gtars-python/src/models/genome_assembly.rs, genomic_distributions/tools.rs:8-70)
+ *
+ * An assembly handle holds the sequences on the host as the file has them: no case folding, N stays.  Its device
+ * image -- one packed byte buffer, every chromosome at a 16-byte-aligned offset and followed by at least 16 zero bytes,
+ * with u64 offset and length columns -- is built at the first counting call, on the device current then, which the
+ * handle keeps: host-column calls run there whatever the caller's current device is, the device-pointer call refuses
+ * another one.
+ *
+ * FASTA (GenomeAssembly::try_from, models.rs:163-187; plain files only).  The reference reads through an external
+ * FASTA crate; what its fixtures pin is kept, the rest is this library's choice:
+ *   - a record starts at a line whose first byte is '>'; its name is the text behind '>' up to the first ASCII
+ *     whitespace (an empty name is a name); the sequence is the following lines up to the next '>' line, joined,
+ *     every line stripped of trailing ASCII whitespace ('\r' included), blank lines adding nothing
+ *   - an empty file is an assembly without chromosomes; a non-empty file whose first byte is not '>' is
+ *     GTARS_ERR_PARSE; a missing or unreadable file GTARS_ERR_IO
+ *   - a repeated name keeps the LAST record (HashMap::insert); chromosome ids follow the first appearance of a name
+ * .fab (BinaryGenomeAssembly::from_file, models.rs:249-318): "GFAB", version u8 = 1, n_chroms u32 LE, per chromosome
+ *   { name_len u16 LE, name, file offset u64 LE, length u64 LE }, then the sequences.  GTARS_ERR_PARSE for a file that
+ *   is too short, has bad magic bytes, another version, a truncated index or index entry, a name that is not UTF-8, or
+ *   (checked per query by the reference, here on load) an entry with offset + length beyond the file.  A repeated
+ *   name resolves to the last entry.
+ * ---------------------------------------------------------------------- */
+typedef struct gtars_assembly gtars_assembly_t;
+gtars_status gtars_assembly_from_fasta(const char *path, gtars_assembly_t **out);
+gtars_status gtars_assembly_from_fab(const char *path, gtars_assembly_t **out);
+/* BinaryGenomeAssembly::write_from_fasta (models.rs:357-412): every record of the FASTA file in file order, repeated
+ * names included, sequences back to back behind the index */
+gtars_status gtars_fab_write_from_fasta(const char *fasta_path, const char *out_path);
+void gtars_assembly_free(gtars_assembly_t *a);
+uint32_t gtars_assembly_n_chrom(const gtars_assembly_t *a);
+const char *gtars_assembly_chrom_name(const gtars_assembly_t *a, uint32_t id);
+uint64_t gtars_assembly_chrom_len(const gtars_assembly_t *a, uint32_t id);
+int gtars_assembly_contains(const gtars_assembly_t *a, const char *name);
+/* seq_from_region (models.rs:190-210, 321-350): *out = the bytes [start, end) of chromosome `name`, borrowed from the
+ * handle; GTARS_ERR_INVALID_ARG for an unknown chromosome or unless end <= length && start <= end */
+gtars_status gtars_assembly_sequence(const gtars_assembly_t *a, const char *name, uint64_t start, uint64_t end,
+                                     const uint8_t **out);
+int gtars_assembly_device(const gtars_assembly_t *a); /* -1 until the first counting call */
+
+#define GTARS_SEQ_GC 0
+#define GTARS_SEQ_DINUCL 1
+/* bytes of a region one work item of the counting kernels covers (a region of width w is ceil(w / piece) of them) */
+uint32_t gtars_seqstats_piece_bytes(void);
+/* Integer counts of n device rows (d_chrom: chromosome ids of the assembly; every row start <= end <= length, anything
+ * else is GTARS_ERR_INVALID_ARG and is never read from the image), queued on `stream` (a hipStream_t) of the current
+ * device.  GTARS_SEQ_GC: d_out[n] = bytes of [start, end) that are G, C, g or c.  GTARS_SEQ_DINUCL: d_out[n * 16]
+ * (16-byte aligned) = windows (b[i], b[i + 1]) with start <= i and i + 1 < end whose bytes are both in ACGTacgt, in the
+ * order AA AC AG AT CA .. TT (DINUCL_ORDER, statistics.rs:386-391).  The stream is drained before the call returns (the
+ * number of work items comes to the host on the way).  n == 0 touches nothing. */
+gtars_status gtars_seqstats_counts_device(gtars_assembly_t *a, const uint32_t *d_chrom, const uint32_t *d_start,
+                                          const uint32_t *d_end, uint64_t n, int mode, uint32_t *d_out, void *stream);
+/* calc_gc_content / calc_dinucl_freq (statistics.rs:331-483) of rs.  Output rows: chromosomes in order of first
+ * appearance in rs (iter_chroms), set order within one.  ignore_unk != 0: chromosomes the assembly lacks and rows with
+ * end > length or start > end are skipped; otherwise the first such row in output order fails the call
+ * (GTARS_ERR_INVALID_ARG, the message names chr, start and end) before anything is launched.
+ *   gc:      *gc[*n_out] = count / (end - start) as f64, 0.0 for an empty region (every byte counts, N included)
+ *   dinucl:  *row_index[*n_out] = the row of rs behind each output row; *freq[*n_out * 16] = the counts as f64
+ *            (raw_counts != 0), else (count / total) * 100.0 with total = the row's valid windows, a zero row for
+ *            total == 0
+ * The divisions are host f64 arithmetic on the device's integer counts.  gtars_free each array. */
+gtars_status gtars_seqstats_gc(gtars_assembly_t *a, const gtars_regionset_t *rs, int ignore_unk, double **gc, uint64_t *n_out);
+gtars_status gtars_seqstats_dinucl(gtars_assembly_t *a, const gtars_regionset_t *rs, int raw_counts, int ignore_unk,
+                                   uint64_t **row_index, double **freq, uint64_t *n_out);
+
+/* ------------------------------------------------------------------------
  * Tokenizer  (gtars-tokenizers/src/tokenizer.rs:36-279, universe/mod.rs,
  * config.rs, utils/mod.rs:34-99, utils/special_tokens.rs)
  * ---------------------------------------------------------------------- */
