@@ -244,8 +244,15 @@ def mco_subset_by_overlaps(ix: "Index", qc, qs, qe, min_overlap: Optional[int] =
     if len(c) == 0:
         z = np.zeros(0, dtype=np.uint32)
         return z, z.copy(), z.copy()
-    rows = np.unique(np.stack([c.astype(np.uint64), s.astype(np.uint64), e.astype(np.uint64)], axis=1), axis=0)
-    return rows[:, 0].astype(np.uint32), rows[:, 1].astype(np.uint32), rows[:, 2].astype(np.uint32)
+    # the BTreeSet's order, chromosome by chromosome: (start, end) packed into one u64 key sorts like the pair
+    key = (s.astype(np.uint64) << np.uint64(32)) | e.astype(np.uint64)
+    oc, ok = [], []
+    for ch in np.unique(c):
+        k = np.unique(key[c == ch])
+        oc.append(np.full(len(k), ch, dtype=np.uint32))
+        ok.append(k)
+    oc, ok = np.concatenate(oc), np.concatenate(ok)
+    return oc, (ok >> np.uint64(32)).astype(np.uint32), (ok & np.uint64(0xFFFFFFFF)).astype(np.uint32)
 
 
 def irs_subset_by_overlaps(ix: "Index", src_chrom, src_start, src_end, qc, qs, qe, min_overlap: Optional[int] = None) -> np.ndarray:
