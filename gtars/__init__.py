@@ -9,15 +9,16 @@ nothing beyond region sets.  Sub-modules the hot path does not cover (refget, vr
 them raises ModuleNotFoundError, not a silent stub.  ``gtars.igd``, ``gtars.scoring`` and ``gtars.fragsplit`` are additive (the
 reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats`` is additive too: it holds
 ``GenomeAssembly``, ``BinaryGenomeAssembly``, ``calc_gc_content`` and ``calc_dinucl_freq``, which the reference keeps in
-``gtars.models`` and ``gtars.genomic_distributions``.
+``gtars.models`` and ``gtars.genomic_distributions``; ``gtars.signal`` likewise holds ``SignalMatrix`` and
+``calc_summary_signal``.
 """
 import sys as _sys
 
 import gtars_amd as _impl
-from gtars_amd import fragsplit, genomic_distributions, igd, lola, models, scoring, seqstats, tokenizers, utils  # noqa: F401
+from gtars_amd import fragsplit, genomic_distributions, igd, lola, models, scoring, seqstats, signal, tokenizers, utils  # noqa: F401
 
-for _name in ("tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats"):
+for _name in ("tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal"):
     _sys.modules[f"{__name__}.{_name}"] = getattr(_sys.modules[__name__], _name)
 
 __version__ = _impl.__version__
-__all__ = ["tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats"]
+__all__ = ["tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal"]

@@ -195,6 +195,23 @@ _HOST_SIG = {
     "gtars_seqstats_counts_device": (C.c_int, [vp, vp, vp, vp, u64, C.c_int, vp, vp]),
     "gtars_seqstats_gc": (C.c_int, [vp, vp, C.c_int, pp, pu64]),
     "gtars_seqstats_dinucl": (C.c_int, [vp, vp, C.c_int, C.c_int, pp, pp, pu64]),
+    "gtars_signal_from_tsv": (C.c_int, [cstr, pp]),
+    "gtars_signal_load_bin": (C.c_int, [cstr, pp]),
+    "gtars_signal_save_bin": (C.c_int, [vp, cstr]),
+    "gtars_signal_from_arrays": (C.c_int, [vp, u32, vp, vp, vp, u64, vp, vp, u32, pp]),
+    "gtars_signal_free": (None, [vp]),
+    "gtars_signal_n_regions": (u64, [vp]),
+    "gtars_signal_n_conditions": (u32, [vp]),
+    "gtars_signal_condition_name": (cstr, [vp, u32]),
+    "gtars_signal_n_chrom": (u32, [vp]),
+    "gtars_signal_chrom_name": (cstr, [vp, u32]),
+    "gtars_signal_chrom_ids": (vp, [vp]),
+    "gtars_signal_starts": (vp, [vp]),
+    "gtars_signal_ends": (vp, [vp]),
+    "gtars_signal_values": (vp, [vp]),
+    "gtars_signal_device": (C.c_int, [vp]),
+    "gtars_signal_summary": (C.c_int, [vp, vp, pp, pp, pp, pu64]),
+    "gtars_signal_summary_device": (C.c_int, [vp, vp, vp, vp, u64, vp, pp, pp, pp, pu64]),
     "gtars_tokenizer_from_auto": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_config": (C.c_int, [cstr, pp]),
     "gtars_tokenizer_from_bed": (C.c_int, [cstr, pp]),
@@ -276,6 +293,8 @@ _DEBUG_SIG = {
     "gtars_debug_sort_perm": (C.c_int, [vp, vp, vp, u64, u32, vp]),
     "gtars_debug_scan_u32": (C.c_int, [vp, u64, vp]),
     "gtars_debug_seg_max": (C.c_int, [vp, vp, vp, u64, u32, C.c_int, vp]),
+    "gtars_debug_signal_sort_elems": (u32, [u32]),
+    "gtars_debug_signal_split_hits": (u32, []),
 }
 
 # every symbol the headers declare must resolve -- fail loudly otherwise (GTARS_AMD_LIB_OLDER=1, A/B tooling only: an older

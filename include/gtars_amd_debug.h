@@ -61,6 +61,15 @@ gtars_status gtars_debug_scan_u32(const uint32_t *counts, uint64_t n, uint64_t *
 gtars_status gtars_debug_seg_max(const uint32_t *seg, const uint32_t *val, const uint32_t *start, uint64_t n, uint32_t gap,
                                  int inclusive, uint32_t *out);
 
+/* Test hooks of the signal summary (csrc/signal.hip, K13; tests/test_gpu_signal.py).
+ * gtars_debug_signal_sort_elems: the result columns are sorted in groups of conditions whose rows x conditions stay
+ * at or under `elems` (the device sort takes a 32-bit count); sets it for every later summary of the process and
+ * returns the previous value, 0 puts the default back.  No summary may be in flight.
+ * gtars_debug_signal_split_hits: a query with MORE hits than this is folded by all waves of a workgroup, every wave a
+ * slice of the hits, instead of by one lane group. */
+uint32_t gtars_debug_signal_sort_elems(uint32_t elems);
+uint32_t gtars_debug_signal_split_hits(void);
+
 /* (Stamp builds -- tools/build_variant.sh with -DGTARS_TOK_STAMPS=1 / -DIGD_STAMPS=1 -- additionally export
  * gtars_debug_tok_stamps / gtars_debug_route_stamps / gtars_debug_sweep_stamps: s_memtime at the phase boundaries of the tile
  * loops, read by tools/r03_tok_stamps.py, tools/r03_sweep_stamps.py, tools/r05_rank_stamps.py.  The shipped library has none.) */

@@ -295,6 +295,76 @@ gtars_status gtars_seqstats_dinucl(gtars_assembly_t *a, const gtars_regionset_t 
                                    uint64_t **row_index, double **freq, uint64_t *n_out);
 
 /* ------------------------------------------------------------------------
+ * Signal matrices and calc_summary_signal  (gtars-genomicdist/src/signal.rs; csrc/signal.cpp, csrc/signal.hip: K13)
+ *
+ * A handle holds a region x condition matrix of f64 on the host -- the rows in file order, never sorted, duplicates
+ * kept -- and reads its files without a device.  Its device image (the row-major values and an AIList-kind overlap
+ * index of the rows with val = row) is built at the first summary call, on the device current then, which the handle
+ * keeps: the host call runs there whatever the caller's current device is, the device-pointer call refuses another one.
+ *
+ * TSV (SignalMatrix::from_tsv, signal.rs:73-164), read through gtars_read_file (".gz" by extension).  A line ends at
+ * '\n', a '\r' in front of it is dropped.  The first line is the header, split on tab: fewer than 2 fields is
+ * GTARS_ERR_PARSE, fields 1.. are the condition names.  Every later line is split on tab; field 0 is split on '_' and
+ * must give exactly three parts (a contig name that contains '_' drops the row, an empty name is a name); parts 1 and 2
+ * parse as u32 by Rust's rule (an optional '+', digits only, overflow fails); fewer than 1 + n_conditions fields skip
+ * the row, extra fields are ignored; every value parses by Rust's f64::from_str (optional sign; decimal digits with an
+ * optional '.' and exponent, "5." and ".5" included, "." not; inf / infinity / nan in any case; no whitespace, no hex;
+ * correctly rounded).  Any failure skips the row silently.  An empty file and a file without a valid row are
+ * GTARS_ERR_PARSE.
+ *
+ * SIGM version 2 (save_bin / load_bin_from_bytes, signal.rs:170-354), little-endian: u32 magic 0x5349474D, u32 version,
+ * u32 n_regions, u32 n_conditions; the string table, u32 n_strings then per string u32 length + bytes; u32 n_names
+ * (== n_conditions) and a u16 string id per condition; a u16 chromosome string id per region, a u32 start per region,
+ * a u32 end per region; n_regions x n_conditions f64, row-major.  Written: the table holds the chromosome names in
+ * order of first appearance, then the condition names it lacks (more than 65536 strings: GTARS_ERR_INVALID_ARG).
+ * Read: wrong magic, another version, truncation anywhere, a name-count mismatch and a string id outside the table are
+ * GTARS_ERR_PARSE; bytes behind the values are ignored.
+ * ---------------------------------------------------------------------- */
+typedef struct gtars_signal gtars_signal_t;
+gtars_status gtars_signal_from_tsv(const char *path, gtars_signal_t **out);
+gtars_status gtars_signal_load_bin(const char *path, gtars_signal_t **out);
+gtars_status gtars_signal_save_bin(const gtars_signal_t *sm, const char *path);
+/* n rows (chrom[i] < n_chrom indexes chrom_names) with values[n * n_conditions], row-major; n and n_conditions >= 1.
+ * The handle's chromosome ids follow the first appearance of a name among the rows. */
+gtars_status gtars_signal_from_arrays(const char *const *chrom_names, uint32_t n_chrom, const uint32_t *chrom,
+                                      const uint32_t *start, const uint32_t *end, uint64_t n, const double *values,
+                                      const char *const *condition_names, uint32_t n_conditions, gtars_signal_t **out);
+void gtars_signal_free(gtars_signal_t *sm);
+uint64_t gtars_signal_n_regions(const gtars_signal_t *sm);
+uint32_t gtars_signal_n_conditions(const gtars_signal_t *sm);
+const char *gtars_signal_condition_name(const gtars_signal_t *sm, uint32_t i);
+/* the rows as dictionary-encoded columns (ids index gtars_signal_chrom_name) and the values, borrowed from the handle */
+uint32_t gtars_signal_n_chrom(const gtars_signal_t *sm);
+const char *gtars_signal_chrom_name(const gtars_signal_t *sm, uint32_t id);
+const uint32_t *gtars_signal_chrom_ids(const gtars_signal_t *sm);
+const uint32_t *gtars_signal_starts(const gtars_signal_t *sm);
+const uint32_t *gtars_signal_ends(const gtars_signal_t *sm);
+const double *gtars_signal_values(const gtars_signal_t *sm);
+int gtars_signal_device(const gtars_signal_t *sm); /* -1 until the first summary call */
+
+/* calc_summary_signal (signal.rs:364-454), Bed labels.  A query overlaps a row when row.start < q.end && row.end >
+ * q.start (zero-length and inverted queries as the overlap index treats them; nothing else is filtered).  Output rows:
+ * the queries with at least one hit, in query order.
+ *   *qidx[*n_rows]                   the query's row in rs (its label is "{chr}_{start}_{end}")
+ *   *values[*n_rows * n_conditions]  per condition the fold of the hit rows' values in AIList result order: the first
+ *                                    hit's value, replaced by every later value that is greater.  So a NaN in the first
+ *                                    hit stays (bits kept), NaNs elsewhere are ignored, ties keep the earlier hit
+ *                                    (0.0 against -0.0).  Bit-exact.
+ *   *stats[n_conditions * 5]         boxplot_stats (signal.rs:461-513) of every result column: lower whisker, lower
+ *                                    hinge, median, upper hinge, upper whisker.  A column that holds a NaN has no
+ *                                    defined result in the reference (its comparator is inconsistent there); here NaNs
+ *                                    sort last.
+ * *n_rows == 0 leaves all three NULL (the reference returns no statistics then).  gtars_free each array.
+ * gtars_signal_summary_device: the queries are n device rows, d_chrom the matrix's chromosome ids (any other value: no
+ * hits), queued on `stream` (a hipStream_t) of the current device, which is drained on the way and before the call
+ * returns.  qidx and values may both be NULL: the rows then stay on the device and only the statistics come back. */
+gtars_status gtars_signal_summary(gtars_signal_t *sm, const gtars_regionset_t *rs, uint32_t **qidx, double **values,
+                                  double **stats, uint64_t *n_rows);
+gtars_status gtars_signal_summary_device(gtars_signal_t *sm, const uint32_t *d_chrom, const uint32_t *d_start,
+                                         const uint32_t *d_end, uint64_t n, void *stream, uint32_t **qidx, double **values,
+                                         double **stats, uint64_t *n_rows);
+
+/* ------------------------------------------------------------------------
  * Tokenizer  (gtars-tokenizers/src/tokenizer.rs:36-279, universe/mod.rs,
  * config.rs, utils/mod.rs:34-99, utils/special_tokens.rs)
  * ---------------------------------------------------------------------- */
