@@ -17,6 +17,7 @@
 #include <unordered_map>
 
 #include "common.h"
+#include "pipeline.h"
 #include "../../include/gtars_amd_debug.h"
 
 namespace gtars {
@@ -282,15 +283,16 @@ static gtars_status sorted_perm_device(const std::vector<u32> &chrom, const std:
     const u32 n = (u32)chrom.size();
     perm.resize(n);
     if (!n) return GTARS_OK;
-    DevBuf<u32> buf;
-    GT_TRY(buf.alloc((size_t)n * 4));
-    u32 *dc = buf.p, *d1 = dc + n, *d2 = d1 + n, *dp = d2 + n;
-    GT_HIP(hipMemcpy(dc, chrom.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    GT_HIP(hipMemcpy(d1, k1.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    if (k2) GT_HIP(hipMemcpy(d2, k2->data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    GT_TRY(device_sort_perm(dc, d1, k2 ? d2 : nullptr, n, n_chrom, dp, nullptr));
-    GT_HIP(hipMemcpy(perm.data(), dp, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GTARS_OK;
+    StreamFrame fr(nullptr);
+    u32 *dc;
+    GT_TRY(fr.alloc(&dc, (size_t)n * 4));
+    u32 *d1 = dc + n, *d2 = d1 + n, *dp = d2 + n;
+    GT_TRY(fr.upload_to(dc, chrom.data(), n));
+    GT_TRY(fr.upload_to(d1, k1.data(), n));
+    if (k2) GT_TRY(fr.upload_to(d2, k2->data(), n));
+    GT_TRY(device_sort_perm(dc, d1, k2 ? d2 : nullptr, n, n_chrom, dp, fr.st));
+    GT_TRY(fr.download(perm.data(), dp, n));
+    return fr.drain();
 }
 
 // ================================================================== handles
@@ -705,9 +707,10 @@ int gtars_prof_read(const char **names, double *total_ms, uint64_t *launches, in
 
 // ------------------------------------------------------------- index build
 
-static gtars_status gtars_index_build_impl(const uint32_t *chrom, const uint32_t *start, const uint32_t *end,
-                               const uint32_t *val, uint64_t n, uint32_t n_chrom, int kind,
-                               gtars_index_t **out) {
+// (the builder behind gtars_index_build and gtars_index_insert; it also calls itself, for the flat companion of a nested
+// AIList index)
+static gtars_status build_index(const uint32_t *chrom, const uint32_t *start, const uint32_t *end, const uint32_t *val,
+                                uint64_t n, uint32_t n_chrom, int kind, gtars_index_t **out) {
     if (!out) return fail(GTARS_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (kind != GTARS_KIND_BITS && kind != GTARS_KIND_AILIST)
@@ -1060,7 +1063,7 @@ static gtars_status gtars_index_build_impl(const uint32_t *chrom, const uint32_t
         // nested sub-lists: the flat companion (see gtars_index::flat) -- optional: an index without it answers every call on
         // the generic kernels, as before
         gtars_index *built = nullptr;
-        (void)gtars_index_build_impl(chrom, start, end, val, n, n_chrom, GTARS_KIND_BITS, &built);  // (*out stays null on failure)
+        (void)build_index(chrom, start, end, val, n, n_chrom, GTARS_KIND_BITS, &built);  // (*out stays null on failure)
         std::unique_ptr<gtars_index> fl(built);
         if (fl && fl->has_accel && tokenize_lds_supported(fl->accel())) {
             std::vector<u32> inv(n), map(n);
@@ -1106,6 +1109,11 @@ static gtars_status gtars_index_build_impl(const uint32_t *chrom, const uint32_t
     return GTARS_OK;
 }
 
+gtars_status gtars_index_build(const uint32_t *chrom, const uint32_t *start, const uint32_t *end, const uint32_t *val, uint64_t n,
+                               uint32_t n_chrom, int kind, gtars_index_t **out) {
+    return guarded([&]() -> gtars_status { return build_index(chrom, start, end, val, n, n_chrom, kind, out); });
+}
+
 void gtars_index_free(gtars_index_t *ix) { delete ix; }
 
 uint64_t gtars_index_len(const gtars_index_t *ix) { return ix ? ix->n : 0; }
@@ -1120,16 +1128,17 @@ uint64_t gtars_index_chrom_len(const gtars_index_t *ix, uint32_t c) {
 
 gtars_status gtars_index_stored(const gtars_index_t *ix, uint32_t c, uint32_t *start, uint32_t *end,
                                 uint32_t *val) {
-    if (!ix) return fail(GTARS_ERR_INVALID_ARG, "NULL index");
-    if (c >= ix->n_chrom) return GTARS_OK;
-    const u32 lo = ix->h_chrom_off[c], hi = ix->h_chrom_off[c + 1];
-    // read back from the device so that tests see what the kernels see
-    if (hi > lo) {
-        if (start) GT_HIP(hipMemcpy(start, ix->starts.p + lo, (hi - lo) * 4, hipMemcpyDeviceToHost));
-        if (end) GT_HIP(hipMemcpy(end, ix->ends.p + lo, (hi - lo) * 4, hipMemcpyDeviceToHost));
-        if (val) GT_HIP(hipMemcpy(val, ix->vals.p + lo, (hi - lo) * 4, hipMemcpyDeviceToHost));
-    }
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        if (!ix) return fail(GTARS_ERR_INVALID_ARG, "NULL index");
+        if (c >= ix->n_chrom) return GTARS_OK;
+        const u32 lo = ix->h_chrom_off[c], hi = ix->h_chrom_off[c + 1];
+        // read back from the device so that tests see what the kernels see
+        StreamFrame fr(nullptr);
+        if (start) GT_TRY(fr.download(start, ix->starts.p + lo, hi - lo));
+        if (end) GT_TRY(fr.download(end, ix->ends.p + lo, hi - lo));
+        if (val) GT_TRY(fr.download(val, ix->vals.p + lo, hi - lo));
+        return fr.drain();
+    });
 }
 
 uint32_t gtars_index_max_len(const gtars_index_t *ix, uint32_t c) {
@@ -1359,88 +1368,103 @@ gtars_status gtars_count_overlaps_device(const gtars_index_t *ix, const uint32_t
 
 // host-pointer helpers -------------------------------------------------------
 
-struct DevQueries {
-    DevBuf<u8> buf;
-    u32 *c = nullptr, *s = nullptr, *e = nullptr;
-    gtars_status upload(const u32 *qc, const u32 *qs, const u32 *qe, u64 nq) {
-        const size_t pad = ((size_t)nq * 4 + 255) & ~(size_t)255;
-        GT_TRY(buf.alloc(pad * 3));
-        c = (u32 *)buf.p;
-        s = (u32 *)(buf.p + pad);
-        e = (u32 *)(buf.p + 2 * pad);
-        if (nq) {
-            GT_HIP(hipMemcpy(c, qc, nq * 4, hipMemcpyHostToDevice));
-            GT_HIP(hipMemcpy(s, qs, nq * 4, hipMemcpyHostToDevice));
-            GT_HIP(hipMemcpy(e, qe, nq * 4, hipMemcpyHostToDevice));
-        }
-        return GTARS_OK;
-    }
-};
+// Every host-pointer entry point of the engine is one StreamFrame on the null stream (the stream tls_workspace keys these calls
+// on): the frame owns the call's device memory, the copies are queued on it and drain() is the call's synchronisation.  Host
+// memory that a queued copy writes is declared BEFORE the frame, so the frame has drained the stream when that memory goes away.
 
-template <class T>
-static T *host_alloc(u64 n) {
-    return (T *)malloc(std::max<u64>(n, 1) * sizeof(T));
+// the three query columns in ONE allocation of the frame, every column on a 256-byte boundary (kernels load them as 16-byte vectors)
+static gtars_status upload_queries(StreamFrame &fr, const u32 *qc, const u32 *qs, const u32 *qe, u64 nq, u32 **dc, u32 **ds,
+                                   u32 **de) {
+    const size_t pad = ((size_t)nq * 4 + 255) & ~(size_t)255;
+    u8 *buf;
+    GT_TRY(fr.alloc(&buf, pad * 3));
+    *dc = (u32 *)buf, *ds = (u32 *)(buf + pad), *de = (u32 *)(buf + 2 * pad);
+    GT_TRY(fr.upload_to(*dc, qc, nq));
+    GT_TRY(fr.upload_to(*ds, qs, nq));
+    return fr.upload_to(*de, qe, nq);
 }
 
-// fused enumerate into library-allocated host arrays
+// A result array the library allocates for its caller (who frees it with gtars_free): max(n, 1) elements from malloc, freed with
+// this object unless release() has handed it on.  A call releases in ONE place, on its success path behind its last drain(): on
+// every other way out the caller's out pointers are still null and nothing stays allocated.
+namespace {
+template <class T>
+struct HostOut {
+    T *p = nullptr;
+    HostOut() = default;
+    HostOut(const HostOut &) = delete;
+    HostOut &operator=(const HostOut &) = delete;
+    ~HostOut() { free(p); }
+    gtars_status alloc(u64 n) {
+        free(p);
+        p = (T *)malloc(std::max<u64>(n, 1) * sizeof(T));
+        return p ? GTARS_OK : fail(GTARS_ERR_INTERNAL, "out of host memory");
+    }
+    // a fresh array of n elements and, queued on the frame, the copy of d[0 .. n) into it
+    gtars_status download(StreamFrame &fr, const T *d, u64 n) {
+        GT_TRY(alloc(n));
+        return fr.download(p, d, n);
+    }
+    T *release() {
+        T *r = p;
+        p = nullptr;
+        return r;
+    }
+};
+}  // namespace
+
+// fused enumerate into library-allocated host arrays (any of out_val / out_start / out_end / out_n / offsets may be null)
 static gtars_status enumerate_to_host(const gtars_index_t *ix, const u32 *qc, const u32 *qs, const u32 *qe,
                                       u64 nq, int has_min, i32 min_overlap, u64 *offsets, u32 **out_val,
                                       u32 **out_start, u32 **out_end, u64 *out_n) {
-    gtars_status st = require_device();
-    if (st) return st;
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u64> d_off;
-    DevBuf<u8> d_ws;
-    GT_TRY(d_off.alloc(nq + 1));
+    if (out_val) *out_val = nullptr;
+    if (out_start) *out_start = nullptr;
+    if (out_end) *out_end = nullptr;
+    if (out_n) *out_n = 0;
+    GT_TRY(require_device());
+    HostOut<u32> h_val, h_start, h_end;
+    StreamFrame fr(nullptr);
+    u32 *dc, *ds, *de;
+    GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+    u64 *d_off;
+    u8 *d_ws;
+    GT_TRY(fr.alloc(&d_off, nq + 1));
     const size_t wsb = fused_ws_bytes(ix, nq);
-    GT_TRY(d_ws.alloc(wsb));
+    GT_TRY(fr.alloc(&d_ws, wsb));
     // pass 1: offsets + total only (no payload buffers)
-    EnumOut o1{d_off.p, nullptr, nullptr, nullptr, 0};
+    EnumOut o1{d_off, nullptr, nullptr, nullptr, 0};
     ScanEpoch ep;
     u64 h = 0;
-    st = run_fused_sync(ix, q.c, q.s, q.e, nq, has_min, min_overlap, o1, d_ws.p, wsb, ep, nullptr, &h);
-    if (st) return st;
-    if (offsets) GT_HIP(hipMemcpy(offsets, d_off.p, (nq + 1) * 8, hipMemcpyDeviceToHost));
-    if (out_n) *out_n = h;
-    const int nout = (out_val ? 1 : 0) + (out_start ? 1 : 0) + (out_end ? 1 : 0);
-    if (nout) {
-        DevBuf<u8> d_out;
+    GT_TRY(run_fused_sync(ix, dc, ds, de, nq, has_min, min_overlap, o1, d_ws, wsb, ep, fr.st, &h));
+    if (offsets) GT_TRY(fr.download(offsets, d_off, nq + 1));
+    if (out_val || out_start || out_end) {
+        u8 *d_out;
         const size_t pad = ((size_t)h * 4 + 255) & ~(size_t)255;
-        GT_TRY(d_out.alloc(pad * 3));
-        u32 *dv = out_val ? (u32 *)d_out.p : nullptr;
-        u32 *ds = out_start ? (u32 *)(d_out.p + pad) : nullptr;
-        u32 *de = out_end ? (u32 *)(d_out.p + 2 * pad) : nullptr;
+        GT_TRY(fr.alloc(&d_out, pad * 3));
+        u32 *dv = out_val ? (u32 *)d_out : nullptr;
+        u32 *dst = out_start ? (u32 *)(d_out + pad) : nullptr;
+        u32 *den = out_end ? (u32 *)(d_out + 2 * pad) : nullptr;
         if (use_lds_path(ix)) {
             // the fused tokenizer once more, this time emitting the hits' stored positions (reference order, Bits or
             // AIList), and one gather of the payload columns by position -- instead of the generic per-query fill pass
-            DevBuf<u32> d_pos;
-            GT_TRY(d_pos.alloc(pad / 4));
-            EnumOut o2{d_off.p, d_pos.p, nullptr, nullptr, h};
-            st = launch_tokenize_lds(ix->accel_pos(), q.c, q.s, q.e, nq, has_min, min_overlap, o2, d_ws.p, wsb, ep, nullptr, nullptr,
-                                     nullptr, ix->kind == GTARS_KIND_AILIST);
-            if (st) return st;
-            st = launch_gather_hits(ix->view(), d_pos.p, h, dv, ds, de, nullptr);
-            if (st) return st;
-            GT_HIP(hipDeviceSynchronize());
+            u32 *d_pos;
+            GT_TRY(fr.alloc(&d_pos, pad / 4));
+            EnumOut o2{d_off, d_pos, nullptr, nullptr, h};
+            GT_TRY(launch_tokenize_lds(ix->accel_pos(), dc, ds, de, nq, has_min, min_overlap, o2, d_ws, wsb, ep, fr.st, nullptr, nullptr,
+                                       ix->kind == GTARS_KIND_AILIST));
+            GT_TRY(launch_gather_hits(ix->view(), d_pos, h, dv, dst, den, fr.st));
         } else {
-            st = launch_fill(ix->view(), ix->kind, q.c, q.s, q.e, nq, has_min, min_overlap, d_off.p, dv, ds,
-                             de, nullptr);
-            if (st) return st;
-            GT_HIP(hipDeviceSynchronize());
+            GT_TRY(launch_fill(ix->view(), ix->kind, dc, ds, de, nq, has_min, min_overlap, d_off, dv, dst, den, fr.st));
         }
-        auto fetch = [&](u32 **dst, u32 *src) -> gtars_status {
-            if (!dst) return GTARS_OK;
-            *dst = host_alloc<u32>(h);
-            if (!*dst) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-            if (h) GT_HIP(hipMemcpy(*dst, src, h * 4, hipMemcpyDeviceToHost));
-            return GTARS_OK;
-        };
-        if ((st = fetch(out_val, dv))) return st;
-        if ((st = fetch(out_start, ds))) return st;
-        if ((st = fetch(out_end, de))) return st;
+        if (out_val) GT_TRY(h_val.download(fr, dv, h));
+        if (out_start) GT_TRY(h_start.download(fr, dst, h));
+        if (out_end) GT_TRY(h_end.download(fr, den, h));
     }
+    GT_TRY(fr.drain());
+    if (out_val) *out_val = h_val.release();
+    if (out_start) *out_start = h_start.release();
+    if (out_end) *out_end = h_end.release();
+    if (out_n) *out_n = h;
     return GTARS_OK;
 }
 
@@ -1747,73 +1771,66 @@ static gtars_status tokenize_pipeline(const gtars_index_t *ix, const u32 *qc, co
 
 extern "C" {
 
-static gtars_status gtars_tokenize_into_impl(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
+gtars_status gtars_tokenize_into(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
                                  uint64_t nq, uint64_t *offsets, uint32_t *ids, uint64_t ids_capacity, uint64_t *out_n) {
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (!offsets || !out_n || (ids_capacity && !ids)) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
-    *out_n = 0;
-    st = require_device();
-    if (st) return st;
-    return tokenize_pipeline(ix, qc, qs, qe, nq, offsets, ids_capacity ? ids : nullptr, ids_capacity, out_n);
+    return guarded([&]() -> gtars_status {
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (!offsets || !out_n || (ids_capacity && !ids)) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        *out_n = 0;
+        GT_TRY(require_device());
+        return tokenize_pipeline(ix, qc, qs, qe, nq, offsets, ids_capacity ? ids : nullptr, ids_capacity, out_n);
+    });
 }
 
-static gtars_status gtars_tokenize_impl(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
+gtars_status gtars_tokenize(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
                             const uint32_t *qe, uint64_t nq, uint64_t *offsets, uint32_t **out_ids,
                             uint64_t *out_n) {
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (!out_ids || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
-    *out_ids = nullptr;
-    *out_n = 0;
-    st = require_device();
-    if (st) return st;
-    // the streaming pipeline with a guessed capacity; a second (ids only) pass on overflow
-    u64 cap = nq * 2 + 1024, total = 0;
-    u32 *ids = host_alloc<u32>(cap);
-    if (!ids) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    std::vector<u64> tmp_off;
-    u64 *off = offsets;
-    if (!off) {
-        tmp_off.resize(nq + 1);
-        off = tmp_off.data();
-    }
-    st = tokenize_pipeline(ix, qc, qs, qe, nq, off, ids, cap, &total);
-    if (st == GTARS_ERR_CAPACITY) {
-        free(ids);
-        cap = total;
-        ids = host_alloc<u32>(cap);
-        if (!ids) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-        st = tokenize_pipeline(ix, qc, qs, qe, nq, off, ids, cap, &total);
-    }
-    if (st) {
-        free(ids);
-        return st;
-    }
-    *out_ids = ids;
-    *out_n = total;
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (!out_ids || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        *out_ids = nullptr;
+        *out_n = 0;
+        GT_TRY(require_device());
+        // the streaming pipeline with a guessed capacity; a second (ids only) pass on overflow
+        u64 cap = nq * 2 + 1024, total = 0;
+        HostOut<u32> ids;
+        GT_TRY(ids.alloc(cap));
+        std::vector<u64> tmp_off;
+        u64 *off = offsets;
+        if (!off) {
+            tmp_off.resize(nq + 1);
+            off = tmp_off.data();
+        }
+        gtars_status st = tokenize_pipeline(ix, qc, qs, qe, nq, off, ids.p, cap, &total);
+        if (st == GTARS_ERR_CAPACITY) {
+            cap = total;
+            GT_TRY(ids.alloc(cap));
+            st = tokenize_pipeline(ix, qc, qs, qe, nq, off, ids.p, cap, &total);
+        }
+        if (st) return st;
+        *out_ids = ids.release();
+        *out_n = total;
+        return GTARS_OK;
+    });
 }
 
 gtars_status gtars_count_overlaps(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
                                   const uint32_t *qe, uint64_t nq, int has_min, int32_t min_overlap,
                                   uint32_t *counts) {
-    GT_ON_DEVICE_OF(ix);
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (nq && !counts) return fail(GTARS_ERR_INVALID_ARG, "counts is NULL");
-    st = require_device();
-    if (st) return st;
-    if (!nq) return GTARS_OK;
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u32> d;
-    GT_TRY(d.alloc(nq));
-    st = count_dispatch(ix, q.c, q.s, q.e, nq, has_min, min_overlap, d.p, nullptr, nullptr);
-    if (st) return st;
-    GT_HIP(hipMemcpy(counts, d.p, nq * 4, hipMemcpyDeviceToHost));
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (nq && !counts) return fail(GTARS_ERR_INVALID_ARG, "counts is NULL");
+        GT_TRY(require_device());
+        if (!nq) return GTARS_OK;
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de, *d;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d, nq));
+        GT_TRY(count_dispatch(ix, dc, ds, de, nq, has_min, min_overlap, d, nullptr, fr.st));
+        GT_TRY(fr.download(counts, d, nq));
+        return fr.drain();
+    });
 }
 
 static gtars_status bits_count_prepare(const gtars_index_t *ix) {
@@ -1842,121 +1859,113 @@ gtars_status gtars_bits_count_device(const gtars_index_t *ix, const uint32_t *d_
 
 gtars_status gtars_bits_count(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
                               uint64_t nq, uint64_t *counts) {
-    GT_ON_DEVICE_OF(ix);
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (nq && !counts) return fail(GTARS_ERR_INVALID_ARG, "counts is NULL");
-    st = require_device();
-    if (st) return st;
-    if ((st = bits_count_prepare(ix))) return st;
-    if (!nq) return GTARS_OK;
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u64> d;
-    GT_TRY(d.alloc(nq));
-    st = launch_bits_count(ix->view(), ix->ends_sorted.p, q.c, q.s, q.e, nq, d.p, nullptr);
-    if (st) return st;
-    GT_HIP(hipMemcpy(counts, d.p, nq * 8, hipMemcpyDeviceToHost));
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (nq && !counts) return fail(GTARS_ERR_INVALID_ARG, "counts is NULL");
+        GT_TRY(require_device());
+        GT_TRY(bits_count_prepare(ix));
+        if (!nq) return GTARS_OK;
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de;
+        u64 *d;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d, nq));
+        GT_TRY(launch_bits_count(ix->view(), ix->ends_sorted.p, dc, ds, de, nq, d, fr.st));
+        GT_TRY(fr.download(counts, d, nq));
+        return fr.drain();
+    });
 }
 
 gtars_status gtars_any_overlaps(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
                                 const uint32_t *qe, uint64_t nq, int has_min, int32_t min_overlap,
                                 uint8_t *out) {
-    GT_ON_DEVICE_OF(ix);
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (nq && !out) return fail(GTARS_ERR_INVALID_ARG, "out is NULL");
-    st = require_device();
-    if (st) return st;
-    if (!nq) return GTARS_OK;
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u8> d;
-    GT_TRY(d.alloc(nq));
-    st = count_dispatch(ix, q.c, q.s, q.e, nq, has_min, min_overlap, nullptr, d.p, nullptr);
-    if (st) return st;
-    GT_HIP(hipMemcpy(out, d.p, nq, hipMemcpyDeviceToHost));
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (nq && !out) return fail(GTARS_ERR_INVALID_ARG, "out is NULL");
+        GT_TRY(require_device());
+        if (!nq) return GTARS_OK;
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de;
+        u8 *d;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d, nq));
+        GT_TRY(count_dispatch(ix, dc, ds, de, nq, has_min, min_overlap, nullptr, d, fr.st));
+        GT_TRY(fr.download(out, d, nq));
+        return fr.drain();
+    });
 }
 
 gtars_status gtars_find_overlaps(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
                                  const uint32_t *qe, uint64_t nq, int has_min, int32_t min_overlap,
                                  uint64_t *offsets, uint32_t **out_start, uint32_t **out_end,
                                  uint32_t **out_val, uint64_t *out_n) {
-    GT_ON_DEVICE_OF(ix);
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (out_start) *out_start = nullptr;
-    if (out_end) *out_end = nullptr;
-    if (out_val) *out_val = nullptr;
-    return enumerate_to_host(ix, qc, qs, qe, nq, has_min, min_overlap, offsets, out_val, out_start, out_end,
-                             out_n);
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        return enumerate_to_host(ix, qc, qs, qe, nq, has_min, min_overlap, offsets, out_val, out_start, out_end, out_n);
+    });
 }
 
 gtars_status gtars_find_overlap_indices(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
                                         const uint32_t *qe, uint64_t nq, int has_min, int32_t min_overlap,
                                         uint64_t *offsets, uint32_t **out_idx, uint64_t *out_n) {
-    GT_ON_DEVICE_OF(ix);
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (!out_idx || !out_n || !offsets) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
-    *out_idx = nullptr;
-    *out_n = 0;
-    st = require_device();
-    if (st) return st;
-    if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (sorted unique source rows: the same from either order)
-    // Every source row that shares a hit's coordinates is itself a hit (same
-    // overlap, same filter), so "all rows sharing coordinates, sorted, dedup"
-    // (indexed_region_set.rs:246-263) == the hit source indices, sorted.
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u64> d_off, d_off2;
-    DevBuf<u32> d_cnt;
-    DevBuf<u8> d_ws;
-    GT_TRY(d_off.alloc(nq + 1));
-    GT_TRY(d_off2.alloc(nq + 1));
-    GT_TRY(d_cnt.alloc(nq));
-    const size_t wsb = std::max(fused_ws_bytes(ix, nq), scan_ws_bytes(nq));
-    GT_TRY(d_ws.alloc(wsb));
-    EnumOut o1{d_off.p, nullptr, nullptr, nullptr, 0};
-    ScanEpoch ep;
-    u64 h = 0;
-    st = run_fused_sync(ix, q.c, q.s, q.e, nq, has_min, min_overlap, o1, d_ws.p, wsb, ep, nullptr, &h);
-    if (st) return st;
-    DevBuf<u32> d_val;
-    GT_TRY(d_val.alloc(h));
-    if (use_lds_path(ix)) {  // the fused tokenizer writes the source indices itself (the order inside a query does not matter here)
-        EnumOut o2{d_off.p, d_val.p, nullptr, nullptr, h};
-        st = launch_tokenize_lds(ix->accel(), q.c, q.s, q.e, nq, has_min, min_overlap, o2, d_ws.p, wsb, ep, nullptr, nullptr, nullptr,
-                                 ix->kind == GTARS_KIND_AILIST);
-    } else {
-        st = launch_fill(ix->view(), ix->kind, q.c, q.s, q.e, nq, has_min, min_overlap, d_off.p, d_val.p, nullptr, nullptr, nullptr);
-    }
-    if (st) return st;
-    GT_TRY(launch_sort_unique_segments(d_val.p, d_off.p, nq, d_cnt.p, nullptr));
-    GT_TRY(launch_scan_u32_to_u64(d_cnt.p, nq, d_off2.p, d_ws.p, wsb, nullptr));
-    // compact on the host side of the copy: segments are already contiguous
-    // when nothing was de-duplicated (the overwhelmingly common case)
-    std::vector<u64> off1(nq + 1), off2(nq + 1);
-    GT_HIP(hipMemcpy(off1.data(), d_off.p, (nq + 1) * 8, hipMemcpyDeviceToHost));
-    GT_HIP(hipMemcpy(off2.data(), d_off2.p, (nq + 1) * 8, hipMemcpyDeviceToHost));
-    std::vector<u32> vals(h);
-    if (h) GT_HIP(hipMemcpy(vals.data(), d_val.p, h * 4, hipMemcpyDeviceToHost));
-    const u64 h2 = off2[nq];
-    u32 *res = host_alloc<u32>(h2);
-    if (!res) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    for (u64 qi = 0; qi < nq; ++qi) {
-        const u64 len = off2[qi + 1] - off2[qi];
-        if (len) memcpy(res + off2[qi], vals.data() + off1[qi], len * 4);
-    }
-    memcpy(offsets, off2.data(), (nq + 1) * 8);
-    *out_idx = res;
-    *out_n = h2;
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (!out_idx || !out_n || !offsets) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        *out_idx = nullptr;
+        *out_n = 0;
+        GT_TRY(require_device());
+        if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (sorted unique source rows: the same from either order)
+        // Every source row that shares a hit's coordinates is itself a hit (same
+        // overlap, same filter), so "all rows sharing coordinates, sorted, dedup"
+        // (indexed_region_set.rs:246-263) == the hit source indices, sorted.
+        std::vector<u64> off1, off2;
+        std::vector<u32> vals;
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de, *d_cnt, *d_val;
+        u64 *d_off, *d_off2;
+        u8 *d_ws;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d_off, nq + 1));
+        GT_TRY(fr.alloc(&d_off2, nq + 1));
+        GT_TRY(fr.alloc(&d_cnt, nq));
+        const size_t wsb = std::max(fused_ws_bytes(ix, nq), scan_ws_bytes(nq));
+        GT_TRY(fr.alloc(&d_ws, wsb));
+        EnumOut o1{d_off, nullptr, nullptr, nullptr, 0};
+        ScanEpoch ep;
+        u64 h = 0;
+        GT_TRY(run_fused_sync(ix, dc, ds, de, nq, has_min, min_overlap, o1, d_ws, wsb, ep, fr.st, &h));
+        GT_TRY(fr.alloc(&d_val, h));
+        if (use_lds_path(ix)) {  // the fused tokenizer writes the source indices itself (the order inside a query does not matter here)
+            EnumOut o2{d_off, d_val, nullptr, nullptr, h};
+            GT_TRY(launch_tokenize_lds(ix->accel(), dc, ds, de, nq, has_min, min_overlap, o2, d_ws, wsb, ep, fr.st, nullptr, nullptr,
+                                       ix->kind == GTARS_KIND_AILIST));
+        } else {
+            GT_TRY(launch_fill(ix->view(), ix->kind, dc, ds, de, nq, has_min, min_overlap, d_off, d_val, nullptr, nullptr, fr.st));
+        }
+        GT_TRY(launch_sort_unique_segments(d_val, d_off, nq, d_cnt, fr.st));
+        GT_TRY(launch_scan_u32_to_u64(d_cnt, nq, d_off2, d_ws, wsb, fr.st));
+        // compact on the host side of the copy: segments are already contiguous
+        // when nothing was de-duplicated (the overwhelmingly common case)
+        GT_TRY(fr.download(off1, d_off, nq + 1));
+        GT_TRY(fr.download(off2, d_off2, nq + 1));
+        GT_TRY(fr.download(vals, d_val, h));
+        GT_TRY(fr.drain());
+        const u64 h2 = off2[nq];
+        HostOut<u32> res;
+        GT_TRY(res.alloc(h2));
+        for (u64 qi = 0; qi < nq; ++qi) {
+            const u64 len = off2[qi + 1] - off2[qi];
+            if (len) memcpy(res.p + off2[qi], vals.data() + off1[qi], len * 4);
+        }
+        memcpy(offsets, off2.data(), (nq + 1) * 8);
+        *out_idx = res.release();
+        *out_n = h2;
+        return GTARS_OK;
+    });
 }
 
 // ---- index-side subset (multi_chrom_overlapper.rs:449-478, indexed_region_set.rs:201-230) ----------------------
@@ -1991,16 +2000,15 @@ static gtars_status subset_positions(const gtars_index_t *ix, const u32 *qc, con
                                      i32 min_overlap, std::vector<u32> &pos) {
     pos.clear();
     if (!nq || !ix->n) return GTARS_OK;
-    DevQueries q;
-    gtars_status st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
     const size_t words = ((size_t)ix->n + 31) / 32;
-    DevBuf<u32> d_mark;
-    GT_TRY(d_mark.alloc(words));
-    st = gtars_mark_overlapped_device(ix, q.c, q.s, q.e, nq, has_min, min_overlap, d_mark.p, nullptr);
-    if (st) return st;
-    std::vector<u32> mark(words);
-    GT_HIP(hipMemcpy(mark.data(), d_mark.p, words * 4, hipMemcpyDeviceToHost));
+    std::vector<u32> mark;
+    StreamFrame fr(nullptr);
+    u32 *dc, *ds, *de, *d_mark;
+    GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+    GT_TRY(fr.alloc(&d_mark, words));
+    GT_TRY(gtars_mark_overlapped_device(ix, dc, ds, de, nq, has_min, min_overlap, d_mark, fr.st));
+    GT_TRY(fr.download(mark, d_mark, words));
+    GT_TRY(fr.drain());
     for (size_t w = 0; w < words; ++w) {
         u32 m = mark[w];
         while (m) {
@@ -2013,121 +2021,96 @@ static gtars_status subset_positions(const gtars_index_t *ix, const u32 *qc, con
 
 extern "C" {
 
-static gtars_status gtars_subset_by_overlaps_impl(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
-                                                  uint64_t nq, int has_min, int32_t min_overlap, uint32_t **out_chrom,
-                                                  uint32_t **out_start, uint32_t **out_end, uint64_t *out_n) {
-    GT_ON_DEVICE_OF(ix);
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (!out_chrom || !out_start || !out_end || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
-    *out_chrom = *out_start = *out_end = nullptr;
-    *out_n = 0;
-    if ((st = require_device())) return st;
-    struct Trip {
-        u32 c, s, e;
-        bool operator<(const Trip &o) const { return std::tie(c, s, e) < std::tie(o.c, o.s, o.e); }
-        bool operator==(const Trip &o) const { return c == o.c && s == o.s && e == o.e; }
-    };
-    std::vector<Trip> hits;
-    if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (a set of coordinates: the same from either stored order)
-    if (use_lds_path(ix)) {
-        std::vector<u32> pos;
-        if ((st = subset_positions(ix, qc, qs, qe, nq, has_min, min_overlap, pos))) return st;
-        hits.reserve(pos.size());
-        u32 c = 0;
-        for (u32 p : pos) {  // positions ascend: so do their chromosomes
-            while (c + 1 < ix->h_chrom_off.size() && p >= ix->h_chrom_off[c + 1]) ++c;
-            hits.push_back(Trip{c, ix->h_starts[p], ix->h_ends[p]});
-        }
-    } else {
-        // generic kernels: the hits' coordinates per query (find_overlaps_regions), the set is formed here
-        std::vector<u64> off(nq + 1);
-        u32 *hs = nullptr, *he = nullptr;
-        u64 h = 0;
-        st = enumerate_to_host(ix, qc, qs, qe, nq, has_min, min_overlap, off.data(), nullptr, &hs, &he, &h);
-        if (st) {
-            free(hs);
-            free(he);
-            return st;
-        }
-        hits.reserve(h);
-        for (u64 qi = 0; qi < nq; ++qi)
-            for (u64 k = off[qi]; k < off[qi + 1]; ++k) hits.push_back(Trip{qc[qi], hs[k], he[k]});
-        free(hs);
-        free(he);
-    }
-    // BTreeSet<(chr, start, end)>: sorted, de-duplicated (Bits positions are already in this order; AIList's are not)
-    if (!std::is_sorted(hits.begin(), hits.end())) std::sort(hits.begin(), hits.end());
-    hits.erase(std::unique(hits.begin(), hits.end()), hits.end());
-    const u64 n = hits.size();
-    u32 *oc = host_alloc<u32>(n), *os = host_alloc<u32>(n), *oe = host_alloc<u32>(n);
-    if (!oc || !os || !oe) {
-        free(oc);
-        free(os);
-        free(oe);
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    }
-    for (u64 i = 0; i < n; ++i) {
-        oc[i] = hits[i].c;
-        os[i] = hits[i].s;
-        oe[i] = hits[i].e;
-    }
-    *out_chrom = oc;
-    *out_start = os;
-    *out_end = oe;
-    *out_n = n;
-    return GTARS_OK;
-}
-
 gtars_status gtars_subset_by_overlaps(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe, uint64_t nq,
                                       int has_min, int32_t min_overlap, uint32_t **out_chrom, uint32_t **out_start,
                                       uint32_t **out_end, uint64_t *out_n) {
-    return guarded([&] { return gtars_subset_by_overlaps_impl(ix, qc, qs, qe, nq, has_min, min_overlap, out_chrom, out_start, out_end, out_n); });
-}
-
-static gtars_status gtars_subset_source_indices_impl(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
-                                                     const uint32_t *qe, uint64_t nq, int has_min, int32_t min_overlap,
-                                                     uint32_t **out_idx, uint64_t *out_n) {
-    GT_ON_DEVICE_OF(ix);
-    gtars_status st = check_query_args(ix, qc, qs, qe, nq);
-    if (st) return st;
-    if (!out_idx || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
-    *out_idx = nullptr;
-    *out_n = 0;
-    if ((st = require_device())) return st;
-    std::vector<u32> vals;
-    if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (a set of source rows: the same from either stored order)
-    if (use_lds_path(ix)) {
-        std::vector<u32> pos;
-        if ((st = subset_positions(ix, qc, qs, qe, nq, has_min, min_overlap, pos))) return st;
-        vals.reserve(pos.size());
-        for (u32 p : pos) vals.push_back(ix->h_vals[p]);
-    } else {
-        std::vector<u64> off(nq + 1);
-        u32 *hv = nullptr;
-        u64 h = 0;
-        st = enumerate_to_host(ix, qc, qs, qe, nq, has_min, min_overlap, off.data(), &hv, nullptr, nullptr, &h);
-        if (st) {
-            free(hv);
-            return st;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (!out_chrom || !out_start || !out_end || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        *out_chrom = *out_start = *out_end = nullptr;
+        *out_n = 0;
+        GT_TRY(require_device());
+        struct Trip {
+            u32 c, s, e;
+            bool operator<(const Trip &o) const { return std::tie(c, s, e) < std::tie(o.c, o.s, o.e); }
+            bool operator==(const Trip &o) const { return c == o.c && s == o.s && e == o.e; }
+        };
+        std::vector<Trip> hits;
+        if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (a set of coordinates: the same from either stored order)
+        if (use_lds_path(ix)) {
+            std::vector<u32> pos;
+            GT_TRY(subset_positions(ix, qc, qs, qe, nq, has_min, min_overlap, pos));
+            hits.reserve(pos.size());
+            u32 c = 0;
+            for (u32 p : pos) {  // positions ascend: so do their chromosomes
+                while (c + 1 < ix->h_chrom_off.size() && p >= ix->h_chrom_off[c + 1]) ++c;
+                hits.push_back(Trip{c, ix->h_starts[p], ix->h_ends[p]});
+            }
+        } else {
+            // generic kernels: the hits' coordinates per query (find_overlaps_regions), the set is formed here
+            std::vector<u64> off(nq + 1);
+            HostOut<u32> hs, he;
+            u64 h = 0;
+            GT_TRY(enumerate_to_host(ix, qc, qs, qe, nq, has_min, min_overlap, off.data(), nullptr, &hs.p, &he.p, &h));
+            hits.reserve(h);
+            for (u64 qi = 0; qi < nq; ++qi)
+                for (u64 k = off[qi]; k < off[qi + 1]; ++k) hits.push_back(Trip{qc[qi], hs.p[k], he.p[k]});
         }
-        vals.assign(hv, hv + h);
-        free(hv);
-    }
-    // BTreeSet<usize>: ascending, unique
-    std::sort(vals.begin(), vals.end());
-    vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
-    u32 *res = host_alloc<u32>(vals.size());
-    if (!res) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    if (!vals.empty()) memcpy(res, vals.data(), vals.size() * 4);
-    *out_idx = res;
-    *out_n = vals.size();
-    return GTARS_OK;
+        // BTreeSet<(chr, start, end)>: sorted, de-duplicated (Bits positions are already in this order; AIList's are not)
+        if (!std::is_sorted(hits.begin(), hits.end())) std::sort(hits.begin(), hits.end());
+        hits.erase(std::unique(hits.begin(), hits.end()), hits.end());
+        const u64 n = hits.size();
+        HostOut<u32> oc, os, oe;
+        GT_TRY(oc.alloc(n));
+        GT_TRY(os.alloc(n));
+        GT_TRY(oe.alloc(n));
+        for (u64 i = 0; i < n; ++i) {
+            oc.p[i] = hits[i].c;
+            os.p[i] = hits[i].s;
+            oe.p[i] = hits[i].e;
+        }
+        *out_chrom = oc.release();
+        *out_start = os.release();
+        *out_end = oe.release();
+        *out_n = n;
+        return GTARS_OK;
+    });
 }
 
 gtars_status gtars_subset_source_indices(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
                                          uint64_t nq, int has_min, int32_t min_overlap, uint32_t **out_idx, uint64_t *out_n) {
-    return guarded([&] { return gtars_subset_source_indices_impl(ix, qc, qs, qe, nq, has_min, min_overlap, out_idx, out_n); });
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        GT_TRY(check_query_args(ix, qc, qs, qe, nq));
+        if (!out_idx || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        *out_idx = nullptr;
+        *out_n = 0;
+        GT_TRY(require_device());
+        std::vector<u32> vals;
+        if (ix->flat && lds_target(ix) == ix->flat.get()) ix = ix->flat.get();  // (a set of source rows: the same from either stored order)
+        if (use_lds_path(ix)) {
+            std::vector<u32> pos;
+            GT_TRY(subset_positions(ix, qc, qs, qe, nq, has_min, min_overlap, pos));
+            vals.reserve(pos.size());
+            for (u32 p : pos) vals.push_back(ix->h_vals[p]);
+        } else {
+            std::vector<u64> off(nq + 1);
+            HostOut<u32> hv;
+            u64 h = 0;
+            GT_TRY(enumerate_to_host(ix, qc, qs, qe, nq, has_min, min_overlap, off.data(), &hv.p, nullptr, nullptr, &h));
+            vals.assign(hv.p, hv.p + h);
+        }
+        // BTreeSet<usize>: ascending, unique
+        std::sort(vals.begin(), vals.end());
+        vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+        HostOut<u32> res;
+        GT_TRY(res.alloc(vals.size()));
+        if (!vals.empty()) memcpy(res.p, vals.data(), vals.size() * 4);
+        *out_idx = res.release();
+        *out_n = vals.size();
+        return GTARS_OK;
+    });
 }
 
 // ---------------------------------------------------------------------- IGD
@@ -2389,30 +2372,31 @@ static gtars_status build_pieces_view(gtars_igd *g, const uint32_t *chrom, const
     return GTARS_OK;
 }
 
-static gtars_status gtars_igd_build_impl(const uint32_t *chrom, const int32_t *start, const int32_t *end,
-                                         const int32_t *value, const uint32_t *file_idx, uint64_t n, uint32_t n_chrom,
-                                         uint32_t n_files, gtars_igd_t **out) {
-    gtars_status st = gtars_igd_build_core(chrom, start, end, value, file_idx, n, n_chrom, n_files, false, out);
-    if (st) return st;
-    // The pieces view is an accelerator, not part of the database: when it cannot be built (device or host memory: it is a second
-    // copy of the records) the flat layout alone serves every query correctly, only slower for databases with long records.
-    try {
-        const gtars_status pv = build_pieces_view(*out, chrom, start, end, file_idx, n);
-        if (pv != GTARS_OK) {
-            // (an accelerator that is missing is a slowdown nobody asked about: say so once per process, and why -- a failure that
-            // is not a memory shortage would otherwise only ever show as that slowdown)
-            static std::atomic<bool> said{false};
-            if (!said.exchange(true))
-                fprintf(stderr, "gtars_amd: the pieces view of an IGD database could not be built (status %d: %s); databases with long records count slower\n",
-                        (int)pv, gtars_last_error());
-            prof_note_fact("igd_pieces_view_dropped");
-            (void)hipGetLastError();
-            set_error("");
+gtars_status gtars_igd_build(const uint32_t *chrom, const int32_t *start, const int32_t *end,
+                             const int32_t *value, const uint32_t *file_idx, uint64_t n, uint32_t n_chrom,
+                             uint32_t n_files, gtars_igd_t **out) {
+    return guarded([&]() -> gtars_status {
+        GT_TRY(gtars_igd_build_core(chrom, start, end, value, file_idx, n, n_chrom, n_files, false, out));
+        // The pieces view is an accelerator, not part of the database: when it cannot be built (device or host memory: it is a second
+        // copy of the records) the flat layout alone serves every query correctly, only slower for databases with long records.
+        try {
+            const gtars_status pv = build_pieces_view(*out, chrom, start, end, file_idx, n);
+            if (pv != GTARS_OK) {
+                // (an accelerator that is missing is a slowdown nobody asked about: say so once per process, and why -- a failure that
+                // is not a memory shortage would otherwise only ever show as that slowdown)
+                static std::atomic<bool> said{false};
+                if (!said.exchange(true))
+                    fprintf(stderr, "gtars_amd: the pieces view of an IGD database could not be built (status %d: %s); databases with long records count slower\n",
+                            (int)pv, gtars_last_error());
+                prof_note_fact("igd_pieces_view_dropped");
+                (void)hipGetLastError();
+                set_error("");
+            }
+        } catch (const std::bad_alloc &) {
+            (*out)->pieces = nullptr;
         }
-    } catch (const std::bad_alloc &) {
-        (*out)->pieces = nullptr;
-    }
-    return GTARS_OK;
+        return GTARS_OK;
+    });
 }
 
 // which index serves a count: the pieces view for min_overlap == 1 when the database has one (binary counts: only in their
@@ -2459,25 +2443,25 @@ uint64_t gtars_igd_total_records(const gtars_igd_t *g, int32_t nbp) {
 
 gtars_status gtars_igd_export(const gtars_igd_t *g, uint32_t *chrom, int32_t *start, int32_t *end, int32_t *value,
                               uint32_t *file_idx) {
-    GT_ON_DEVICE_OF(g);
-    if (!g) return fail(GTARS_ERR_INVALID_ARG, "NULL handle");
-    const size_t n = g->n;
-    if (!n) return GTARS_OK;
-    if (start || end) {
-        gtars_status ms = g->ensure_mirror();
-        if (ms) return ms;
-    }
-    if (start) memcpy(start, g->h_starts.data(), n * 4);
-    if (end) memcpy(end, g->h_ends.data(), n * 4);
-    if (value) GT_HIP(hipMemcpy(value, g->values.p, n * 4, hipMemcpyDeviceToHost));
-    if (file_idx) GT_HIP(hipMemcpy(file_idx, g->files.p, n * 4, hipMemcpyDeviceToHost));
-    if (chrom) {
-        std::vector<u32> off(g->n_chrom + 1);
-        GT_HIP(hipMemcpy(off.data(), g->chrom_off.p, off.size() * 4, hipMemcpyDeviceToHost));
-        for (u32 c = 0; c < g->n_chrom; ++c)
-            for (u32 i = off[c]; i < off[c + 1]; ++i) chrom[i] = c;
-    }
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(g);
+        if (!g) return fail(GTARS_ERR_INVALID_ARG, "NULL handle");
+        const size_t n = g->n;
+        if (!n) return GTARS_OK;
+        if (start || end) GT_TRY(g->ensure_mirror());
+        if (start) memcpy(start, g->h_starts.data(), n * 4);
+        if (end) memcpy(end, g->h_ends.data(), n * 4);
+        std::vector<u32> off;
+        StreamFrame fr(nullptr);
+        if (value) GT_TRY(fr.download(value, g->values.p, n));
+        if (file_idx) GT_TRY(fr.download(file_idx, g->files.p, n));
+        if (chrom) GT_TRY(fr.download(off, g->chrom_off.p, (size_t)g->n_chrom + 1));
+        GT_TRY(fr.drain());
+        if (chrom)
+            for (u32 c = 0; c < g->n_chrom; ++c)
+                for (u32 i = off[c]; i < off[c + 1]; ++i) chrom[i] = c;
+        return GTARS_OK;
+    });
 }
 
 gtars_status gtars_igd_count_device(const gtars_igd_t *g, const uint32_t *d_qc, const uint32_t *d_qs,
@@ -2567,108 +2551,95 @@ gtars_status gtars_igd_count_sets_device(const gtars_igd_t *g, const uint32_t *d
 
 gtars_status gtars_igd_count_sets(const gtars_igd_t *g, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
                                   const uint64_t *set_off, uint32_t n_sets, int32_t min_overlap, int binary, uint64_t *hits) {
-    GT_ON_DEVICE_OF(g);
-    if (!set_off || n_sets == 0) return fail(GTARS_ERR_INVALID_ARG, "set_off is NULL or n_sets is 0");
-    const u64 nq = set_off[n_sets];
-    gtars_status st = check_query_args(g, qc, qs, qe, nq);
-    if (st) return st;
-    if (!hits && g->n_files) return fail(GTARS_ERR_INVALID_ARG, "hits is NULL");
-    st = require_device();
-    if (st) return st;
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u64> d;
-    GT_TRY(d.alloc((size_t)std::max<u32>(g->n_files, 1) * n_sets));
-    st = gtars_igd_count_sets_device(g, q.c, q.s, q.e, set_off, n_sets, min_overlap, binary, d.p, nullptr);
-    if (st) return st;
-    if (g->n_files) GT_HIP(hipMemcpy(hits, d.p, (size_t)g->n_files * n_sets * 8, hipMemcpyDeviceToHost));
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(g);
+        if (!set_off || n_sets == 0) return fail(GTARS_ERR_INVALID_ARG, "set_off is NULL or n_sets is 0");
+        const u64 nq = set_off[n_sets];
+        GT_TRY(check_query_args(g, qc, qs, qe, nq));
+        if (!hits && g->n_files) return fail(GTARS_ERR_INVALID_ARG, "hits is NULL");
+        GT_TRY(require_device());
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de;
+        u64 *d;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d, (size_t)std::max<u32>(g->n_files, 1) * n_sets));
+        GT_TRY(gtars_igd_count_sets_device(g, dc, ds, de, set_off, n_sets, min_overlap, binary, d, fr.st));
+        GT_TRY(fr.download(hits, d, (size_t)g->n_files * n_sets));
+        return fr.drain();
+    });
 }
 
 gtars_status gtars_igd_count(const gtars_igd_t *g, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
                              uint64_t nq, int32_t min_overlap, int binary, uint64_t *hits) {
-    GT_ON_DEVICE_OF(g);
-    gtars_status st = check_query_args(g, qc, qs, qe, nq);
-    if (st) return st;
-    if (!hits && g->n_files) return fail(GTARS_ERR_INVALID_ARG, "hits is NULL");
-    st = require_device();
-    if (st) return st;
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u64> d;
-    GT_TRY(d.alloc(std::max<u32>(g->n_files, 1)));
-    st = gtars_igd_count_device(g, q.c, q.s, q.e, nq, min_overlap, binary, d.p, nullptr);
-    if (st) return st;
-    if (g->n_files) GT_HIP(hipMemcpy(hits, d.p, (size_t)g->n_files * 8, hipMemcpyDeviceToHost));
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(g);
+        GT_TRY(check_query_args(g, qc, qs, qe, nq));
+        if (!hits && g->n_files) return fail(GTARS_ERR_INVALID_ARG, "hits is NULL");
+        GT_TRY(require_device());
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de;
+        u64 *d;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d, std::max<u32>(g->n_files, 1)));
+        GT_TRY(gtars_igd_count_device(g, dc, ds, de, nq, min_overlap, binary, d, fr.st));
+        GT_TRY(fr.download(hits, d, g->n_files));
+        return fr.drain();
+    });
 }
 
 gtars_status gtars_igd_count_per_query(const gtars_igd_t *g, const uint32_t *qc, const uint32_t *qs,
                                        const uint32_t *qe, uint64_t nq, int32_t min_overlap,
                                        uint32_t *counts) {
-    GT_ON_DEVICE_OF(g);
-    gtars_status st = check_query_args(g, qc, qs, qe, nq);
-    if (st) return st;
-    st = require_device();
-    if (st) return st;
-    if (!nq) return GTARS_OK;
-    if (min_overlap < 1 && (st = g->ensure_ntiles())) return st;  // the walk's tile test (kernels.hip, IgdQual)
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u32> d;
-    GT_TRY(d.alloc(nq));
-    bool uniq = false;
-    if ((st = g->ensure_values_unique(&uniq))) return st;
-    st = launch_igd_count_per_query(g->view(), q.c, q.s, q.e, nq, min_overlap, d.p, uniq, nullptr);
-    if (st) return st;
-    GT_HIP(hipMemcpy(counts, d.p, nq * 4, hipMemcpyDeviceToHost));
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(g);
+        GT_TRY(check_query_args(g, qc, qs, qe, nq));
+        GT_TRY(require_device());
+        if (!nq) return GTARS_OK;
+        if (min_overlap < 1) GT_TRY(g->ensure_ntiles());  // the walk's tile test (kernels.hip, IgdQual)
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de, *d;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d, nq));
+        bool uniq = false;
+        GT_TRY(g->ensure_values_unique(&uniq));
+        GT_TRY(launch_igd_count_per_query(g->view(), dc, ds, de, nq, min_overlap, d, uniq, fr.st));
+        GT_TRY(fr.download(counts, d, nq));
+        return fr.drain();
+    });
 }
 
 gtars_status gtars_igd_find_pairs(const gtars_igd_t *g, const uint32_t *qc, const uint32_t *qs,
                                   const uint32_t *qe, uint64_t nq, int32_t min_overlap, uint32_t **out_q,
                                   uint32_t **out_s, uint64_t *out_n) {
-    GT_ON_DEVICE_OF(g);
-    gtars_status st = check_query_args(g, qc, qs, qe, nq);
-    if (st) return st;
-    if (!out_q || !out_s || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
-    *out_q = *out_s = nullptr;
-    *out_n = 0;
-    st = require_device();
-    if (st) return st;
-    if (min_overlap < 1 && (st = g->ensure_ntiles())) return st;  // the walk's tile test (kernels.hip, IgdQual)
-    DevQueries q;
-    st = q.upload(qc, qs, qe, nq);
-    if (st) return st;
-    DevBuf<u32> d_cnt;
-    DevBuf<u64> d_off;
-    DevBuf<u8> d_ws;
-    GT_TRY(d_cnt.alloc(nq));
-    GT_TRY(d_off.alloc(nq + 1));
-    const size_t wsb = scan_ws_bytes(nq);
-    GT_TRY(d_ws.alloc(wsb));
-    bool uniq = false;
-    if ((st = g->ensure_values_unique(&uniq))) return st;
-    GT_TRY(launch_igd_count_per_query(g->view(), q.c, q.s, q.e, nq, min_overlap, d_cnt.p, uniq, nullptr));
-    GT_TRY(launch_scan_u32_to_u64(d_cnt.p, nq, d_off.p, d_ws.p, wsb, nullptr));
-    u64 h = 0;
-    GT_HIP(hipMemcpy(&h, d_off.p + nq, 8, hipMemcpyDeviceToHost));
-    DevBuf<u32> d_q, d_s;
-    GT_TRY(d_q.alloc(h));
-    GT_TRY(d_s.alloc(h));
-    GT_TRY(launch_igd_fill_pairs(g->view(), q.c, q.s, q.e, nq, min_overlap, d_off.p, d_q.p, d_s.p, uniq, nullptr));
-    *out_q = host_alloc<u32>(h);
-    *out_s = host_alloc<u32>(h);
-    if (!*out_q || !*out_s) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    if (h) {
-        GT_HIP(hipMemcpy(*out_q, d_q.p, h * 4, hipMemcpyDeviceToHost));
-        GT_HIP(hipMemcpy(*out_s, d_s.p, h * 4, hipMemcpyDeviceToHost));
-    }
-    *out_n = h;
-    return GTARS_OK;
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(g);
+        GT_TRY(check_query_args(g, qc, qs, qe, nq));
+        if (!out_q || !out_s || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        *out_q = *out_s = nullptr;
+        *out_n = 0;
+        GT_TRY(require_device());
+        if (min_overlap < 1) GT_TRY(g->ensure_ntiles());  // the walk's tile test (kernels.hip, IgdQual)
+        HostOut<u32> h_q, h_s;
+        StreamFrame fr(nullptr);
+        u32 *dc, *ds, *de, *d_cnt, *d_q, *d_s;
+        GT_TRY(upload_queries(fr, qc, qs, qe, nq, &dc, &ds, &de));
+        GT_TRY(fr.alloc(&d_cnt, nq));
+        bool uniq = false;
+        GT_TRY(g->ensure_values_unique(&uniq));
+        GT_TRY(launch_igd_count_per_query(g->view(), dc, ds, de, nq, min_overlap, d_cnt, uniq, fr.st));
+        u64 *d_off, h = 0;
+        GT_TRY(scan_total(fr, d_cnt, nq, &d_off, &h));
+        GT_TRY(fr.alloc(&d_q, h));
+        GT_TRY(fr.alloc(&d_s, h));
+        GT_TRY(launch_igd_fill_pairs(g->view(), dc, ds, de, nq, min_overlap, d_off, d_q, d_s, uniq, fr.st));
+        GT_TRY(h_q.download(fr, d_q, h));
+        GT_TRY(h_s.download(fr, d_s, h));
+        GT_TRY(fr.drain());
+        *out_q = h_q.release();
+        *out_s = h_s.release();
+        *out_n = h;
+        return GTARS_OK;
+    });
 }
 
 gtars_status gtars_lola_contingency_device(const uint64_t *d_user_hits, const uint64_t *d_universe_hits,
@@ -2698,104 +2669,74 @@ static u32 bits_insert_pos(const u32 *S, const u32 *E, u32 n, u32 start, u32 end
     return cursor;
 }
 
-static gtars_status gtars_index_insert_impl(const gtars_index_t *ix, uint32_t chrom, uint32_t start, uint32_t end,
-                                            uint32_t val, gtars_index_t **out) {
-    GT_ON_DEVICE_OF(ix);
-    if (!out) return fail(GTARS_ERR_INVALID_ARG, "out is NULL");
-    *out = nullptr;
-    if (!ix) return fail(GTARS_ERR_INVALID_ARG, "NULL index");
-    if (ix->kind != GTARS_KIND_BITS) return fail(GTARS_ERR_INVALID_ARG, "insert is a Bits operation (bits.rs:209-222)");
-    if (chrom >= ix->n_chrom) return fail(GTARS_ERR_INVALID_ARG, "interval chromosome id >= n_chrom");
-    const u64 n = ix->n + 1;
-    std::vector<u32> c(n), s(n), e(n), v(n);
-    const u32 lo = ix->h_chrom_off[chrom], hi = ix->h_chrom_off[chrom + 1];
-    const u32 at = lo + bits_insert_pos(ix->h_starts.data() + lo, ix->h_ends.data() + lo, hi - lo, start, end);
-    u64 w = 0;
-    for (u32 k = 0; k < ix->n_chrom; ++k)
-        for (u32 p = ix->h_chrom_off[k]; p <= ix->h_chrom_off[k + 1]; ++p) {
-            if (k == chrom && p == at) {  // in front of equal (start, end) keys: the stable build keeps it there
-                c[w] = chrom, s[w] = start, e[w] = end, v[w] = val;
-                ++w;
-            }
-            if (p == ix->h_chrom_off[k + 1]) break;
-            c[w] = k, s[w] = ix->h_starts[p], e[w] = ix->h_ends[p], v[w] = ix->h_vals[p];
-            ++w;
-        }
-    return gtars_index_build_impl(c.data(), s.data(), e.data(), v.data(), n, ix->n_chrom, GTARS_KIND_BITS, out);
-}
-
-static gtars_status gtars_index_seek_impl(const gtars_index_t *ix, uint32_t chrom, uint32_t start, uint32_t stop,
-                                          uint64_t *cursor, uint32_t *out_vals, uint64_t capacity, uint64_t *n_hits) {
-    if (!ix || !cursor || !n_hits) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    if (ix->kind != GTARS_KIND_BITS) return fail(GTARS_ERR_INVALID_ARG, "seek is a Bits operation (bits.rs:364-386)");
-    *n_hits = 0;
-    if (chrom >= ix->n_chrom) return GTARS_OK;
-    const u32 lo = ix->h_chrom_off[chrom];
-    const u64 n = ix->h_chrom_off[chrom + 1] - lo;
-    const u32 *S = ix->h_starts.data() + lo, *E = ix->h_ends.data() + lo, *V = ix->h_vals.data() + lo;
-    const u32 max_len = ix->h_chrom_aux[chrom];
-    const u32 key = start >= max_len ? start - max_len : 0u;  // checked_sub(..).unwrap_or(0)
-    u64 cur = *cursor;
-    if (cur == 0 || (cur < n && S[cur] > start)) {
-        // Bits::lower_bound (bits.rs:250-264), same probe sequence
-        u64 size = n, low = 0;
-        while (size > 0) {
-            const u64 half = size / 2, other_half = size - half, probe = low + half, other_low = low + other_half;
-            size = half;
-            low = S[probe] < key ? other_low : low;
-        }
-        cur = low;
-    }
-    while (cur + 1 < n && S[cur + 1] < key) ++cur;
-    *cursor = cur;
-    u64 k = 0;
-    for (u64 off = cur; off < n; ++off) {  // IterFind::next, bits.rs:433-446
-        if (S[off] < stop && E[off] > start) {
-            if (out_vals && k < capacity) out_vals[k] = V[off];
-            ++k;
-        } else if (S[off] >= stop) {
-            break;
-        }
-    }
-    *n_hits = k;
-    if (out_vals && k > capacity) return fail(GTARS_ERR_CAPACITY, "seek: more hits than capacity");
-    return GTARS_OK;
-}
-
-// ---- the C ABI never lets a C++ exception cross it (std::bad_alloc of a huge build, std::length_error ...)
 extern "C" {
-
-gtars_status gtars_index_build(const uint32_t *chrom, const uint32_t *start, const uint32_t *end,
-                               const uint32_t *val, uint64_t n, uint32_t n_chrom, int kind,
-                               gtars_index_t **out) {
-    return guarded([&]() -> gtars_status { return gtars_index_build_impl(chrom, start, end, val, n, n_chrom, kind, out); });
-}
 
 gtars_status gtars_index_insert(const gtars_index_t *ix, uint32_t chrom, uint32_t start, uint32_t end, uint32_t val,
                                 gtars_index_t **out) {
-    return guarded([&]() -> gtars_status { return gtars_index_insert_impl(ix, chrom, start, end, val, out); });
+    return guarded([&]() -> gtars_status {
+        GT_ON_DEVICE_OF(ix);
+        if (!out) return fail(GTARS_ERR_INVALID_ARG, "out is NULL");
+        *out = nullptr;
+        if (!ix) return fail(GTARS_ERR_INVALID_ARG, "NULL index");
+        if (ix->kind != GTARS_KIND_BITS) return fail(GTARS_ERR_INVALID_ARG, "insert is a Bits operation (bits.rs:209-222)");
+        if (chrom >= ix->n_chrom) return fail(GTARS_ERR_INVALID_ARG, "interval chromosome id >= n_chrom");
+        const u64 n = ix->n + 1;
+        std::vector<u32> c(n), s(n), e(n), v(n);
+        const u32 lo = ix->h_chrom_off[chrom], hi = ix->h_chrom_off[chrom + 1];
+        const u32 at = lo + bits_insert_pos(ix->h_starts.data() + lo, ix->h_ends.data() + lo, hi - lo, start, end);
+        u64 w = 0;
+        for (u32 k = 0; k < ix->n_chrom; ++k)
+            for (u32 p = ix->h_chrom_off[k]; p <= ix->h_chrom_off[k + 1]; ++p) {
+                if (k == chrom && p == at) {  // in front of equal (start, end) keys: the stable build keeps it there
+                    c[w] = chrom, s[w] = start, e[w] = end, v[w] = val;
+                    ++w;
+                }
+                if (p == ix->h_chrom_off[k + 1]) break;
+                c[w] = k, s[w] = ix->h_starts[p], e[w] = ix->h_ends[p], v[w] = ix->h_vals[p];
+                ++w;
+            }
+        return build_index(c.data(), s.data(), e.data(), v.data(), n, ix->n_chrom, GTARS_KIND_BITS, out);
+    });
 }
 
 gtars_status gtars_index_seek(const gtars_index_t *ix, uint32_t chrom, uint32_t start, uint32_t stop, uint64_t *cursor,
                               uint32_t *out_vals, uint64_t capacity, uint64_t *n_hits) {
-    return guarded([&]() -> gtars_status { return gtars_index_seek_impl(ix, chrom, start, stop, cursor, out_vals, capacity, n_hits); });
-}
-
-gtars_status gtars_igd_build(const uint32_t *chrom, const int32_t *start, const int32_t *end,
-                             const int32_t *value, const uint32_t *file_idx, uint64_t n, uint32_t n_chrom,
-                             uint32_t n_files, gtars_igd_t **out) {
-    return guarded([&]() -> gtars_status { return gtars_igd_build_impl(chrom, start, end, value, file_idx, n, n_chrom, n_files, out); });
-}
-
-gtars_status gtars_tokenize(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs,
-                            const uint32_t *qe, uint64_t nq, uint64_t *offsets, uint32_t **out_ids,
-                            uint64_t *out_n) {
-    return guarded([&]() -> gtars_status { return gtars_tokenize_impl(ix, qc, qs, qe, nq, offsets, out_ids, out_n); });
-}
-
-gtars_status gtars_tokenize_into(const gtars_index_t *ix, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe,
-                                 uint64_t nq, uint64_t *offsets, uint32_t *ids, uint64_t ids_capacity, uint64_t *out_n) {
-    return guarded([&]() -> gtars_status { return gtars_tokenize_into_impl(ix, qc, qs, qe, nq, offsets, ids, ids_capacity, out_n); });
+    return guarded([&]() -> gtars_status {
+        if (!ix || !cursor || !n_hits) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (ix->kind != GTARS_KIND_BITS) return fail(GTARS_ERR_INVALID_ARG, "seek is a Bits operation (bits.rs:364-386)");
+        *n_hits = 0;
+        if (chrom >= ix->n_chrom) return GTARS_OK;
+        const u32 lo = ix->h_chrom_off[chrom];
+        const u64 n = ix->h_chrom_off[chrom + 1] - lo;
+        const u32 *S = ix->h_starts.data() + lo, *E = ix->h_ends.data() + lo, *V = ix->h_vals.data() + lo;
+        const u32 max_len = ix->h_chrom_aux[chrom];
+        const u32 key = start >= max_len ? start - max_len : 0u;  // checked_sub(..).unwrap_or(0)
+        u64 cur = *cursor;
+        if (cur == 0 || (cur < n && S[cur] > start)) {
+            // Bits::lower_bound (bits.rs:250-264), same probe sequence
+            u64 size = n, low = 0;
+            while (size > 0) {
+                const u64 half = size / 2, other_half = size - half, probe = low + half, other_low = low + other_half;
+                size = half;
+                low = S[probe] < key ? other_low : low;
+            }
+            cur = low;
+        }
+        while (cur + 1 < n && S[cur + 1] < key) ++cur;
+        *cursor = cur;
+        u64 k = 0;
+        for (u64 off = cur; off < n; ++off) {  // IterFind::next, bits.rs:433-446
+            if (S[off] < stop && E[off] > start) {
+                if (out_vals && k < capacity) out_vals[k] = V[off];
+                ++k;
+            } else if (S[off] >= stop) {
+                break;
+            }
+        }
+        *n_hits = k;
+        if (out_vals && k > capacity) return fail(GTARS_ERR_CAPACITY, "seek: more hits than capacity");
+        return GTARS_OK;
+    });
 }
 
 }  // extern "C"
