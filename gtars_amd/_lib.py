@@ -168,11 +168,25 @@ _HOST_SIG = {
     "gtars_regionset_chromosome_statistics": (C.c_int, [vp, pp, pp, pu64]),
     "gtars_gtf_read": (C.c_int, [cstr, C.c_int, C.c_int, pp, pp, pp]),
     "gtars_regionset_stranded_reduce": (C.c_int, [vp, vp, vp, pp, pp]),
+    "gtars_regionset_stranded_setdiff": (C.c_int, [vp, vp, vp, vp, pp, pp]),
+    "gtars_gtf_read_utrs": (C.c_int, [cstr, C.c_int, C.c_int, pp, pp, pp]),
     "gtars_tss_index_from_regionset": (C.c_int, [vp, pp]),
     "gtars_tss_index_free": (None, [vp]),
     "gtars_tss_index_len": (u64, [vp]),
     "gtars_tss_index_device": (C.c_int, [vp]),
     "gtars_tss_index_distances": (C.c_int, [vp, vp, vp, vp]),
+    "gtars_partition_list_from_sets": (C.c_int, [vp, vp, u32, pp]),
+    "gtars_partition_list_free": (None, [vp]),
+    "gtars_partition_list_len": (u32, [vp]),
+    "gtars_partition_list_name": (cstr, [vp, u32]),
+    "gtars_partition_list_n_chrom": (u32, [vp]),
+    "gtars_partition_list_chrom_name": (cstr, [vp, u32]),
+    "gtars_partition_list_set": (C.c_int, [vp, u32, pp]),
+    "gtars_partition_list_sizes": (C.c_int, [vp, vp]),
+    "gtars_partition_list_device": (C.c_int, [vp]),
+    "gtars_partitions_count": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "gtars_partitions_count_device": (C.c_int, [vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, vp]),
+    "gtars_partition_expected": (C.c_int, [vp, vp, u32, u32, u64, vp, vp, vp]),
     "gtars_uniwig_counts": (C.c_int, [vp, vp, u64, u32, u32, C.c_int, u64, pu64, pp, pu64]),
     "gtars_uniwig_extent": (C.c_int, [vp, vp, u64, u32, u32, C.c_int, pu64, pu64]),
     "gtars_uniwig_counts_device": (C.c_int, [vp, vp, u64, u32, C.c_int, u64, u64, vp, vp]),

@@ -1468,8 +1468,19 @@ struct GtfChunk {
     std::string err;  // the chunk's first error (rows after it are never read)
 };
 
-// the lines of text[b, e) (e is a line start or the end of the text)
-void gtf_scan(const std::string &text, size_t b, size_t e, bool filter_pc, bool convert, GtfChunk &c) {
+// One kept row of a GTF: its feature (index into kFeatures of gtf_rows), the chromosome name after conversion, the
+// coordinates, and the row's 7th and 9th fields as they stand
+struct GtfRow {
+    int feature;
+    const std::string &chr;
+    uint32_t start, end;
+    std::string_view strand, attrs;
+};
+
+// row(GtfRow) for every kept row among the lines of text[b, e) (e is a line start or the end of the text); err: the first
+// error (rows after it are never read)
+template <class F>
+void gtf_rows(const std::string &text, size_t b, size_t e, bool filter_pc, bool convert, std::string &err, F &&row) {
     static const char *const kFeatures[] = {"gene", "exon", "three_prime_utr", "five_prime_utr", "UTR", "CDS"};
     const char *s = text.data();
     std::string name;
@@ -1481,7 +1492,7 @@ void gtf_scan(const std::string &text, size_t b, size_t e, bool filter_pc, bool 
         const size_t lb = b;
         b = nl ? le + 1 : e;
         if (!valid_utf8((const unsigned char *)s + lb, le - lb)) {
-            c.err = "stream did not contain valid UTF-8";
+            err = "stream did not contain valid UTF-8";
             return;
         }
         if (ce > lb && s[lb] == '#') continue;
@@ -1502,35 +1513,100 @@ void gtf_scan(const std::string &text, size_t b, size_t e, bool filter_pc, bool 
         for (int k = 0; k < 6; ++k)
             if (ft == kFeatures[k]) f = k;
         if (f < 0) continue;
+        const std::string_view at(s + fb[8], fe[8] - fb[8]);
         if (filter_pc) {
-            const std::string_view at(s + fb[8], fe[8] - fb[8]);
             if (at.find("gene_biotype \"protein_coding\"") == std::string_view::npos &&
                 at.find("gene_type \"protein_coding\"") == std::string_view::npos)
                 continue;
         }
         uint32_t st, en;
         if (const char *m = rust_parse_u32(s + fb[3], fe[3] - fb[3], st)) {
-            c.err = std::string("Parsing GTF start: ") + m;
+            err = std::string("Parsing GTF start: ") + m;
             return;
         }
         if (const char *m = rust_parse_u32(s + fb[4], fe[4] - fb[4], en)) {
-            c.err = std::string("Parsing GTF end: ") + m;
+            err = std::string("Parsing GTF end: ") + m;
             return;
         }
         name.assign(s + fb[0], fe[0] - fb[0]);
         if (convert && name.compare(0, 3, "chr") != 0) name.insert(0, "chr");
-        auto it = c.ids.find(name);
+        row(GtfRow{f, name, st ? st - 1 : 0, en, std::string_view(s + fb[6], fe[6] - fb[6]), at});
+    }
+}
+
+// Strand::from_char of the field's first character, `dflt` when the field is empty
+uint8_t strand_code(std::string_view field, char dflt) {
+    const char sc = field.empty() ? dflt : field[0];
+    return sc == '+' ? 0 : sc == '-' ? 1 : 2;
+}
+
+void gtf_scan(const std::string &text, size_t b, size_t e, bool filter_pc, bool convert, GtfChunk &c) {
+    gtf_rows(text, b, e, filter_pc, convert, c.err, [&](const GtfRow &r) {
+        auto it = c.ids.find(r.chr);
         if (it == c.ids.end()) {
-            it = c.ids.emplace(name, (uint32_t)c.names.size()).first;
-            c.names.push_back(name);
+            it = c.ids.emplace(r.chr, (uint32_t)c.names.size()).first;
+            c.names.push_back(r.chr);
         }
         c.chrom.push_back(it->second);
-        c.start.push_back(st ? st - 1 : 0);
-        c.end.push_back(en);
-        const char sc = fe[6] > fb[6] ? s[fb[6]] : '.';
-        c.strand.push_back(sc == '+' ? 0 : sc == '-' ? 1 : 2);
-        c.feature.push_back((uint8_t)f);
+        c.start.push_back(r.start);
+        c.end.push_back(r.end);
+        c.strand.push_back(strand_code(r.strand, '.'));
+        c.feature.push_back((uint8_t)r.feature);
+    });
+}
+
+// the GTF's text: plain, or gzip members when the path ends in ".gz"
+gtars_status gtf_text(const char *path, std::string &text) {
+    const std::string p(path);
+    if (!is_regular_file(p)) return fail(GTARS_ERR_IO, "No such file or directory (os error 2): " + p);
+    std::string err;
+    if (ends_with(p, ".gz")) {
+        // MultiGzDecoder: gzip members only
+        std::string raw;
+        size_t n_raw = 0;
+        if (!read_file_padded(p, raw, n_raw)) return fail(GTARS_ERR_IO, "Failed to open file: \"" + p + "\": " + strerror(errno));
+        if (n_raw && (n_raw < 2 || (unsigned char)raw[0] != 0x1f || (unsigned char)raw[1] != 0x8b))
+            return fail(GTARS_ERR_IO, "invalid gzip header");
     }
+    if (!read_all(p, text, err)) return fail(GTARS_ERR_IO, err);
+    return GTARS_OK;
+}
+
+// extract_gtf_transcript_id (partitions.rs:353-361): behind the first `transcript_id "` up to the next '"'
+bool gtf_transcript_id(std::string_view attrs, std::string &out) {
+    static const std::string_view marker = "transcript_id \"";
+    const size_t at = attrs.find(marker);
+    if (at == std::string_view::npos) return false;
+    const size_t b = at + marker.size(), e = attrs.find('"', b);
+    if (e == std::string_view::npos) return false;
+    out.assign(attrs.substr(b, e - b));
+    return true;
+}
+
+// (segment key, start, end) columns of the rows i of rs with keep[i] != 0: segment = (chr bytewise, strand_ord)
+gtars_status stranded_cols(const RankSpace &sp, const gtars_regionset *rs, const uint8_t *strand, const uint8_t *keep,
+                           std::vector<uint32_t> &seg, std::vector<uint32_t> &st, std::vector<uint32_t> &en) {
+    const std::vector<uint32_t> r = sp.ranks_of(rs);
+    for (size_t i = 0; i < rs->size(); ++i) {
+        if (keep && !keep[i]) continue;
+        if (strand[i] > 2) return fail(GTARS_ERR_INVALID_ARG, "strand code out of range");
+        seg.push_back(r[i] * 3 + strand[i]);
+        st.push_back(rs->starts[i]);
+        en.push_back(rs->ends[i]);
+    }
+    return GTARS_OK;
+}
+
+// ... and a result over such keys as a region set and its strand codes
+gtars_status stranded_result(const RankSpace &sp, gtars::SetOut &o, gtars_regionset_t **out, uint8_t **out_strand) {
+    std::vector<uint8_t> ostrand(o.rank.size());
+    for (size_t i = 0; i < o.rank.size(); ++i) {
+        ostrand[i] = (uint8_t)(o.rank[i] % 3);
+        o.rank[i] /= 3;
+    }
+    if (const gtars_status e = to_malloc(ostrand, out_strand)) return e;
+    *out = regionset_from(sp, o);
+    return GTARS_OK;
 }
 
 }  // namespace
@@ -1543,18 +1619,8 @@ gtars_status gtars_gtf_read(const char *path, int filter_protein_coding, int con
         if (!path || !out_rows || !out_strand || !out_feature) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
         *out_rows = nullptr;
         *out_strand = *out_feature = nullptr;
-        const std::string p(path);
-        if (!is_regular_file(p)) return fail(GTARS_ERR_IO, "No such file or directory (os error 2): " + p);
-        std::string text, err;
-        if (ends_with(p, ".gz")) {
-            // MultiGzDecoder: gzip members only
-            std::string raw;
-            size_t n_raw = 0;
-            if (!read_file_padded(p, raw, n_raw)) return fail(GTARS_ERR_IO, "Failed to open file: \"" + p + "\": " + strerror(errno));
-            if (n_raw && (n_raw < 2 || (unsigned char)raw[0] != 0x1f || (unsigned char)raw[1] != 0x8b))
-                return fail(GTARS_ERR_IO, "invalid gzip header");
-        }
-        if (!read_all(p, text, err)) return fail(GTARS_ERR_IO, err);
+        std::string text;
+        if (const gtars_status e = gtf_text(path, text)) return e;
         // cut at line starts into up to 16 chunks of >= 1 MiB
         const size_t n = text.size();
         const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_thread_budget(16), n >> 20));
@@ -1618,26 +1684,109 @@ gtars_status gtars_regionset_stranded_reduce(const gtars_regionset_t *rs, const 
         RankSpace sp;
         sp.build({rs});
         if (sp.size() > 0x7FFFFFFFu / 3) return fail(GTARS_ERR_INVALID_ARG, "too many chromosomes");
-        const std::vector<uint32_t> r = sp.ranks_of(rs);
         std::vector<uint32_t> seg, st, en;
-        for (size_t i = 0; i < rs->size(); ++i) {
-            if (keep && !keep[i]) continue;
-            if (strand[i] > 2) return fail(GTARS_ERR_INVALID_ARG, "strand code out of range");
-            seg.push_back(r[i] * 3 + strand[i]);  // (chr bytewise, strand_ord): one segment key
-            st.push_back(rs->starts[i]);
-            en.push_back(rs->ends[i]);
-        }
+        if (const gtars_status e = stranded_cols(sp, rs, strand, keep, seg, st, en)) return e;
         gtars::SetOut o;
         if (const gtars_status e = gtars::setops_reduce(gtars::SetCols{seg.data(), st.data(), en.data(), (uint64_t)seg.size()},
                                                         sp.size() * 3, o))
             return e;
-        std::vector<uint8_t> ostrand(o.rank.size());
-        for (size_t i = 0; i < o.rank.size(); ++i) {
-            ostrand[i] = (uint8_t)(o.rank[i] % 3);
-            o.rank[i] /= 3;
+        return stranded_result(sp, o, out, out_strand);
+    });
+}
+
+gtars_status gtars_regionset_stranded_setdiff(const gtars_regionset_t *a, const uint8_t *a_strand, const gtars_regionset_t *b,
+                                              const uint8_t *b_strand, gtars_regionset_t **out, uint8_t **out_strand) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!a || !b || !out || !out_strand || (!a_strand && a->size()) || (!b_strand && b->size()))
+            return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        *out_strand = nullptr;
+        RankSpace sp;
+        sp.build({a, b});
+        if (sp.size() > 0x7FFFFFFFu / 3) return fail(GTARS_ERR_INVALID_ARG, "too many chromosomes");
+        // The reference's sweep (stranded_region_set.rs:175-211) is sweep_setdiff_chr (region_set.rs:1229-1265) line for
+        // line, zero-length and inverted rows included, run per (chr, strand) instead of per chr: K8's setdiff over
+        // the folded key is that.
+        std::vector<uint32_t> seg[2], st[2], en[2];
+        if (const gtars_status e = stranded_cols(sp, a, a_strand, nullptr, seg[0], st[0], en[0])) return e;
+        if (const gtars_status e = stranded_cols(sp, b, b_strand, nullptr, seg[1], st[1], en[1])) return e;
+        gtars::SetOut o;
+        if (const gtars_status e = gtars::setops_setdiff(gtars::SetCols{seg[0].data(), st[0].data(), en[0].data(), (uint64_t)seg[0].size()},
+                                                         gtars::SetCols{seg[1].data(), st[1].data(), en[1].data(), (uint64_t)seg[1].size()},
+                                                         sp.size() * 3, o))
+            return e;
+        return stranded_result(sp, o, out, out_strand);
+    });
+}
+
+gtars_status gtars_gtf_read_utrs(const char *path, int filter_protein_coding, int convert_ensembl_ucsc, gtars_regionset_t **out_rows,
+                                 uint8_t **out_strand, uint8_t **out_kind) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!path || !out_rows || !out_strand || !out_kind) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_rows = nullptr;
+        *out_strand = *out_kind = nullptr;
+        std::string text, err, tid;
+        if (const gtars_status e = gtf_text(path, text)) return e;
+        struct Piece {  // an exon or an undifferentiated UTR with its transcript
+            uint32_t chr, start, end, tx;
+            char strand;  // the row's strand character, '+' when the field is empty
+        };
+        struct Cds {
+            uint32_t lo = 0xFFFFFFFFu, hi = 0;
+            bool any = false;
+        };
+        auto rs = std::make_unique<gtars_regionset>();
+        std::vector<uint8_t> strand, kind;
+        Dict tx, chrs;  // (a chromosome enters the result's dictionary with its first row)
+        std::vector<Cds> cds;
+        std::vector<Piece> exons, pending;
+        auto emit = [&](uint32_t chr, uint32_t s, uint32_t e, uint8_t st, uint8_t k) {
+            rs->chrom_ids.push_back(rs->chroms.get_or_add(chrs.names[chr]));
+            rs->starts.push_back(s);
+            rs->ends.push_back(e);
+            strand.push_back(st);
+            kind.push_back(k);
+        };
+        gtf_rows(text, 0, text.size(), filter_protein_coding != 0, convert_ensembl_ucsc != 0, err, [&](const GtfRow &r) {
+            if (r.feature == 0) return;  // gene
+            const uint32_t chr = chrs.get_or_add(r.chr);
+            if (r.feature == 2 || r.feature == 3) return emit(chr, r.start, r.end, strand_code(r.strand, '.'), r.feature == 2 ? 0 : 1);
+            if (!gtf_transcript_id(r.attrs, tid)) return;
+            const uint32_t t = tx.get_or_add(tid);
+            if (cds.size() <= t) cds.resize(t + 1);
+            if (r.feature == 5) {
+                cds[t].lo = std::min(cds[t].lo, r.start), cds[t].hi = std::max(cds[t].hi, r.end), cds[t].any = true;
+                return;
+            }
+            (r.feature == 1 ? exons : pending).push_back(Piece{chr, r.start, r.end, t, r.strand.empty() ? '+' : r.strand[0]});
+        });
+        if (!err.empty()) return fail(GTARS_ERR_PARSE, err);
+        auto code = [](char c) -> uint8_t { return c == '+' ? 0 : c == '-' ? 1 : 2; };
+        for (const Piece &u : pending) {
+            const Cds &c = cds[u.tx];
+            if (!c.any) continue;  // a transcript without CDS: dropped
+            const uint64_t um = ((uint64_t)u.start + u.end) / 2, cm = ((uint64_t)c.lo + c.hi) / 2;
+            const bool five = u.strand == '+' ? um < cm : um > cm;
+            emit(u.chr, u.start, u.end, code(u.strand), five ? 1 : 0);
         }
-        if (const gtars_status e = to_malloc(ostrand, out_strand)) return e;
-        *out = regionset_from(sp, o);
+        if (kind.empty()) {  // no UTR row of either form: exon minus CDS per transcript
+            for (const Piece &x : exons) {
+                const Cds &c = cds[x.tx];
+                if (!c.any) continue;
+                const bool minus = x.strand == '-';
+                if (x.start < c.lo) emit(x.chr, x.start, std::min(x.end, c.lo), code(x.strand), minus ? 0 : 1);
+                if (x.end > c.hi) emit(x.chr, std::max(x.start, c.hi), x.end, code(x.strand), minus ? 1 : 0);
+            }
+        }
+        rs->rest_off.assign(kind.size(), 0);
+        rs->has_rest.assign(kind.size(), 0);
+        if (const gtars_status e = to_malloc(strand, out_strand)) return e;
+        if (const gtars_status e = to_malloc(kind, out_kind)) {
+            free(*out_strand);
+            *out_strand = nullptr;
+            return e;
+        }
+        *out_rows = rs.release();
         return GTARS_OK;
     });
 }

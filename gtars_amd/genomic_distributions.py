@@ -4,8 +4,8 @@ nothing beyond region sets.
 ``consensus`` runs on the GPU (csrc/setops.hip, K9): one reduce over the concatenation of the sets, carrying each
 region's set through the sort, and a count of the distinct sets whose regions hit each union region under the AIList
 rule (start < u.end && u.start < end).  ``median_abs_distance`` is host arithmetic.  ``calc_gc_content`` /
-``calc_dinucl_freq`` live in ``gtars.seqstats`` and ``calc_summary_signal`` in ``gtars.signal``; the functions that need
-partitions are not provided.
+``calc_dinucl_freq`` live in ``gtars.seqstats`` and ``calc_summary_signal`` in ``gtars.signal``; ``calc_partitions`` and
+``calc_expected_partitions`` in ``gtars.partitions``.
 """
 from __future__ import annotations
 

@@ -22,9 +22,11 @@ The structural operations and statistics of region_set.rs:288-531 are here too: 
 
 The annotation side of the reference's ``gtars.models`` (gtars-python/src/models/{tss_index,gene_model,gda}.rs) is here
 too: ``TssIndex`` (distances to the nearest TSS / feature midpoint on the GPU, csrc/annot.hip, K10), ``GeneModel`` and
-``GenomicDistAnnotation`` (a GTF read by host threads, genes and exons merged by a strand-aware reduce on the GPU).
-``PartitionList``, ``GenomicDistAnnotation.partition_list`` / ``load_bin``, ``GenomeAssembly``, ``BinaryGenomeAssembly``
-and ``SignalMatrix`` are not provided.
+``GenomicDistAnnotation`` (a GTF read by host threads; genes, exons and the two UTR sets each merged by a strand-aware
+reduce on the GPU).  ``PartitionList`` and what classifies against it live in ``gtars.partitions``
+(``PartitionList.from_annotation`` stands for ``GenomicDistAnnotation.partition_list``); ``GenomicDistAnnotation.load_bin`` /
+``save_bin`` are not provided; ``GenomeAssembly`` / ``BinaryGenomeAssembly`` live
+in ``gtars.seqstats`` and ``SignalMatrix`` in ``gtars.signal``.
 """
 from __future__ import annotations
 
@@ -608,23 +610,75 @@ def _read_gtf(path, filter_protein_coding: bool, convert_ensembl_ucsc: bool):
     return rows, cols[0], cols[1]
 
 
+def _stranded_setdiff(a: _Stranded, b: _Stranded) -> _Stranded:
+    """a minus b, each row cut only by rows of its own strand code (stranded_region_set.rs:138-217)"""
+    h, p = C.c_void_p(), C.c_void_p()
+    check(lib.gtars_regionset_stranded_setdiff(a.regions._h, ptr(a.strands), b.regions._h, ptr(b.strands), C.byref(h), C.byref(p)))
+    return _Stranded(RegionSet._from_handle(h), np.array(_take(p, C.c_uint8, int(lib.gtars_regionset_len(h))), dtype=np.uint8))
+
+
+def _reduce_all(rows: RegionSet, strand: np.ndarray) -> _Stranded:
+    return _stranded_reduce(rows, np.ascontiguousarray(strand, dtype=np.uint8), np.ones(len(rows), dtype=np.uint8))
+
+
+def _read_gtf_utrs(path, filter_protein_coding: bool, convert_ensembl_ucsc: bool):
+    h, ps, pk = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    st = lib.gtars_gtf_read_utrs(str(path).encode(), int(bool(filter_protein_coding)), int(bool(convert_ensembl_ucsc)),
+                                 C.byref(h), C.byref(ps), C.byref(pk))
+    if st != 0:
+        raise ValueError(_lib.last_error())
+    rows = RegionSet._from_handle(h)
+    n = len(rows)
+    return rows, np.array(_take(ps, C.c_uint8, n), dtype=np.uint8), np.array(_take(pk, C.c_uint8, n), dtype=np.uint8)
+
+
+def _bed_stranded(path, what: str) -> _Stranded:
+    """a BED file with the strand of column 6 (the third field of ``rest``; unstranded without one), stranded-reduced"""
+    try:
+        rs = RegionSet(str(path))
+    except Exception as e:
+        raise ValueError(f"Loading {what}: {e}") from None
+    code = np.full(len(rs), 2, dtype=np.uint8)
+    for i in range(len(rs)):
+        rest = dec(lib.gtars_regionset_rest(rs._h, i))
+        f = rest.split("\t") if rest is not None else []
+        if len(f) >= 3:
+            code[i] = {"+": 0, "-": 1}.get(f[2][:1], 2)
+    return _reduce_all(rs, code)
+
+
 class GeneModel:
-    """gtars.models.GeneModel -- genes and exons of a GTF, each merged by a strand-aware reduce.
+    """gtars.models.GeneModel -- genes, exons and the two UTR sets of a gene model, each merged by a strand-aware reduce.
 
     ``from_gtf`` reads the GTF on host threads (a malformed number or a line that is not UTF-8 raises ``ValueError``
-    before any device work) and reduces on the GPU.  The reader keeps UTR and CDS rows too, but they only feed the
-    reference's partitions (its ``PendingUtr`` / exon-minus-CDS UTR derivation), which are not provided here."""
+    before any device work) and reduces on the GPU.  ``three_utr`` / ``five_utr`` are ``None`` when the model has no
+    such rows: typed rows, else ``UTR`` rows classified against their transcript's CDS, else exon minus CDS."""
 
     def __init__(self, *args, **kwargs):
         raise TypeError("No constructor defined for GeneModel")
 
     @staticmethod
+    def _of(genes: _Stranded, exons: _Stranded, three: Optional[_Stranded], five: Optional[_Stranded]) -> "GeneModel":
+        self = GeneModel.__new__(GeneModel)
+        self._genes, self._exons = genes, exons
+        self._three_utr = three if three is not None and len(three) else None
+        self._five_utr = five if five is not None and len(five) else None
+        return self
+
+    @staticmethod
     def from_gtf(path: str, filter_protein_coding: bool = True, convert_ensembl_ucsc: bool = True) -> "GeneModel":
         rows, strand, feature = _read_gtf(path, filter_protein_coding, convert_ensembl_ucsc)
-        self = GeneModel.__new__(GeneModel)
-        self._genes = _stranded_reduce(rows, strand, feature == _GTF_GENE)
-        self._exons = _stranded_reduce(rows, strand, feature == _GTF_EXON)
-        return self
+        utr, ustrand, kind = _read_gtf_utrs(path, filter_protein_coding, convert_ensembl_ucsc)
+        three, five = (_stranded_reduce(utr, ustrand, kind == k) if (kind == k).any() else None for k in (0, 1))
+        return GeneModel._of(_stranded_reduce(rows, strand, feature == _GTF_GENE), _stranded_reduce(rows, strand, feature == _GTF_EXON),
+                             three, five)
+
+    @staticmethod
+    def from_bed_files(genes: str, exons: str, three_utr: Optional[str] = None, five_utr: Optional[str] = None) -> "GeneModel":
+        """partitions.rs:63-101: every file stranded-reduced, an empty UTR set is None"""
+        return GeneModel._of(_bed_stranded(genes, "genes"), _bed_stranded(exons, "exons"),
+                             _bed_stranded(three_utr, "3'UTR") if three_utr is not None else None,
+                             _bed_stranded(five_utr, "5'UTR") if five_utr is not None else None)
 
     @property
     def n_genes(self) -> int:
@@ -633,6 +687,14 @@ class GeneModel:
     @property
     def n_exons(self) -> int:
         return len(self._exons)
+
+    @property
+    def three_utr(self) -> Optional[RegionSet]:
+        return self._three_utr.regions if self._three_utr is not None else None
+
+    @property
+    def five_utr(self) -> Optional[RegionSet]:
+        return self._five_utr.regions if self._five_utr is not None else None
 
     def __repr__(self) -> str:
         return f"GeneModel(n_genes={self.n_genes}, n_exons={self.n_exons})"

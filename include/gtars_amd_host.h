@@ -167,6 +167,24 @@ gtars_status gtars_gtf_read(const char *path, int filter_protein_coding, int con
 gtars_status gtars_regionset_stranded_reduce(const gtars_regionset_t *rs, const uint8_t *strand, const uint8_t *keep,
                                              gtars_regionset_t **out, uint8_t **out_strand);
 
+/* StrandedRegionSet::setdiff (stranded_region_set.rs:138-217), on the current device: both sides stranded-reduced, then per
+ * (chr, strand) group of a the sweep of gtars_regionset_setdiff, so a row is only ever cut by rows of its own strand code.
+ * *out: a's reduced order, no rest; *out_strand (gtars_free) */
+gtars_status gtars_regionset_stranded_setdiff(const gtars_regionset_t *a, const uint8_t *a_strand, const gtars_regionset_t *b,
+                                              const uint8_t *b_strand, gtars_regionset_t **out, uint8_t **out_strand);
+/* The UTR rows of GeneModel::from_gtf before their reduce (partitions.rs:144-328), read and filtered as gtars_gtf_read does.
+ * Host only.  *out_kind: 0 three-prime, 1 five-prime.
+ *   - three_prime_utr / five_prime_utr rows as they are, strand from field 7 ('.' when empty), in file order; then
+ *   - every UTR row whose 9th field names a transcript (the text between the first `transcript_id "` and the next '"')
+ *     that has a CDS row: five-prime when mid(UTR) < mid(CDS bounds) on '+', when mid(UTR) > mid(CDS bounds) on any other
+ *     strand character, else three-prime; mid = (start + end) / 2 in u64, the CDS bounds are the smallest start and the
+ *     largest end of the transcript's CDS rows; the strand character is field 7's first, '+' when empty;
+ *   - only when neither gave a row: per exon row of a transcript with a CDS, [start, min(end, cds start)) when start <
+ *     cds start (three-prime on '-', else five-prime) and [max(start, cds end), end) when end > cds end (five-prime on '-',
+ *     else three-prime), in file order.  The reference emits these in hash-map order; every consumer reduces them. */
+gtars_status gtars_gtf_read_utrs(const char *path, int filter_protein_coding, int convert_ensembl_ucsc, gtars_regionset_t **out_rows,
+                                 uint8_t **out_strand, uint8_t **out_kind);
+
 typedef struct gtars_tss_index gtars_tss_index_t;
 /* TssIndex::try_from(RegionSet) (models.rs:525-549): a snapshot of rs; host only -- the device index (midpoints
  * start + (u32)(end - start) / 2 sorted per chromosome, duplicates kept) is built at the first distance call, on the
@@ -181,6 +199,55 @@ int gtars_tss_index_device(const gtars_tss_index_t *ix);   /* -1 until the first
  * nearest midpoint - query midpoint, the left neighbour on a tie, INT64_MAX on a chromosome the index lacks. */
 gtars_status gtars_tss_index_distances(gtars_tss_index_t *ix, const gtars_regionset_t *query, uint32_t *out_abs,
                                        int64_t *out_signed);
+
+/* ------------------------------------------------------------------------
+ * Genomic partitions  (gtars-genomicdist/src/partitions.rs:363-784; csrc/partitions.cpp, csrc/partitions.hip: K14)
+ *
+ * A partition list is an ordered list of named region sets (at most 255); the order is the priority.  The handle keeps
+ * a snapshot of the rows on one chromosome dictionary (names in order of first appearance over the sets).  Its device
+ * index is built at the first counting call, on the device current then, which the handle keeps: the host call runs
+ * there whatever the caller's current device is, the device-pointer call refuses another one.  Empty sets are legal.
+ * ---------------------------------------------------------------------- */
+typedef struct gtars_partition_list gtars_partition_list_t;
+gtars_status gtars_partition_list_from_sets(const char *const *names, const gtars_regionset_t *const *sets, uint32_t n,
+                                            gtars_partition_list_t **out);
+void gtars_partition_list_free(gtars_partition_list_t *pl);
+uint32_t gtars_partition_list_len(const gtars_partition_list_t *pl);
+const char *gtars_partition_list_name(const gtars_partition_list_t *pl, uint32_t i); /* NULL: out of range */
+uint32_t gtars_partition_list_n_chrom(const gtars_partition_list_t *pl);
+const char *gtars_partition_list_chrom_name(const gtars_partition_list_t *pl, uint32_t id);
+/* *out: a new region set with the rows of partition i in their order (no rest) */
+gtars_status gtars_partition_list_set(const gtars_partition_list_t *pl, uint32_t i, gtars_regionset_t **out);
+/* out[len]: per partition the u64 sum of (u32)(end - start), what calc_expected_partitions calls its size */
+gtars_status gtars_partition_list_sizes(const gtars_partition_list_t *pl, uint64_t *out);
+int gtars_partition_list_device(const gtars_partition_list_t *pl); /* -1 until the first counting call */
+/* calc_partitions (partitions.rs:493-592).  A row hits a query when row.start < q.end && row.end > q.start on the same
+ * chromosome name.  counts[len + 1], the last entry is "intergenic".
+ *   bp_proportion == 0: counts[p] = queries whose first hit partition in list order is p, counts[len] = queries
+ *       without a hit, *total = (u32)len(query); assignments (may be NULL): per query that bucket, in query order
+ *   bp_proportion != 0: counts[p] = sum over queries and the rows of p they hit of min(q.end, row.end) - max(q.start,
+ *       row.start) where positive, once per row hit; *total = sum of (u32)(q.end - q.start); both wrap in u32 as the
+ *       reference's release build does, and so does the sum of the counts that counts[len] = total.saturating_sub(sum)
+ *       takes.  assignments must be NULL.
+ * An empty query gives zero counts and total 0.
+ * gtars_partitions_count_device: the queries are n device rows, d_chrom ids of the list's dictionary (any other value:
+ * no hit), queued on `stream` (a hipStream_t) of the current device, which is drained before the call returns;
+ * d_assignments (may be NULL) is a device pointer to n bytes. */
+gtars_status gtars_partitions_count(gtars_partition_list_t *pl, const gtars_regionset_t *query, int bp_proportion,
+                                    uint32_t *counts, uint32_t *total, uint8_t *assignments);
+gtars_status gtars_partitions_count_device(gtars_partition_list_t *pl, const uint32_t *d_chrom, const uint32_t *d_start,
+                                           const uint32_t *d_end, uint64_t n, int bp_proportion, void *stream,
+                                           uint32_t *counts, uint32_t *total, uint8_t *d_assignments);
+/* The rows of calc_expected_partitions (partitions.rs:598-784) from observed[n_partitions + 1] (the last: intergenic),
+ * the partitions' sizes and the genome size, host f64 arithmetic.  The intergenic size is genome_size.saturating_sub(sum
+ * of sizes); expected = (size / genome_size) * total; log10_oe = -inf when observed == 0, else +inf when expected == 0,
+ * else log10(observed / expected); pvalue = 1 - P(0.5, chi / 2) with chi = (O - E)^2 / E + ((T - O) - (T - E))^2 / (T - E),
+ * 1.0 when T == 0, E == 0 or T - E == 0.  P is the reference's own regularized lower incomplete gamma: the series
+ * below a + 1 and one minus Lentz's continued fraction (clamped to [0, 1]) from there, both at most 199 terms with
+ * tolerance 1e-14 and floor 1e-30, over its Lanczos (g = 7, n = 9) ln_gamma.  Each output has n_partitions + 1 entries. */
+gtars_status gtars_partition_expected(const uint32_t *observed, const uint64_t *partition_bp, uint32_t n_partitions,
+                                      uint32_t total, uint64_t genome_size, double *expected, double *log10_oe,
+                                      double *pvalue);
 
 /* ------------------------------------------------------------------------
  * Coverage tracks  (gtars-uniwig, BED input: counting.rs:32-290, utils.rs:31-81, writing.rs:113-214)

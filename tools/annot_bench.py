@@ -56,7 +56,8 @@ def best_of(fn, reps):
 def write_gtf(path, n_genes, n_exons, rng):
     w = np.array([n for _, n in CHROMS], dtype=np.float64)
     gc = rng.choice(len(CHROMS), n_genes, p=w / w.sum())
-    gs = (rng.random(n_genes) * (np.array([n for _, n in CHROMS])[gc] - 200_000)).astype(np.int64) + 1
+    # (MT is shorter than the 200 kb margin: a gene drawn there starts at 1)
+    gs = np.maximum((rng.random(n_genes) * (np.array([n for _, n in CHROMS])[gc] - 200_000)).astype(np.int64), 0) + 1
     glen = rng.integers(500, 150_000, n_genes)
     gst = rng.choice(np.array(["+", "-"]), n_genes)
     pc = rng.random(n_genes) < 0.35
