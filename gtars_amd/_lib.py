@@ -159,6 +159,10 @@ _HOST_SIG = {
     "gtars_regionset_closest": (C.c_int, [vp, vp, pp, pp, pp, pu64]),
     "gtars_regionset_cluster": (C.c_int, [vp, u32, vp]),
     "gtars_regionset_pairwise_jaccard": (C.c_int, [vp, u64, vp]),
+    "gtars_regionset_list_union_all": (C.c_int, [vp, u64, pp]),
+    "gtars_regionset_list_intersect_all": (C.c_int, [vp, u64, pp]),
+    "gtars_regionset_list_union_except": (C.c_int, [vp, u64, u64, pp]),
+    "gtars_regionset_list_bulk_union_except": (C.c_int, [vp, u64, pp, pp]),
     "gtars_regionset_disjoin": (C.c_int, [vp, pp]),
     "gtars_regionset_gaps": (C.c_int, [vp, vp, vp, u64, pp]),
     "gtars_regionset_consensus": (C.c_int, [vp, u64, pp, pp]),

@@ -1100,6 +1100,115 @@ gtars_status gtars_regionset_pairwise_jaccard(const gtars_regionset_t *const *se
 
 }  // extern "C"
 
+// RegionSetListOps (gtars-genomicdist/src/region_set_list_ops.rs:103-181): the folds over a list.  "None" is GTARS_OK with a
+// NULL handle.  The lists the reference answers with a clone (one set; the other set of two for union_except) get an
+// unreduced copy, rest included, before any device call.
+namespace {
+
+template <class F>
+gtars_status with_list_cols(const gtars_regionset *const *sets, uint64_t n, F &&op) {
+    for (uint64_t k = 0; k < n; ++k)
+        if (!sets[k]) return fail(GTARS_ERR_INVALID_ARG, "NULL region set");
+    RankSpace sp;
+    sp.build_list(sets, n);
+    std::vector<std::vector<uint32_t>> ranks(n);
+    std::vector<gtars::SetCols> cols(n);
+    for (uint64_t k = 0; k < n; ++k) {
+        ranks[k] = sp.ranks_of(sets[k]);
+        cols[k] = cols_of(sets[k], ranks[k]);
+    }
+    return op(sp, cols);
+}
+
+template <class F>
+gtars_status list_fold(const gtars_regionset *const *sets, uint64_t n, gtars_regionset_t **out, F &&op) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out || (n && !sets)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        if (n == 0) return GTARS_OK;
+        if (n == 1) {
+            if (!sets[0]) return fail(GTARS_ERR_INVALID_ARG, "NULL region set");
+            *out = new gtars_regionset(*sets[0]);
+            return GTARS_OK;
+        }
+        return with_list_cols(sets, n, [&](const RankSpace &sp, const std::vector<gtars::SetCols> &cols) -> gtars_status {
+            gtars::SetOut o;
+            if (const gtars_status e = op(cols, sp.size(), o)) return e;
+            *out = regionset_from(sp, o);
+            return GTARS_OK;
+        });
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+gtars_status gtars_regionset_list_union_all(const gtars_regionset_t *const *sets, uint64_t n, gtars_regionset_t **out) {
+    return list_fold(sets, n, out, gtars::setops_list_union_all);
+}
+
+gtars_status gtars_regionset_list_intersect_all(const gtars_regionset_t *const *sets, uint64_t n, gtars_regionset_t **out) {
+    return list_fold(sets, n, out, gtars::setops_list_intersect_all);
+}
+
+gtars_status gtars_regionset_list_union_except(const gtars_regionset_t *const *sets, uint64_t n, uint64_t skip,
+                                               gtars_regionset_t **out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out || (n && !sets)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        if (n < 2 || skip >= n) return GTARS_OK;
+        if (n == 2) {
+            const gtars_regionset *other = sets[skip == 0 ? 1 : 0];
+            if (!sets[0] || !sets[1]) return fail(GTARS_ERR_INVALID_ARG, "NULL region set");
+            *out = new gtars_regionset(*other);
+            return GTARS_OK;
+        }
+        return with_list_cols(sets, n, [&](const RankSpace &sp, const std::vector<gtars::SetCols> &cols) -> gtars_status {
+            gtars::SetOut o;
+            if (const gtars_status e = gtars::setops_list_union_except(cols, sp.size(), skip, o)) return e;
+            *out = regionset_from(sp, o);
+            return GTARS_OK;
+        });
+    });
+}
+
+gtars_status gtars_regionset_list_bulk_union_except(const gtars_regionset_t *const *sets, uint64_t n, gtars_regionset_t **out_union,
+                                                    gtars_regionset_t ***out_except) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out_union || !out_except || (n && !sets)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_union = nullptr;
+        *out_except = nullptr;
+        if (n < 2) return GTARS_OK;
+        return with_list_cols(sets, n, [&](const RankSpace &sp, const std::vector<gtars::SetCols> &cols) -> gtars_status {
+            gtars::SetOut uni;
+            std::vector<gtars::SetOut> except;
+            if (n == 2) {
+                if (const gtars_status e = gtars::setops_list_union_all(cols, sp.size(), uni)) return e;
+            } else if (const gtars_status e = gtars::setops_list_bulk_union_except(cols, sp.size(), uni, except)) {
+                return e;
+            }
+            auto **arr = (gtars_regionset_t **)calloc((size_t)n, sizeof(gtars_regionset_t *));
+            if (!arr) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+            try {
+                for (uint64_t i = 0; i < n; ++i) {
+                    arr[i] = n == 2 ? new gtars_regionset(*sets[1 - i]) : regionset_from(sp, except[i]);
+                    if (n > 2) except[i] = gtars::SetOut();  // the columns now live in the set
+                }
+                *out_union = regionset_from(sp, uni);
+            } catch (...) {
+                for (uint64_t i = 0; i < n; ++i) delete arr[i];
+                free(arr);
+                throw;
+            }
+            *out_except = arr;
+            return GTARS_OK;
+        });
+    });
+}
+
+}  // extern "C"
+
 // ============================================================ structural operations and region-set statistics
 // disjoin / gaps (region_set.rs:786-1090), consensus (gtars-genomicdist/src/consensus.rs:29-68) and the statistics of
 // gtars-genomicdist/src/statistics.rs:88-316, computed by setops.hip (K9).  chrom_sizes arrive as parallel name / size

@@ -41,6 +41,15 @@ gtars_status setops_cluster(const SetCols &a, uint32_t n_rank, uint32_t max_gap,
 // RegionSetList::pairwise_jaccard: out[i * n + j] == reduce(S_i).jaccard(reduce(S_j)), 1.0 on the diagonal
 gtars_status setops_pairwise_jaccard(const std::vector<SetCols> &sets, uint32_t n_rank, double *out);
 
+// RegionSetListOps (gtars-genomicdist/src/region_set_list_ops.rs:103-181) for lists of >= 2 sets; the host layer answers
+// the shorter ones.  union_except: reduce of the concatenation of every set but `skip` (skip >= sets.size(): of all).
+gtars_status setops_list_union_all(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &out);
+gtars_status setops_list_union_except(const std::vector<SetCols> &sets, uint32_t n_rank, uint64_t skip, SetOut &out);
+// uni = reduce(concat), except[i] = reduce(concat without set i), all from one sort and one top-2-by-owner scan
+gtars_status setops_list_bulk_union_except(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &uni, std::vector<SetOut> &except);
+// the left fold of intersect: the stretches of positive length that every set's own reduce covers
+gtars_status setops_list_intersect_all(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &out);
+
 // GTARS_ERR_NO_DEVICE unless a device is visible (common.h)
 gtars_status require_device();
 

@@ -1,6 +1,7 @@
 // setops.hip -- K8: region-set algebra on the device (gtars-core/src/models/region_set.rs:675-1420,
 // gtars-genomicdist/src/region_set_list_ops.rs:20-45): reduce / union, setdiff / intersect, the bp totals behind
-// jaccard / coverage / overlap_coefficient, closest, cluster, and the pairwise Jaccard matrix of a list of sets.
+// jaccard / coverage / overlap_coefficient, closest, cluster, the pairwise Jaccard matrix of a list of sets, and the folds
+// over a list (union_all, intersect_all, union_except, bulk_union_except).
 //
 // Building blocks, all on the calling thread's current device and its null stream (drained on every exit):
 //   * the stable radix sort of sort.hip: (rank, start) for reduce and closest, (rank, start, end) for cluster;
@@ -16,6 +17,19 @@
 //   * pairwise Jaccard: all sets reduced in one pass (segments = set x chromosome), per-set prefix sums of widths, and
 //     for a pair the covered bp of S_j before p as one binary search: |S_i & S_j| = sum over x in S_i of
 //     F_j(x.end) - F_j(x.start).  One work list of (smaller set, other set, chunk) items covers every pair.
+//   * folds over a list (region_set_list_ops.rs:103-181; the second part of K8, after K9 in this file): union_all and
+//     union_except(i) are one reduce of the concatenation (without set i); bulk_union_except gives the union of all and
+//     every union_except(i) from one upload, one sort and one segmented scan whose value is the top two ends by owner
+//     (m1, the set s1 that attains it, m2 over the other sets): the running maximum without set i is s1 == i ? m2 : m1,
+//     reduce's rule is applied with it, and one workgroup per tile of sorted rows counts, then writes, the runs of every
+//     output set (a compare, a ballot and a popcount per set and 64 rows).  intersect_all reduces every set in one pass
+//     (segment = set x chromosome), drops the reduced regions with start >= end and sweeps the open / close events
+//     sorted by (rank, position): a stretch is emitted where the depth is the number of sets.  This is the reference's
+//     left fold exactly, inverted regions included, and needs no sequential path: in sweep_intersect_chr a region with
+//     start >= end yields no piece on either side (max(starts) >= min(ends)), it never hides a later region from the
+//     sweep (a's starts ascend, and a b region is skipped only once its end is at or below the current start), and the
+//     well-formed regions of a reduced set keep gaps >= 1 (each opened past every earlier end), so every step's result
+//     is sorted, separated and its own reduce;
 // Widths and totals are the reference's release-build u32 values: (u32)(end - start), summed modulo 2^32 (u64 on the
 // device, truncated), and the intersection is a_bp + b_bp - union_bp in wrapping u32.
 // K9 (the second half of the file) builds disjoin, gaps, consensus and the region-set statistics of gtars-genomicdist
@@ -1266,6 +1280,376 @@ gtars_status setops_chrom_stats(const SetCols &a, uint32_t n_rank, std::vector<C
     for (u32 r = 0; r < n_rank; ++r)
         if (h_cnt[r]) out[r] = ChromStat{h_cnt[r], h_min_s[r], h_max_e[r], h_min_w[r], h_max_w[r], h_mean[r], h_median[r]};
     return GTARS_OK;
+}
+
+// ============================================================ K8, second part: folds over a list of sets (RegionSetListOps)
+// union_all / union_except / bulk_union_except / intersect_all of gtars-genomicdist/src/region_set_list_ops.rs:103-181 for
+// lists of >= 2 sets (the host layer answers the shorter lists, which the reference returns as unreduced copies).
+// DESIGN.md §3 K8 "Folds over a list".
+namespace {
+
+// ------------------------------------------------------------------------------- top-2-by-owner segmented max-scan
+// The summary of a span of rows (end, set): m1 = the largest end, s1 = a set that attains it, m2 = the largest end among
+// the rows of every other set.  The running maximum without set i is then s1 == i ? m2 : m1.  Each maximum has a valid
+// bit of its own: an end of 0xFFFFFFFF is a value, not "none yet".
+struct T2 {
+    u32 f;  // T2_V1 | T2_V2 | T2_HEAD
+    u32 m1, s1, m2;
+};
+constexpr u32 T2_V1 = 1u, T2_V2 = 2u, T2_HEAD = 4u;  // m1 valid, m2 valid, a segment head lies in the span
+constexpr u32 T2_CHR = 4u;                           // in a stored row: the row opens a chromosome (or is the row past the end)
+constexpr u32 T2_CLS_SHIFT = 3;                      // in a stored row: 0 no head, 1 head for every set but its own, 2 head for s1 only
+
+__device__ __forceinline__ T2 t2_op(T2 a, T2 b) {
+    if (b.f & T2_HEAD) return b;
+    if (!(b.f & T2_V1)) return a;
+    const u32 head = a.f & T2_HEAD;
+    if (!(a.f & T2_V1)) return T2{b.f | head, b.m1, b.s1, b.m2};
+    if (a.s1 == b.s1) {
+        const u32 v2 = (a.f | b.f) & T2_V2;
+        const u32 m2 = (a.f & b.f & T2_V2) ? max(a.m2, b.m2) : (a.f & T2_V2) ? a.m2 : b.m2;
+        return T2{T2_V1 | v2 | head, max(a.m1, b.m1), a.s1, m2};
+    }
+    const bool bw = b.m1 > a.m1;  // the larger m1 wins; the loser's m1 is the largest end of its span, and not the winner's set
+    const T2 w = bw ? b : a, l = bw ? a : b;
+    return T2{T2_V1 | T2_V2 | head, w.m1, w.s1, (w.f & T2_V2) ? max(w.m2, l.m1) : l.m1};
+}
+__device__ __forceinline__ uint4 t2_pack(T2 a) { return make_uint4(a.f, a.m1, a.s1, a.m2); }
+__device__ __forceinline__ T2 t2_unpack(uint4 x) { return T2{x.x, x.y, x.z, x.w}; }
+__device__ __forceinline__ T2 t2_row(const u32 *__restrict__ seg, const u32 *__restrict__ end, const u32 *__restrict__ set, u64 i) {
+    return T2{T2_V1 | (is_head(seg, i) ? T2_HEAD : 0u), end[i], set[i], 0u};
+}
+
+// the 16-byte form of block_incl: lds[t] holds thread t's inclusive value afterwards
+template <int TPB>
+__device__ __forceinline__ T2 t2_block_incl(T2 x, uint4 *lds) {
+    const int t = threadIdx.x;
+    lds[t] = t2_pack(x);
+    __syncthreads();
+    for (int d = 1; d < TPB; d <<= 1) {
+        T2 y = x;
+        if (t >= d) y = t2_op(t2_unpack(lds[t - d]), x);
+        __syncthreads();
+        lds[t] = t2_pack(y);
+        x = y;
+        __syncthreads();
+    }
+    return x;
+}
+
+// a thread's SO_IPT rows folded in order; rows past n are the identity
+__device__ __forceinline__ T2 t2_thread(const u32 *__restrict__ seg, const u32 *__restrict__ end, const u32 *__restrict__ set, u32 n,
+                                        u64 base) {
+    T2 acc{0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < SO_IPT; ++k)
+        if (base + k < n) acc = t2_op(acc, t2_row(seg, end, set, base + k));
+    return acc;
+}
+
+__global__ void __launch_bounds__(SO_TPB)
+k_t2_tiles(const u32 *__restrict__ seg, const u32 *__restrict__ end, const u32 *__restrict__ set, u32 n, uint4 *__restrict__ agg) {
+    __shared__ uint4 lds[SO_TPB];
+    const u64 base = (u64)blockIdx.x * SO_TILE + (u64)threadIdx.x * SO_IPT;
+    const T2 acc = t2_block_incl<SO_TPB>(t2_thread(seg, end, set, n, base), lds);
+    if (threadIdx.x == SO_TPB - 1) agg[blockIdx.x] = t2_pack(acc);
+}
+
+// tile aggregates -> exclusive carries, in place (one workgroup)
+__global__ void __launch_bounds__(1024) k_t2_carry(uint4 *__restrict__ agg, u32 n_tiles) {
+    __shared__ uint4 lds[1024];
+    T2 run{0, 0, 0, 0};
+    for (u32 b = 0; b < n_tiles; b += 1024) {
+        const u32 t = b + threadIdx.x;
+        const T2 x = t < n_tiles ? t2_unpack(agg[t]) : T2{0, 0, 0, 0};
+        (void)t2_block_incl<1024>(x, lds);
+        const T2 ex = threadIdx.x ? t2_op(run, t2_unpack(lds[threadIdx.x - 1])) : run;
+        const T2 last = t2_unpack(lds[1023]);
+        __syncthreads();
+        if (t < n_tiles) agg[t] = t2_pack(ex);
+        run = t2_op(run, last);
+    }
+}
+
+// rows[k], k in [0, n]: the summary of the rows from the head of row k - 1's chromosome to row k - 1, whether row k opens
+// a chromosome (row n, past the end, does), and for which sets row k opens a run of "the union without that set":
+// reduce()'s rule start > (running max of end over the chromosome so far) with the maximum taken without the set.
+// m2 <= m1, so a row past m1 is a head for every set but its own, and a row in (m2, m1] for s1 alone.
+__global__ void __launch_bounds__(SO_TPB)
+k_t2_apply(const u32 *__restrict__ seg, const u32 *__restrict__ start, const u32 *__restrict__ end, const u32 *__restrict__ set, u32 n,
+           const uint4 *__restrict__ carry, uint4 *__restrict__ rows) {
+    __shared__ uint4 lds[SO_TPB];
+    const u64 base = (u64)blockIdx.x * SO_TILE + (u64)threadIdx.x * SO_IPT;
+    (void)t2_block_incl<SO_TPB>(t2_thread(seg, end, set, n, base), lds);
+    T2 run = t2_unpack(carry[blockIdx.x]);
+    if (threadIdx.x) run = t2_op(run, t2_unpack(lds[threadIdx.x - 1]));
+#pragma unroll
+    for (int k = 0; k < SO_IPT; ++k) {
+        const u64 i = base + k;
+        if (i > n) break;
+        const bool chr = i == n || is_head(seg, i);
+        u32 cls = 0;
+        if (i < n) {
+            const u32 s = start[i];
+            if (chr || !(run.f & T2_V1) || s > run.m1) cls = 1;
+            else if (set[i] != run.s1 && (!(run.f & T2_V2) || s > run.m2)) cls = 2;
+        }
+        rows[i] = make_uint4((run.f & (T2_V1 | T2_V2)) | (chr ? T2_CHR : 0u) | (cls << T2_CLS_SHIFT), run.m1, run.s1, run.m2);
+        if (i < n) run = t2_op(run, t2_row(seg, end, set, i));
+    }
+}
+
+__global__ void k_gather1(const u32 *__restrict__ perm, u32 n, const u32 *__restrict__ a, u32 *__restrict__ oa) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) oa[i] = a[perm[i]];
+}
+
+// One workgroup per tile of the sorted rows [0, n]; each wave takes the output sets i = wave, wave + 4, ... < n_out (set
+// n_out - 1 owns no row: the union of all) and walks the tile 64 rows at a time: a compare, a ballot and a popcount per
+// step.  !WRITE: cnt[i * tiles + tile] = the heads of set i in the tile.  WRITE: head number p of set i (off: the
+// exclusive scan of cnt, so set i's runs are one slice of the output) gets its rank, start and own end, and the row
+// that ends run p - 1 -- the next head of the chromosome, or the row that opens the next chromosome -- writes the running
+// maximum without i up to it into oclose[p - 1].  k_ue_finish picks between the two ends.
+template <bool WRITE>
+__global__ void __launch_bounds__(SO_TPB)
+k_ue_emit(const uint4 *__restrict__ rows, const u32 *__restrict__ sset, const u32 *__restrict__ seg, const u32 *__restrict__ start,
+          const u32 *__restrict__ end, u32 n, u32 n_out, u32 tiles, u32 *__restrict__ cnt, const u64 *__restrict__ off,
+          u32 *__restrict__ oseg, u32 *__restrict__ ostart, u32 *__restrict__ oend, u32 *__restrict__ oclose) {
+    __shared__ u32 l_f[SO_TILE], l_m1[SO_TILE], l_s1[SO_TILE], l_m2[SO_TILE], l_own[SO_TILE];
+    const u64 t0 = (u64)blockIdx.x * SO_TILE;
+    for (u32 j = threadIdx.x; j < SO_TILE; j += SO_TPB) {
+        const u64 k = t0 + j;
+        const uint4 e = k <= n ? rows[k] : make_uint4(0, 0, 0, 0);
+        l_f[j] = e.x;
+        l_m1[j] = e.y;
+        l_s1[j] = e.z;
+        l_m2[j] = e.w;
+        l_own[j] = k < n ? sset[k] : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 live = (u32)min((u64)SO_TILE, (u64)n + 1 - t0), chunks = (live + 63) / 64;
+    for (u32 i = wave; i < n_out; i += SO_TPB / 64) {
+        const u64 base = WRITE ? off[(u64)i * tiles + blockIdx.x] : 0;
+        u32 c = 0;
+        for (u32 ch = 0; ch < chunks; ++ch) {
+            const u32 j = ch * 64 + lane;
+            const u32 f = l_f[j], s1 = l_s1[j], cls = (f >> T2_CLS_SHIFT) & 3u;
+            const bool head = (cls == 1 && l_own[j] != i) || (cls == 2 && s1 == i);
+            const u64 b = __ballot(head);
+            if (WRITE) {
+                const u64 p = base + c + __popcll(b & ((1ull << lane) - 1ull));
+                if (head) {
+                    const u64 k = t0 + j;
+                    oseg[p] = seg[k];
+                    ostart[p] = start[k];
+                    oend[p] = end[k];
+                }
+                if ((head || (f & T2_CHR)) && (f & (s1 == i ? T2_V2 : T2_V1))) oclose[p - 1] = s1 == i ? l_m2[j] : l_m1[j];
+            }
+            c += (u32)__popcll(b);
+        }
+        if (!WRITE && lane == 0) cnt[(u64)i * tiles + blockIdx.x] = c;
+    }
+}
+
+// A run whose head is inverted (start > end) has one row and ends at its own end; every other run ends at the running
+// maximum at its last row (the earlier runs of the chromosome ended below its start).
+__global__ void k_ue_finish(const u32 *__restrict__ ostart, u32 *__restrict__ oend, const u32 *__restrict__ oclose, u64 m) {
+    for (u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (u64)gridDim.x * blockDim.x)
+        if (ostart[p] <= oend[p]) oend[p] = oclose[p];
+}
+
+// out[i] = off[i * tiles], i in [0, n_out]
+__global__ void k_ue_slices(const u64 *__restrict__ off, u32 tiles, u32 n_out, u64 *__restrict__ out) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i <= n_out; i += (u64)gridDim.x * blockDim.x) out[i] = off[i * tiles];
+}
+
+// ------------------------------------------------------------------------------------------------- intersect_all
+// events 2i and 2i + 1: the start and the end of reduced region i (segment = set * nr + rank).  A region that is not
+// well-formed (start >= end) never yields a piece of an intersect sweep: its events go to the rank past the last.
+__global__ void k_ia_events(const u32 *__restrict__ seg, const u32 *__restrict__ start, const u32 *__restrict__ end, u32 n, u32 nr,
+                            u32 *__restrict__ ev_rank, u32 *__restrict__ ev_pos) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        ev_rank[2 * i] = ev_rank[2 * i + 1] = start[i] < end[i] ? seg[i] % nr : nr;
+        ev_pos[2 * i] = start[i];
+        ev_pos[2 * i + 1] = end[i];
+    }
+}
+
+// piece [pos[j], pos[j + 1]) when j is the last event at its position, the next event is on the same chromosome and
+// every set covers the stretch: the depth after j (opens minus closes so far) is n_sets
+template <bool WRITE>
+__global__ void k_ia_pieces(const u32 *__restrict__ srank, const u32 *__restrict__ spos, const u64 *__restrict__ co,
+                            const u64 *__restrict__ cc, u32 m, u32 nr, u64 n_sets, u32 *__restrict__ keep,
+                            const u64 *__restrict__ off, u32 *__restrict__ orank, u32 *__restrict__ ostart, u32 *__restrict__ oend) {
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (u64)gridDim.x * blockDim.x) {
+        const bool k = j + 1 < m && srank[j] < nr && srank[j + 1] == srank[j] && spos[j + 1] != spos[j] &&
+                       co[j + 1] - cc[j + 1] == n_sets;
+        if (!WRITE) {
+            keep[j] = k;
+        } else if (k) {
+            const u64 o = off[j];
+            orank[o] = srank[j];
+            ostart[o] = spos[j];
+            oend[o] = spos[j + 1];
+        }
+    }
+}
+
+// the concatenation of the sets but `skip` (none: sets.size()) on the device, and its size checked
+gtars_status list_concat(StreamFrame &fr, const std::vector<SetCols> &sets, size_t skip, DevSet &C) {
+    std::vector<SetCols> parts;
+    for (size_t k = 0; k < sets.size(); ++k)
+        if (k != skip) parts.push_back(sets[k]);
+    return upload_concat(fr, parts.data(), parts.size(), C);
+}
+
+u64 list_rows(const std::vector<SetCols> &sets) {
+    u64 n = 0;
+    for (const SetCols &s : sets) n += s.n;
+    return n;
+}
+
+}  // namespace
+
+gtars_status setops_list_union_except(const std::vector<SetCols> &sets, uint32_t n_rank, uint64_t skip, SetOut &res) {
+    res = SetOut();
+    const u64 n = list_rows(sets) - (skip < sets.size() ? sets[skip].n : 0);
+    GT_TRY(check_sizes(n, n_rank));
+    if (!n) return GTARS_OK;
+    StreamFrame fr(nullptr);
+    DevSet C, R;
+    GT_TRY(list_concat(fr, sets, skip, C));
+    GT_TRY(dev_reduce(fr, C, n_rank, R));
+    GT_TRY(download(fr, R, res));
+    return fr.drain();
+}
+
+gtars_status setops_list_union_all(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &res) {
+    return setops_list_union_except(sets, n_rank, sets.size(), res);
+}
+
+gtars_status setops_list_bulk_union_except(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &uni, std::vector<SetOut> &except) {
+    const u64 n64 = list_rows(sets), n_sets = sets.size();
+    uni = SetOut();
+    except.assign(n_sets, SetOut());
+    GT_TRY(check_sizes(n64, n_rank));
+    // one row of counts per output set (every set, and the union of all) and tile of the rows [0, n]
+    const u64 tiles64 = n64 / SO_TILE + 1;
+    if ((n_sets + 1) * tiles64 > SO_MAX_N)
+        return fail(GTARS_ERR_INVALID_ARG, "too many region sets x regions for one bulk_union_except call (" + std::to_string(n_sets) +
+                                               " sets, " + std::to_string(n64) + " regions)");
+    if (!n64) return GTARS_OK;
+    const u32 n = (u32)n64, tiles = (u32)tiles64, n_out = (u32)n_sets + 1;
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
+    // the concatenation with each row's set, sorted once by (rank, start)
+    DevSet C, S;
+    u32 *set, *sset, *perm;
+    GT_TRY(upload_concat(fr, sets.data(), n_sets, C));
+    GT_TRY(fr.alloc(&set, n));
+    u64 at = 0;
+    for (u32 k = 0; k < n_sets; ++k) {
+        if (sets[k].n) hipLaunchKernelGGL(k_fill, dim3(grid_for(sets[k].n)), dim3(256), 0, st, set + at, (u32)sets[k].n, k);
+        at += sets[k].n;
+    }
+    GT_TRY(sorted_set(fr, C, C.seg, nullptr, n_rank, S, &perm));
+    GT_TRY(fr.alloc(&sset, n));
+    hipLaunchKernelGGL(k_gather1, dim3(grid_for(n)), dim3(256), 0, st, perm, n, set, sset);
+    // the top-2 scan, left per row
+    uint4 *agg, *rows;
+    GT_TRY(fr.alloc(&agg, tiles));
+    GT_TRY(fr.alloc(&rows, (size_t)n + 1));
+    hipLaunchKernelGGL(k_t2_tiles, dim3(tiles), dim3(SO_TPB), 0, st, S.seg, S.end, sset, n, agg);
+    hipLaunchKernelGGL(k_t2_carry, dim3(1), dim3(1024), 0, st, agg, tiles);
+    hipLaunchKernelGGL(k_t2_apply, dim3(tiles), dim3(SO_TPB), 0, st, S.seg, S.start, S.end, sset, n, agg, rows);
+    // count / scan / write, every output set in one launch
+    u32 *cnt;
+    const u64 n_cnt = (u64)n_out * tiles;
+    GT_TRY(fr.alloc(&cnt, n_cnt));
+    hipLaunchKernelGGL(k_ue_emit<false>, dim3(tiles), dim3(SO_TPB), 0, st, rows, sset, S.seg, S.start, S.end, n, n_out, tiles, cnt, nullptr,
+                       nullptr, nullptr, nullptr, nullptr);
+    GT_HIP(hipGetLastError());
+    u64 *off, m = 0, *d_slice;
+    GT_TRY(scan_total(fr, cnt, n_cnt, &off, &m));
+    if (m > SO_MAX_N) return fail(GTARS_ERR_CAPACITY, "bulk_union_except result too large: need " + std::to_string(m) + " regions");
+    u32 *oseg, *ostart, *oend, *oclose;
+    GT_TRY(fr.alloc(&oseg, m));
+    GT_TRY(fr.alloc(&ostart, m));
+    GT_TRY(fr.alloc(&oend, m));
+    GT_TRY(fr.alloc(&oclose, m));
+    hipLaunchKernelGGL(k_ue_emit<true>, dim3(tiles), dim3(SO_TPB), 0, st, rows, sset, S.seg, S.start, S.end, n, n_out, tiles, nullptr, off,
+                       oseg, ostart, oend, oclose);
+    hipLaunchKernelGGL(k_ue_finish, dim3(grid_for(m)), dim3(256), 0, st, ostart, oend, oclose, m);
+    GT_TRY(fr.alloc(&d_slice, (size_t)n_out + 1));
+    hipLaunchKernelGGL(k_ue_slices, dim3(grid_for((u64)n_out + 1)), dim3(256), 0, st, off, tiles, n_out, d_slice);
+    GT_HIP(hipGetLastError());
+    std::vector<u64> slice;
+    GT_TRY(fr.download(slice, d_slice, (size_t)n_out + 1));
+    GT_TRY(fr.drain());
+    for (u32 i = 0; i < n_out; ++i) {
+        SetOut &o = i < n_sets ? except[i] : uni;
+        const u64 lo = slice[i], k = slice[i + 1] - lo;
+        GT_TRY(fr.download(o.rank, oseg + lo, k));
+        GT_TRY(fr.download(o.start, ostart + lo, k));
+        GT_TRY(fr.download(o.end, oend + lo, k));
+    }
+    return fr.drain();
+}
+
+gtars_status setops_list_intersect_all(const std::vector<SetCols> &sets, uint32_t n_rank, SetOut &res) {
+    const u64 n = list_rows(sets), n_sets = sets.size();
+    res = SetOut();
+    GT_TRY(check_sizes(2 * n, n_rank));
+    const u32 nr = std::max<u32>(n_rank, 1);
+    if (n_sets * nr > 0x7FFFFFFFull) return fail(GTARS_ERR_INVALID_ARG, "too many sets x chromosomes for one intersect_all call");
+    for (const SetCols &s : sets)
+        if (!s.n) return GTARS_OK;  // nothing is in an empty set
+    if (!n_sets) return GTARS_OK;
+    StreamFrame fr(nullptr);
+    hipStream_t st = fr.st;
+    // every set reduced in one pass: segment = set * nr + chromosome rank, as the pairwise matrix does
+    std::vector<u32> hseg(n);
+    DevSet C, R, O;
+    C.n = (u32)n;
+    GT_TRY(fr.alloc(&C.start, n));
+    GT_TRY(fr.alloc(&C.end, n));
+    u64 at = 0;
+    for (u64 k = 0; k < n_sets; ++k) {
+        const SetCols &s = sets[k];
+        for (u64 i = 0; i < s.n; ++i) hseg[at + i] = (u32)k * nr + s.rank[i];
+        GT_TRY(fr.upload_to(C.start + at, s.start, s.n));
+        GT_TRY(fr.upload_to(C.end + at, s.end, s.n));
+        at += s.n;
+    }
+    GT_TRY(fr.upload(&C.seg, hseg.data(), n));
+    GT_TRY(dev_reduce(fr, C, (u32)(n_sets * nr), R));
+    // the open / close events of the well-formed reduced regions by (rank, position), and the depth along them
+    const u32 m = 2 * R.n;
+    u32 *ev_rank, *ev_pos, *perm, *srank, *spos, *opens, *closes, *keep;
+    GT_TRY(fr.alloc(&ev_rank, m));
+    GT_TRY(fr.alloc(&ev_pos, m));
+    hipLaunchKernelGGL(k_ia_events, dim3(grid_for(R.n)), dim3(256), 0, st, R.seg, R.start, R.end, R.n, nr, ev_rank, ev_pos);
+    GT_TRY(sort_perm(fr, ev_rank, ev_pos, nullptr, m, nr + 1, &perm));
+    GT_TRY(fr.alloc(&srank, m));
+    GT_TRY(fr.alloc(&spos, m));
+    GT_TRY(fr.alloc(&opens, m));
+    GT_TRY(fr.alloc(&closes, m));
+    hipLaunchKernelGGL(k_dj_gather, dim3(grid_for(m)), dim3(256), 0, st, perm, m, ev_rank, ev_pos, R.start, R.end, srank, spos, opens,
+                       closes);
+    u64 *co, *cc, *off, t = 0, k = 0;
+    GT_TRY(scan_total(fr, opens, m, &co, &t));
+    GT_TRY(scan_total(fr, closes, m, &cc, &t));
+    GT_TRY(fr.alloc(&keep, m));
+    hipLaunchKernelGGL(k_ia_pieces<false>, dim3(grid_for(m)), dim3(256), 0, st, srank, spos, co, cc, m, nr, n_sets, keep, nullptr, nullptr,
+                       nullptr, nullptr);
+    GT_TRY(scan_total(fr, keep, m, &off, &k));
+    GT_TRY(alloc_set(fr, k, O));
+    hipLaunchKernelGGL(k_ia_pieces<true>, dim3(grid_for(m)), dim3(256), 0, st, srank, spos, co, cc, m, nr, n_sets, nullptr, off, O.seg,
+                       O.start, O.end);
+    GT_HIP(hipGetLastError());
+    GT_TRY(download(fr, O, res));
+    return fr.drain();
 }
 
 }  // namespace gtars

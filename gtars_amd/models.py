@@ -490,6 +490,92 @@ class RegionSetList:
         check(lib.gtars_regionset_pairwise_jaccard(C.cast(handles, C.c_void_p), n, ptr(out)))
         return out.tolist()
 
+    # -- RegionSetListOps (gtars-genomicdist/src/region_set_list_ops.rs:53-182) ------------------------------------
+    # The folds run on the GPU (csrc/setops.hip): one upload and one sort of the concatenation.  What the reference
+    # answers without a union -- None, and the clones it returns for one set (or for the other set of two) -- is
+    # answered here on the host, before any device call.
+    def _pair(self, i: int, j: int) -> Optional[Tuple[RegionSet, RegionSet]]:
+        """the reference's indices are usize: a negative index is out of range"""
+        n = len(self._sets)
+        return (self._sets[i], self._sets[j]) if 0 <= i < n and 0 <= j < n else None
+
+    def _handles(self):
+        return C.cast((C.c_void_p * max(len(self._sets), 1))(*[s._h for s in self._sets]), C.c_void_p)
+
+    @staticmethod
+    def _clone(s: RegionSet) -> RegionSet:
+        """the set as it is: rows in their order, unmerged, rest and strands kept"""
+        regs = s.regions
+        return RegionSet._from_columns([r.chr for r in regs], [r.start for r in regs], [r.end for r in regs],
+                                       [r.rest for r in regs], s._strands)
+
+    def pintersect_at(self, i: int, j: int) -> Optional[RegionSet]:
+        p = self._pair(i, j)
+        return None if p is None else p[0].pintersect(p[1])
+
+    def pintersect_count(self, i: int, j: int) -> Optional[int]:
+        r = self.pintersect_at(i, j)
+        return None if r is None else len(r)
+
+    def jaccard_at(self, i: int, j: int) -> Optional[float]:
+        p = self._pair(i, j)
+        return None if p is None else p[0].jaccard(p[1])
+
+    def union_at(self, i: int, j: int) -> Optional[RegionSet]:
+        p = self._pair(i, j)
+        return None if p is None else p[0].union(p[1])
+
+    def setdiff_at(self, i: int, j: int) -> Optional[RegionSet]:
+        p = self._pair(i, j)
+        return None if p is None else p[0].setdiff(p[1])
+
+    def region_count(self, i: int) -> Optional[int]:
+        return len(self._sets[i]) if 0 <= i < len(self._sets) else None
+
+    def _fold(self, fn) -> Optional[RegionSet]:
+        n = len(self._sets)
+        if n == 0:
+            return None
+        if n == 1:
+            return self._clone(self._sets[0])
+        h = C.c_void_p()
+        check(fn(self._handles(), n, C.byref(h)))
+        return RegionSet._from_handle(h)
+
+    def union_all(self) -> Optional[RegionSet]:
+        """reduce of the concatenation of every set; one set: that set, unmerged; no set: None"""
+        return self._fold(lib.gtars_regionset_list_union_all)
+
+    def intersect_all(self) -> Optional[RegionSet]:
+        """the left fold of intersect: what every set's own reduce covers; one set: that set, unmerged; no set: None"""
+        return self._fold(lib.gtars_regionset_list_intersect_all)
+
+    def union_except(self, skip: int) -> Optional[RegionSet]:
+        """reduce of the concatenation of every set but ``skip``; of two sets: the other one, unmerged"""
+        n = len(self._sets)
+        if n < 2 or not 0 <= skip < n:
+            return None
+        if n == 2:
+            return self._clone(self._sets[1 - skip])
+        h = C.c_void_p()
+        check(lib.gtars_regionset_list_union_except(self._handles(), n, skip, C.byref(h)))
+        return RegionSet._from_handle(h)
+
+    def bulk_union_except(self) -> Optional[Tuple[RegionSet, List[RegionSet]]]:
+        """(union_all(), [union_except(i) for every i]) from one upload, one sort and one scan on the device"""
+        n = len(self._sets)
+        if n < 2:
+            return None
+        if n == 2:
+            return self.union_all(), [self._clone(self._sets[1]), self._clone(self._sets[0])]
+        h, arr = C.c_void_p(), C.c_void_p()
+        check(lib.gtars_regionset_list_bulk_union_except(self._handles(), n, C.byref(h), C.byref(arr)))
+        try:
+            hs = C.cast(arr, C.POINTER(C.c_void_p))
+            return RegionSet._from_handle(h), [RegionSet._from_handle(C.c_void_p(hs[i])) for i in range(n)]
+        finally:
+            lib.gtars_free(arr)
+
 
 # ---------------------------------------------------------------------------------------------------------------------
 # TSS / feature distances and gene models (gtars-genomicdist/src/models.rs:516-690, partitions.rs:123-340,

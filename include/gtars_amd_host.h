@@ -101,6 +101,23 @@ gtars_status gtars_regionset_cluster(const gtars_regionset_t *rs, uint32_t max_g
 /* RegionSetList::pairwise_jaccard (gtars-genomicdist/src/region_set_list_ops.rs:20-45): out[i * n + j] =
  * reduce(S_i).jaccard(reduce(S_j)), 1.0 on the diagonal; every pair in one device pass */
 gtars_status gtars_regionset_pairwise_jaccard(const gtars_regionset_t *const *sets, uint64_t n, double *out);
+/* RegionSetListOps (region_set_list_ops.rs:103-181): the folds over a list of n sets.  "None" is GTARS_OK with *out == NULL.
+ * Results of a device fold are plain sets in bytewise chromosome order; where the reference returns a clone the result is
+ * an unreduced copy of that set, rest included, made on the host.
+ * union_all: NULL when n == 0; the copy of the set when n == 1; else reduce(concat of all sets).
+ * intersect_all: NULL when n == 0; the copy when n == 1; else the left fold of intersect (each step reduces both
+ * operands): the stretches of positive length that every set's own reduce covers.
+ * union_except: NULL when n < 2 or skip >= n; the copy of the other set when n == 2; else reduce(concat of every set but
+ * skip).
+ * bulk_union_except: both NULL when n < 2; else *out_union = union_all and (*out_except)[i] = union_except(i), from one
+ * upload, one sort and one scan.  *out_except: n handles, each released with gtars_regionset_free, then the array with
+ * gtars_free. */
+gtars_status gtars_regionset_list_union_all(const gtars_regionset_t *const *sets, uint64_t n, gtars_regionset_t **out);
+gtars_status gtars_regionset_list_intersect_all(const gtars_regionset_t *const *sets, uint64_t n, gtars_regionset_t **out);
+gtars_status gtars_regionset_list_union_except(const gtars_regionset_t *const *sets, uint64_t n, uint64_t skip,
+                                               gtars_regionset_t **out);
+gtars_status gtars_regionset_list_bulk_union_except(const gtars_regionset_t *const *sets, uint64_t n,
+                                                    gtars_regionset_t **out_union, gtars_regionset_t ***out_except);
 
 /* ------------------------------------------------------------------------
  * Structural operations and region-set statistics (gtars-core region_set.rs,

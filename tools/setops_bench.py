@@ -1,12 +1,21 @@
 """Region-set algebra (csrc/setops.hip) on the device vs the plain-Python restatement (tests/setops_ref.py).
 
   python tools/setops_bench.py [--sets 200] [--set-regions 50000] [--big 10000000] [--reps 3] [--json out.json]
+                               [--fold-sets 64] [--fold-set-regions 200000] [--only folds|algebra]
 
 Device figures are wall times of one library call (host columns in, host results out, the stream drained), the best of
 --reps after a warm-up call.  pairwise_jaccard runs on --sets x --set-regions synth.py query sets; reduce / closest / cluster
 on --big synth.py regions (closest against a quarter as many).  The CPU restatement is pure Python: it is timed on a
 smaller share of the same work (--cpu-big regions, --cpu-sets sets) and its results are compared with the device's there;
 at full size the device results are checked against numpy restatements (reduce, cluster) and sampled pairs.
+
+The folds over a list (RegionSetList.union_all / intersect_all / bulk_union_except) run on the --sets x --set-regions sets
+and on --fold-sets x --fold-set-regions.  Each is timed (one call, results as RegionSets on the host) next to the same
+answer from a Python fold of RegionSet.union / RegionSet.intersect_all through the library, in the same process: N - 1
+calls for union_all and intersect_all, the prefix / suffix scheme of 3 N unions for bulk_union_except.  Every device
+output must equal the fold's, union_all must equal a numpy reduce of the concatenation, and sampled union_except(i) must
+equal a numpy reduce of the other sets' rows, overlap every row of theirs and have no region that misses them all
+(any_overlaps).  The JSON is rewritten after every stage, so a run that is cut short leaves what it measured.
 """
 from __future__ import annotations
 
@@ -70,6 +79,97 @@ def tuples(q, n=None):
     return [(synth.CHROM_NAMES[int(q["chrom"][i])], int(q["start"][i]), int(q["end"][i])) for i in range(n)]
 
 
+def same_set(a, b):
+    return a.chrom_names == b.chrom_names and all(np.array_equal(x, y) for x, y in
+                                                  ((a.chrom_ids, b.chrom_ids), (a.starts, b.starts), (a.ends, b.ends)))
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return out, (time.perf_counter() - t0) * 1e3
+
+
+def fold_union_all(sets):
+    acc = sets[0]
+    for s in sets[1:]:
+        acc = acc.union(s)
+    return acc
+
+
+def fold_intersect_all(sets):
+    acc = sets[0]
+    for s in sets[1:]:
+        acc = acc.intersect_all(s)
+    return acc
+
+
+def fold_bulk_union_except(sets):
+    """the prefix / suffix scheme: about 3 N unions of growing sets"""
+    n = len(sets)
+    prefix = [sets[0]]
+    for i in range(1, n):
+        prefix.append(prefix[-1].union(sets[i]))
+    suffix = [None] * n
+    suffix[n - 1] = sets[n - 1]
+    for i in range(n - 2, -1, -1):
+        suffix[i] = sets[i].union(suffix[i + 1])
+    ex = [suffix[1]] + [prefix[i - 1].union(suffix[i + 1]) for i in range(1, n - 1)] + [prefix[n - 2]]
+    return prefix[n - 1], ex
+
+
+def bench_folds(res, tag, cols, sets, reps, flush):
+    """union_all / intersect_all / bulk_union_except of one list: device call vs Python fold, every output checked"""
+    rsl = RegionSetList(sets)
+    n, shape = len(sets), f"{len(sets)} sets x {len(sets[0])} regions"
+    dev, fold, chk = res["device"], res["library_fold"], res["checks"]
+    rank = np.concatenate([byte_rank(c["chrom"]) for c in cols]).astype(np.int64)
+    start, end = (np.concatenate([c[k] for c in cols]).astype(np.int64) for k in ("start", "end"))
+    owner = np.repeat(np.arange(n), [len(c["chrom"]) for c in cols])
+    o = np.lexsort((start, rank))
+    rank, start, end, owner = rank[o], start[o], end[o], owner[o]
+    names_sorted = sorted(synth.CHROM_NAMES)
+
+    def equals_numpy(got, keep):
+        r, s, e = np_reduce(rank[keep], start[keep], end[keep])  # (rows already sorted: the lexsort is stable)
+        gr = np.array([names_sorted.index(nm) for nm in got.chrom_names], dtype=np.int64)[got.chrom_ids]
+        return np.array_equal(gr, r) and np.array_equal(got.starts, s) and np.array_equal(got.ends, e)
+
+    # union_all
+    dev[f"union_all_ms_{tag}"] = best_of(rsl.union_all, reps)
+    want, fold[f"union_all_ms_{tag}"] = timed(lambda: fold_union_all(sets))
+    got = rsl.union_all()
+    assert same_set(got, want) and equals_numpy(got, np.ones(len(owner), dtype=bool))
+    chk[f"union_all_{tag}"] = f"{len(got)} regions == fold == numpy reduce"
+    flush()
+    # intersect_all
+    dev[f"intersect_all_ms_{tag}"] = best_of(rsl.intersect_all, reps)
+    want, fold[f"intersect_all_ms_{tag}"] = timed(lambda: fold_intersect_all(sets))
+    got = rsl.intersect_all()
+    assert same_set(got, want)
+    assert len(got) == 0 or all(all(got.any_overlaps(s)) for s in sets[:: max(1, n // 4)])
+    chk[f"intersect_all_{tag}"] = f"{len(got)} regions == fold, each inside every sampled set"
+    flush()
+    del got, want
+    # bulk_union_except
+    dev[f"bulk_union_except_ms_{tag}"] = best_of(rsl.bulk_union_except, max(1, reps - 1))
+    full, ex = rsl.bulk_union_except()
+    (wfull, wex), fold[f"bulk_union_except_ms_{tag}"] = timed(lambda: fold_bulk_union_except(sets))
+    assert same_set(full, wfull) and all(same_set(g, w) for g, w in zip(ex, wex))
+    del wfull, wex
+    sample = sorted({0, n // 3, n - 1})
+    for i in sample:
+        assert equals_numpy(ex[i], owner != i), i
+        keep = np.flatnonzero(owner != i)
+        others = RegionSet.from_vectors([names_sorted[r] for r in rank[keep].tolist()], start[keep], end[keep])
+        assert all(ex[i].any_overlaps(others)) and all(others.any_overlaps(ex[i])), i
+    chk[f"bulk_union_except_{tag}"] = (f"{n} sets of {min(map(len, ex))}..{max(map(len, ex))} regions == fold; {sample} == numpy "
+                                       "reduce of the other sets, any_overlaps both ways")
+    for k in ("device", "library_fold"):
+        res[k][f"folds_shape_{tag}"] = shape
+    flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", type=int, default=200)
@@ -79,9 +179,28 @@ def main():
     ap.add_argument("--cpu-sets", type=int, default=8)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--fold-sets", type=int, default=64)
+    ap.add_argument("--fold-set-regions", type=int, default=200_000)
+    ap.add_argument("--only", choices=("folds", "algebra"), default=None)
     a = ap.parse_args()
-    res = {"device": {}, "cpu_restatement": {}, "checks": {}}
+    res = {"device": {}, "cpu_restatement": {}, "library_fold": {}, "checks": {}}
     u = synth.make_universe(100_000)
+
+    def flush():
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+
+    if a.only != "algebra":
+        # ---- folds over a list: the pairwise shape, then --fold-sets x --fold-set-regions
+        for tag, n_sets, per, seed in (("a", a.sets, a.set_regions, 1000), ("b", a.fold_sets, a.fold_set_regions, 5000)):
+            made = [make_set(per, seed + 7 * k, u) for k in range(n_sets)]
+            bench_folds(res, tag, [q for q, _ in made], [rs for _, rs in made], a.reps, flush)
+            del made
+    if a.only == "folds":
+        print(json.dumps(res))
+        flush()
+        return
 
     # ---- pairwise Jaccard
     cols, sets = [], []
@@ -173,9 +292,7 @@ def main():
     res["cpu_restatement"]["big_shape"] = f"{k} regions (closest: vs {k // 4})"
     res["checks"]["cpu_vs_device_equal"] = True
     print(json.dumps(res))
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    flush()
 
 
 if __name__ == "__main__":
