@@ -19,6 +19,8 @@ ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_IO, ERR_PARSE, ERR_EM
 
 KIND_BITS = 0
 KIND_AILIST = 1
+PAD_RIGHT = 0
+PAD_LEFT = 1
 UNKNOWN_CHROM = 0xFFFFFFFF
 
 
@@ -86,6 +88,8 @@ _SIG = {
     "gtars_fill_device": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp]),
     "gtars_fill_device_n": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, u64, vp]),
     "gtars_tokenize_device_ex": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, u64, pu64, vp, C.c_int]),
+    "gtars_tokenize_sets_device": (C.c_int, [vp, vp, vp, vp, u64, vp, u64, u32, u64, vp, vp, u64, pu64, pu64, vp]),
+    "gtars_pad_sets_device": (C.c_int, [vp, vp, u64, u64, u32, C.c_int, vp, vp, vp]),
     "gtars_histogram_u32_device": (C.c_int, [vp, u64, u32, vp, vp]),
     "gtars_histogram_rows_device": (C.c_int, [vp, vp, vp, u64, u32, u32, u32, vp, vp]),
     "gtars_tokenize": (C.c_int, [vp, vp, vp, vp, u64, vp, pp, pu64]),
@@ -249,6 +253,9 @@ _HOST_SIG = {
     "gtars_tokenizer_encode_regionset": (C.c_int, [vp, vp, pp, pu64]),
     "gtars_tokenizer_encode_arrays": (C.c_int, [vp, vp, vp, vp, u64, pp, pu64]),
     "gtars_tokenizer_encode_ids": (C.c_int, [vp, vp, vp, vp, u64, vp, pp, pu64]),
+    "gtars_tokenizer_encode_sets": (C.c_int, [vp, vp, u64, u64, pp, pp, pu64]),
+    "gtars_tokenizer_encode_sets_ids": (C.c_int, [vp, vp, vp, vp, u64, vp, u64, u64, pp, pp, pu64]),
+    "gtars_tokenizer_encode_sets_padded": (C.c_int, [vp, vp, vp, vp, u64, vp, u64, u64, u64, C.c_int, pp, pp, pu64]),
     "gtars_tokenizer_tokenize_fragment_file": (C.c_int, [vp, cstr, C.POINTER(C.POINTER(FragmentTokens))]),
     "gtars_fragment_tokens_free": (None, [C.POINTER(FragmentTokens)]),
     "gtars_fragment_tokens_barcodes_joined": (C.c_int, [C.POINTER(FragmentTokens), pp, pu64]),
@@ -313,6 +320,7 @@ _DEBUG_SIG = {
     "gtars_debug_seg_max": (C.c_int, [vp, vp, vp, u64, u32, C.c_int, vp]),
     "gtars_debug_signal_sort_elems": (u32, [u32]),
     "gtars_debug_signal_split_hits": (u32, []),
+    "gtars_debug_tokbatch_tile": (u32, []),
 }
 
 # every symbol the headers declare must resolve -- fail loudly otherwise (GTARS_AMD_LIB_OLDER=1, A/B tooling only: an older
@@ -379,6 +387,17 @@ def take_u32(p: C.c_void_p, n: int) -> np.ndarray:
         if n == 0 or not p.value:
             return np.zeros(0, dtype=np.uint32)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n,)).copy()
+    finally:
+        if p.value:
+            lib.gtars_free(p)
+
+
+def take_array(p: C.c_void_p, n: int, ctype, dtype) -> np.ndarray:
+    """Copy a library-allocated array of n elements into numpy and free it."""
+    try:
+        if n == 0 or not p.value:
+            return np.zeros(0, dtype=dtype)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(n,)).copy()
     finally:
         if p.value:
             lib.gtars_free(p)

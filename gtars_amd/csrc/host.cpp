@@ -38,6 +38,7 @@
 #include "setops.h"
 #include "annot.h"
 #include "uniwig.h"
+#include "tokbatch.h"
 
 namespace gtars {
 gtars_status fail(gtars_status st, const std::string &msg);
@@ -2576,6 +2577,73 @@ gtars_status gtars_tokenizer_encode_ids(const gtars_tokenizer_t *t, const uint32
                                         uint64_t *offsets, uint32_t **out_ids, uint64_t *out_n) {
     if (!t || !out_ids || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
     return gtars_tokenize(t->index, chrom_ids, starts, ends, n, offsets, out_ids, out_n);
+}
+
+// ---- a batch of region sets in one device pass (tokbatch.hip, K15)
+static gtars_status encode_sets_core(const gtars_tokenizer *t, const uint32_t *qc, const uint32_t *qs, const uint32_t *qe, uint64_t n,
+                              const uint64_t *set_offsets, uint64_t n_sets, uint64_t max_length, uint64_t **out_offsets,
+                              uint32_t **out_ids, uint64_t *out_n) {
+    gtars::TokBatchOut out;
+    if (const gtars_status e = gtars::tokbatch_encode(t->index, qc, qs, qe, n, set_offsets, n_sets, t->unk_id, max_length, true, false, 0,
+                                                      GTARS_PAD_RIGHT, 0, out))
+        return e;
+    *out_offsets = out.offsets, *out_ids = out.ids, *out_n = out.total;
+    out.offsets = nullptr, out.ids = nullptr;
+    return GTARS_OK;
+}
+
+gtars_status gtars_tokenizer_encode_sets(const gtars_tokenizer_t *t, const gtars_regionset_t *const *sets, uint64_t n_sets,
+                                         uint64_t max_length, uint64_t **out_offsets, uint32_t **out_ids, uint64_t *out_n) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (const gtars_status e = gtars::require_device()) return e;
+        if (!t || !out_offsets || !out_ids || !out_n || (n_sets && !sets)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_offsets = nullptr, *out_ids = nullptr, *out_n = 0;
+        std::vector<uint64_t> set_off(n_sets + 1, 0);
+        for (uint64_t b = 0; b < n_sets; ++b) {
+            if (!sets[b]) return fail(GTARS_ERR_INVALID_ARG, "NULL region set");
+            set_off[b + 1] = set_off[b] + sets[b]->size();
+        }
+        std::vector<uint32_t> qc, qs, qe;
+        qc.reserve(set_off[n_sets]), qs.reserve(set_off[n_sets]), qe.reserve(set_off[n_sets]);
+        for (uint64_t b = 0; b < n_sets; ++b) {
+            const std::vector<uint32_t> c = translate_chroms(sets[b], t->chroms);
+            qc.insert(qc.end(), c.begin(), c.end());
+            qs.insert(qs.end(), sets[b]->starts.begin(), sets[b]->starts.end());
+            qe.insert(qe.end(), sets[b]->ends.begin(), sets[b]->ends.end());
+        }
+        return encode_sets_core(t, qc.data(), qs.data(), qe.data(), qc.size(), set_off.data(), n_sets, max_length, out_offsets, out_ids,
+                                out_n);
+    });
+}
+
+gtars_status gtars_tokenizer_encode_sets_ids(const gtars_tokenizer_t *t, const uint32_t *chrom_ids, const uint32_t *starts,
+                                             const uint32_t *ends, uint64_t n, const uint64_t *set_offsets, uint64_t n_sets,
+                                             uint64_t max_length, uint64_t **out_offsets, uint32_t **out_ids, uint64_t *out_n) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (const gtars_status e = gtars::require_device()) return e;
+        if (!t || !out_offsets || !out_ids || !out_n) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out_offsets = nullptr, *out_ids = nullptr, *out_n = 0;
+        return encode_sets_core(t, chrom_ids, starts, ends, n, set_offsets, n_sets, max_length, out_offsets, out_ids, out_n);
+    });
+}
+
+gtars_status gtars_tokenizer_encode_sets_padded(const gtars_tokenizer_t *t, const uint32_t *chrom_ids, const uint32_t *starts,
+                                                const uint32_t *ends, uint64_t n, const uint64_t *set_offsets, uint64_t n_sets,
+                                                uint64_t max_length, uint64_t width_or_0, int side, uint32_t **input_ids,
+                                                uint8_t **mask, uint64_t *width) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (const gtars_status e = gtars::require_device()) return e;
+        if (!t || !input_ids || !mask || !width) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *input_ids = nullptr, *mask = nullptr, *width = 0;
+        const uint32_t pad_id = t->region_to_id.at(t->special[1]);
+        gtars::TokBatchOut out;
+        if (const gtars_status e = gtars::tokbatch_encode(t->index, chrom_ids, starts, ends, n, set_offsets, n_sets, t->unk_id, max_length,
+                                                          false, true, width_or_0, side, pad_id, out))
+            return e;
+        *input_ids = out.input_ids, *mask = out.mask, *width = out.width;
+        out.input_ids = nullptr, out.mask = nullptr;
+        return GTARS_OK;
+    });
 }
 
 // tokenize_fragment_file -- gtars-tokenizers/src/utils/fragments.rs:12-82

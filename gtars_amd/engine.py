@@ -223,6 +223,47 @@ class OverlapIndex:
         hm, mo = _minargs(min_overlap)
         check(lib.gtars_count_overlaps_device(self._h, d_qc, d_qs, d_qe, nq, hm, mo, d_counts, stream))
 
+    def tokenize_sets_device(self, d_qc: int, d_qs: int, d_qe: int, nq: int, d_set_offsets: int, n_sets: int, unk_id: int,
+                             d_out_offsets: int, d_out_ids: int, ids_capacity: int, max_length: Optional[int] = None,
+                             stream: int = 0) -> Tuple[int, int]:
+        """The concatenated batch as ``n_sets`` independent ``Tokenizer::tokenize`` calls, on device buffers; see
+        :func:`tokenize_sets_device`."""
+        return tokenize_sets_device(self._h, d_qc, d_qs, d_qe, nq, d_set_offsets, n_sets, unk_id, d_out_offsets, d_out_ids,
+                                    ids_capacity, max_length, stream)
+
+    @staticmethod
+    def pad_sets_device(d_out_offsets: int, d_out_ids: int, n_sets: int, width: int, pad_id: int, d_input_ids: int, d_mask: int,
+                        side: str = "right", stream: int = 0) -> None:
+        """The ragged result as [n_sets, width] ``input_ids`` / ``attention_mask`` on the device; see :func:`pad_sets_device`."""
+        pad_sets_device(d_out_offsets, d_out_ids, n_sets, width, pad_id, d_input_ids, d_mask, side, stream)
+
+
+def tokenize_sets_device(index_handle, d_qc: int, d_qs: int, d_qe: int, nq: int, d_set_offsets: int, n_sets: int, unk_id: int,
+                         d_out_offsets: int, d_out_ids: int, ids_capacity: int, max_length: Optional[int] = None,
+                         stream: int = 0) -> Tuple[int, int]:
+    """``gtars_tokenize_sets_device`` on a ``gtars_index_t*`` (an ``OverlapIndex``'s, or ``Tokenizer.engine_index``): set b =
+    the queries ``[set_offsets[b], set_offsets[b + 1])`` (u64 on the device); ``[unk_id]`` for a set without any id, then the
+    first ``max_length`` ids.  ``d_out_offsets``: u64[n_sets + 1], ``d_out_ids``: room for ``ids_capacity`` u32 (0 / null: a
+    sizing pass).  -> (total ids, longest set); ``CapacityError`` (``.needed``) when the ids do not fit -- the offsets are
+    complete then."""
+    total, longest = C.c_uint64(), C.c_uint64()
+    check(lib.gtars_tokenize_sets_device(index_handle, d_qc, d_qs, d_qe, nq, d_set_offsets, n_sets, int(unk_id), int(max_length or 0),
+                                         d_out_offsets, d_out_ids, ids_capacity, C.byref(total), C.byref(longest), stream))
+    return int(total.value), int(longest.value)
+
+
+def pad_sets_device(d_out_offsets: int, d_out_ids: int, n_sets: int, width: int, pad_id: int, d_input_ids: int, d_mask: int,
+                    side: str = "right", stream: int = 0) -> None:
+    """``gtars_pad_sets_device``: the ragged result as u32 ``input_ids`` / u8 ``attention_mask`` of shape [n_sets, width] on the
+    device; a set longer than ``width`` is a ``ValueError``."""
+    check(lib.gtars_pad_sets_device(d_out_offsets, d_out_ids, n_sets, int(width), int(pad_id), pad_side(side), d_input_ids, d_mask, stream))
+
+
+def pad_side(side: str) -> int:
+    if side not in ("right", "left"):
+        raise ValueError(f"padding_side must be 'right' or 'left', not {side!r}")
+    return _lib.PAD_LEFT if side == "left" else _lib.PAD_RIGHT
+
 
 class IgdIndex:
     """IGD database resident in HBM (gtars-igd/src/igd.rs), one record per stored interval."""

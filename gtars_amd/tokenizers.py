@@ -7,7 +7,10 @@ parsing and the vocabulary live in the C++ host layer, the overlap search runs
 in the HIP kernels; this file only adapts Python objects.
 
 Additive fast path (not in the reference): ``encode_arrays`` / ``encode_ids``
-take numpy columns instead of per-object attribute access.
+take numpy columns instead of per-object attribute access.  Additive as well:
+``encode_many`` / ``tokenize_many`` / ``batch`` encode a list of region sets as
+that many ``tokenize`` calls in one device pass (csrc/tokbatch.hip) and pad them
+into 2-D ``input_ids`` / ``attention_mask``.
 """
 from __future__ import annotations
 
@@ -186,6 +189,134 @@ class Tokenizer:
 
     def encode_arrays(self, chrom_names: Sequence[str], starts, ends) -> Tuple[np.ndarray, np.ndarray]:
         return self.encode_ids(self.chrom_ids(chrom_names), starts, ends)
+
+    # a batch of region sets in one device pass (additive; the reference is called once per set) ------------------------
+    def _concat_sets(self, sets) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """every item as ``_columns_from_py_any`` takes it -> (chrom ids, starts, ends, set_offsets) of the concatenated batch"""
+        cs, ss, es, off = [], [], [], [0]
+        for item in sets:
+            rs, cols = _columns_from_py_any(item)
+            if rs is not None:
+                names = self.chrom_ids(rs.chrom_names)
+                cs.append(names[rs.chrom_ids] if len(rs) else np.zeros(0, dtype=np.uint32))
+                ss.append(rs.starts)
+                es.append(rs.ends)
+            else:
+                chrs, s, e = cols
+                cs.append(self.chrom_ids(chrs))
+                ss.append(s)
+                es.append(e)
+            off.append(off[-1] + len(ss[-1]))
+        cat = lambda parts: np.concatenate(parts).astype(np.uint32, copy=False) if parts else np.zeros(0, dtype=np.uint32)  # noqa: E731
+        return cat(cs), cat(ss), cat(es), np.asarray(off, dtype=np.uint64)
+
+    @staticmethod
+    def _max_length(max_length: Optional[int]) -> int:
+        if max_length is None:
+            return 0
+        if int(max_length) < 1:
+            raise ValueError("max_length must be at least 1 (or None)")
+        return int(max_length)
+
+    def encode_many_arrays(self, chrom_ids, starts, ends, set_offsets, max_length: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """``len(set_offsets) - 1`` region sets, set b = rows ``[set_offsets[b], set_offsets[b + 1])`` of the columns, as that many
+        ``tokenize`` calls in one device pass -> (offsets u64[B + 1], ids u32): per set its ids, ``[unk]`` if it has none, then the
+        first ``max_length``."""
+        c, s, e = _lib.as_u32(chrom_ids), _lib.as_u32(starts), _lib.as_u32(ends)
+        so = np.ascontiguousarray(set_offsets, dtype=np.uint64)
+        if not (len(c) == len(s) == len(e)):
+            raise ValueError("chrom_ids, starts, ends must have the same length")
+        if len(so) < 1:
+            raise ValueError("set_offsets needs at least one entry")
+        po, pi, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        check(lib.gtars_tokenizer_encode_sets_ids(self._h, ptr(c), ptr(s), ptr(e), len(c), ptr(so), len(so) - 1, self._max_length(max_length),
+                                                  C.byref(po), C.byref(pi), C.byref(n)))
+        return _lib.take_array(po, len(so), C.c_uint64, np.uint64), take_u32(pi, n.value)
+
+    def encode_many(self, sets, max_length: Optional[int] = None) -> List[List[int]]:
+        """``[self._encode_regions(s) for s in sets]`` in one device pass; ``max_length`` keeps the first ids of every set."""
+        sets = list(sets)
+        if sets and all(isinstance(x, RegionSet) for x in sets):
+            arr = (C.c_void_p * len(sets))(*[x._h for x in sets])
+            po, pi, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+            check(lib.gtars_tokenizer_encode_sets(self._h, C.cast(arr, C.c_void_p), len(sets), self._max_length(max_length), C.byref(po),
+                                                  C.byref(pi), C.byref(n)))
+            off, ids = _lib.take_array(po, len(sets) + 1, C.c_uint64, np.uint64), take_u32(pi, n.value)
+        else:
+            off, ids = self.encode_many_arrays(*self._concat_sets(sets), max_length=max_length)
+        flat = ids.tolist()
+        return [flat[int(off[b]):int(off[b + 1])] for b in range(len(off) - 1)]
+
+    def tokenize_many(self, sets) -> List[List[str]]:
+        """``[self.tokenize(s) for s in sets]`` in one device pass."""
+        return [[self._id_to_token(i) for i in row] for row in self.encode_many(sets)]
+
+    def batch(self, sets, padding: Union[str, int] = "longest", max_length: Optional[int] = None, padding_side: str = "right",
+              return_tensors: Optional[str] = None) -> BatchEncoding:
+        """The sets encoded and padded into 2-D ``input_ids`` / ``attention_mask`` (1 on ids, 0 on padding) on the device.
+
+        ``padding``: ``"longest"`` or a width, which must hold the longest set (``ValueError`` otherwise: nothing is cut silently;
+        ``max_length`` is what cuts).  ``return_tensors``: ``None`` nested lists, ``"np"`` numpy (uint32 / uint8), ``"pt"`` torch
+        tensors (int32 / uint8) on the current device -- then only the batch's total and longest sizes cross to the host."""
+        return self.batch_arrays(*self._concat_sets(sets), padding=padding, max_length=max_length, padding_side=padding_side,
+                                 return_tensors=return_tensors)
+
+    def batch_arrays(self, chrom_ids, starts, ends, set_offsets, padding: Union[str, int] = "longest", max_length: Optional[int] = None,
+                     padding_side: str = "right", return_tensors: Optional[str] = None) -> BatchEncoding:
+        """``batch`` on the columns of the concatenated sets (see ``encode_many_arrays``)."""
+        from .engine import pad_side, pad_sets_device, tokenize_sets_device
+
+        if return_tensors not in (None, "np", "pt"):
+            raise ValueError(f"return_tensors must be None, 'np' or 'pt', not {return_tensors!r}")
+        if padding == "longest":
+            width = 0
+        elif isinstance(padding, (int, np.integer)) and not isinstance(padding, bool) and int(padding) >= 1:
+            width = int(padding)
+        else:
+            raise ValueError(f"padding must be 'longest' or a width of at least 1, not {padding!r}")
+        side, ml = pad_side(padding_side), self._max_length(max_length)
+        c, s, e = _lib.as_u32(chrom_ids), _lib.as_u32(starts), _lib.as_u32(ends)
+        so = np.ascontiguousarray(set_offsets, dtype=np.uint64)
+        if not (len(c) == len(s) == len(e)):
+            raise ValueError("chrom_ids, starts, ends must have the same length")
+        if len(so) < 1:
+            raise ValueError("set_offsets needs at least one entry")
+        B = len(so) - 1
+        if return_tensors != "pt":
+            pi, pm, w = C.c_void_p(), C.c_void_p(), C.c_uint64()
+            check(lib.gtars_tokenizer_encode_sets_padded(self._h, ptr(c), ptr(s), ptr(e), len(c), ptr(so), B, ml, width, side, C.byref(pi),
+                                                         C.byref(pm), C.byref(w)))
+            W = int(w.value)
+            ids = _lib.take_array(pi, B * W, C.c_uint32, np.uint32).reshape(B, W)
+            mask = _lib.take_array(pm, B * W, C.c_uint8, np.uint8).reshape(B, W)
+            return BatchEncoding(ids, mask) if return_tensors == "np" else BatchEncoding(ids.tolist(), mask.tolist())
+        import torch
+
+        dev = torch.device("cuda", torch.cuda.current_device())
+        stream = torch.cuda.current_stream().cuda_stream
+        d = [torch.from_numpy(a.view(np.int32)).to(dev) for a in (c, s, e)]
+        d_so = torch.from_numpy(so.view(np.int64)).to(dev)
+        out_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        ids = torch.empty(2 * len(c) + B + 1024, dtype=torch.int32, device=dev)
+
+        def run():
+            return tokenize_sets_device(self.engine_index, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), len(c), d_so.data_ptr(), B,
+                                        self.unk_token_id, out_off.data_ptr(), ids.data_ptr(), ids.numel(), ml, stream)
+
+        try:
+            _, longest = run()
+        except _lib.CapacityError as err:  # more than two ids per region on average: once more with the exact size
+            ids = torch.empty(err.needed, dtype=torch.int32, device=dev)
+            _, longest = run()
+        if width and width < longest:
+            raise ValueError(f"padding width {width} is smaller than the longest set ({longest} ids): nothing is cut silently")
+        W = width or longest
+        input_ids = torch.empty((B, W), dtype=torch.int32, device=dev)
+        mask = torch.empty((B, W), dtype=torch.uint8, device=dev)
+        if B and W:
+            pad_sets_device(out_off.data_ptr(), ids.data_ptr(), B, W, self.pad_token_id, input_ids.data_ptr(), mask.data_ptr(), padding_side,
+                            stream)
+        return BatchEncoding(input_ids, mask)
 
     @property
     def engine_index(self) -> int:

@@ -189,6 +189,32 @@ gtars_status gtars_tokenize_into(const gtars_index_t *ix, const uint32_t *qchrom
                                  uint64_t *offsets, uint32_t *ids, uint64_t ids_capacity,
                                  uint64_t *out_n);
 
+/* A batch of region sets as B independent Tokenizer::tokenize calls (gtars-tokenizers/src/tokenizer.rs:140-163) in one
+ * device pass.  The sets are ONE concatenated query batch, set b = the queries [set_offsets[b], set_offsets[b + 1]);
+ * d_set_offsets: n_sets + 1 u64 on the device that start at 0, never descend and end at nq (GTARS_ERR_INVALID_ARG otherwise).
+ * Set b's ids are the ids of its queries' overlaps in query order, each query's in the index's own order; a set that yields
+ * no id at all -- no queries, or only queries without a hit -- is [unk_id] (tokenizer.rs:158-160); then only its first
+ * max_length ids are kept (0: all of them).
+ * d_out_offsets: n_sets + 1 u64, d_out_offsets[0] = 0; d_out_ids: room for ids_capacity u32.  *total = d_out_offsets[n_sets],
+ * *longest = the longest set (either may be NULL); the stream is drained.  More ids than ids_capacity: d_out_offsets is
+ * complete, *total is set, GTARS_ERR_CAPACITY -- as gtars_tokenize_device.  d_out_ids == NULL: a sizing pass, no error.
+ * n_sets == 0 is valid (nq must be 0 then). */
+gtars_status gtars_tokenize_sets_device(const gtars_index_t *ix, const uint32_t *d_qchrom, const uint32_t *d_qstart,
+                                        const uint32_t *d_qend, uint64_t nq, const uint64_t *d_set_offsets,
+                                        uint64_t n_sets, uint32_t unk_id, uint64_t max_length,
+                                        uint64_t *d_out_offsets, uint32_t *d_out_ids, uint64_t ids_capacity,
+                                        uint64_t *total, uint64_t *longest, void *stream);
+
+/* The ragged result above as the [n_sets, width] matrices a model takes (gtars-python/src/tokenizers/py_tokenizers/
+ * mod.rs:275-299): row b of d_input_ids = the set's ids followed (GTARS_PAD_RIGHT) or preceded (GTARS_PAD_LEFT) by pad_id,
+ * d_mask (u8) = 1 on the ids and 0 on the padding.  A set longer than `width` is GTARS_ERR_INVALID_ARG, never cut; so is an
+ * n_sets * width that cannot be counted.  Device pointers; the stream is drained. */
+#define GTARS_PAD_RIGHT 0
+#define GTARS_PAD_LEFT 1
+gtars_status gtars_pad_sets_device(const uint64_t *d_out_offsets, const uint32_t *d_out_ids, uint64_t n_sets,
+                                   uint64_t width, uint32_t pad_id, int side, uint32_t *d_input_ids,
+                                   uint8_t *d_mask, void *stream);
+
 /* bins[id] += 1 for every id < n_bins (device pointers): the scatter-add of gtars-scoring's count matrices
  * (CountMatrix::increment, gtars-scoring/src/fragment_scoring.rs:88-105) -- one matrix row per call, the ids being
  * the token ids of one fragment file's probes (gtars_tokenize_device). */

@@ -70,6 +70,10 @@ gtars_status gtars_debug_seg_max(const uint32_t *seg, const uint32_t *val, const
 uint32_t gtars_debug_signal_sort_elems(uint32_t elems);
 uint32_t gtars_debug_signal_split_hits(void);
 
+/* Test hook of the batched tokenizer (csrc/tokbatch.hip, K15; tests/test_gpu_tokbatch.py): the output ids a workgroup of
+ * k_set_pack packs per step. */
+uint32_t gtars_debug_tokbatch_tile(void);
+
 /* (Stamp builds -- tools/build_variant.sh with -DGTARS_TOK_STAMPS=1 / -DIGD_STAMPS=1 -- additionally export
  * gtars_debug_tok_stamps / gtars_debug_route_stamps / gtars_debug_sweep_stamps: s_memtime at the phase boundaries of the tile
  * loops, read by tools/r03_tok_stamps.py, tools/r03_sweep_stamps.py, tools/r05_rank_stamps.py.  The shipped library has none.) */

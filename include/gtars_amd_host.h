@@ -496,6 +496,30 @@ gtars_status gtars_tokenizer_encode_ids(const gtars_tokenizer_t *t, const uint32
                                         const uint32_t *starts, const uint32_t *ends, uint64_t n,
                                         uint64_t *offsets, uint32_t **out_ids, uint64_t *out_n);
 
+/* Tokenizer::encode of n_sets region sets in one device pass (gtars_tokenize_sets_device): per set what
+ * gtars_tokenizer_encode_regionset gives for it alone -- [unk] for a set without any id -- cut to its first max_length
+ * ids (0: all of them).  *out_offsets: n_sets + 1 entries, set b's ids are (*out_ids)[(*out_offsets)[b] ..
+ * (*out_offsets)[b + 1]); *out_n = their number; both arrays are released with gtars_free.  n_sets == 0 is valid.
+ * gtars_tokenizer_encode_sets_ids is the array form: chromosome IDS of this tokenizer's dictionary for the concatenated
+ * sets, set b = rows [set_offsets[b], set_offsets[b + 1]); set_offsets that do not start at 0, descend or do not end at n
+ * are GTARS_ERR_INVALID_ARG.
+ * gtars_tokenizer_encode_sets_padded gives the [n_sets, *width] matrices over the same inputs: the sets' ids and the
+ * tokenizer's pad id on `side` (GTARS_PAD_RIGHT / GTARS_PAD_LEFT), the mask 1 on ids and 0 on padding.  width_or_0 == 0: the
+ * longest set; otherwise that width, and GTARS_ERR_INVALID_ARG when a set is longer -- nothing is cut silently.
+ * Without a device every one of the three fails with GTARS_ERR_NO_DEVICE before it looks at its arguments. */
+gtars_status gtars_tokenizer_encode_sets(const gtars_tokenizer_t *t, const gtars_regionset_t *const *sets,
+                                         uint64_t n_sets, uint64_t max_length, uint64_t **out_offsets,
+                                         uint32_t **out_ids, uint64_t *out_n);
+gtars_status gtars_tokenizer_encode_sets_ids(const gtars_tokenizer_t *t, const uint32_t *chrom_ids,
+                                             const uint32_t *starts, const uint32_t *ends, uint64_t n,
+                                             const uint64_t *set_offsets, uint64_t n_sets, uint64_t max_length,
+                                             uint64_t **out_offsets, uint32_t **out_ids, uint64_t *out_n);
+gtars_status gtars_tokenizer_encode_sets_padded(const gtars_tokenizer_t *t, const uint32_t *chrom_ids,
+                                                const uint32_t *starts, const uint32_t *ends, uint64_t n,
+                                                const uint64_t *set_offsets, uint64_t n_sets, uint64_t max_length,
+                                                uint64_t width_or_0, int side, uint32_t **input_ids,
+                                                uint8_t **mask, uint64_t *width);
+
 /* ------------------------------------------------------------------------
  * Fragment files as SoA columns (parse_fragment_line, utils/fragments.rs:12-40):
  * `chr start end barcode count` split on whitespace, lines starting with '#'
