@@ -17,7 +17,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <functional>
 #include <limits>
 #include <map>
 #include <memory>
@@ -30,6 +29,7 @@
 #include <thread>
 #include <tuple>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
@@ -39,6 +39,7 @@
 #include "annot.h"
 #include "uniwig.h"
 #include "tokbatch.h"
+#include "host_threads.h"
 
 namespace gtars {
 gtars_status fail(gtars_status st, const std::string &msg);
@@ -512,6 +513,64 @@ inline bool parse_u32_view(const char *p, size_t n, uint32_t &out) {
     return true;
 }
 
+// ---- results that go out through the C ABI as plain allocations, owned until they are handed to the caller
+inline void *or_bad_alloc(void *p) {
+    if (!p) throw std::bad_alloc();
+    return p;
+}
+struct GtarsFree {
+    void operator()(void *p) const { gtars_free(p); }
+};
+struct FragmentTokensFree {
+    void operator()(gtars_fragment_tokens_t *ft) const { gtars_fragment_tokens_free(ft); }
+};
+using FragmentTokensPtr = std::unique_ptr<gtars_fragment_tokens_t, FragmentTokensFree>;
+
+// The tokens of names.size() barcodes: copies of the names, offsets = `cnt` (the inclusive counts: cnt[0] = 0, cnt[b + 1] = the ids
+// of the barcodes up to and including b) and room for cnt.back() ids, which the caller fills.  std::bad_alloc when any of the
+// allocations fails -- a name's copy included.
+template <class Names>
+FragmentTokensPtr new_fragment_tokens(const Names &names, const std::vector<uint64_t> &cnt) {
+    const uint64_t nb = names.size();
+    FragmentTokensPtr ft((gtars_fragment_tokens_t *)or_bad_alloc(calloc(1, sizeof(gtars_fragment_tokens_t))));
+    ft->barcodes = (char **)or_bad_alloc(calloc(nb ? nb : 1, sizeof(char *)));
+    ft->n_barcodes = nb;  // (from here on the free function walks the names; it takes the NULLs behind a failed copy)
+    ft->offsets = (uint64_t *)or_bad_alloc(malloc((nb + 1) * sizeof(uint64_t)));
+    ft->ids = (uint32_t *)or_bad_alloc(malloc((cnt[nb] ? cnt[nb] : 1) * sizeof(uint32_t)));
+    memcpy(ft->offsets, cnt.data(), (nb + 1) * sizeof(uint64_t));
+    for (uint64_t b = 0; b < nb; ++b) ft->barcodes[b] = (char *)or_bad_alloc(dup_cstr(names[b]));
+    return ft;
+}
+
+// ... and those of a run of tokenized fragments grouped by barcode: each(f) calls f(barcode id, the fragment's ids, how many) for
+// every fragment in order; one tokenize() per fragment -- a fragment without hits contributes exactly one unk id
+template <class Names, class Each>
+FragmentTokensPtr tokens_by_barcode(const Names &names, uint32_t unk_id, Each &&each) {
+    std::vector<uint64_t> cnt(names.size() + 1, 0);
+    each([&](uint32_t b, const uint32_t *, uint64_t k) { cnt[b + 1] += k ? k : 1; });
+    for (size_t b = 1; b < cnt.size(); ++b) cnt[b] += cnt[b - 1];
+    FragmentTokensPtr ft = new_fragment_tokens(names, cnt);
+    std::vector<uint64_t> fill(cnt.begin(), cnt.end() - 1);
+    each([&](uint32_t b, const uint32_t *ids, uint64_t k) {
+        uint64_t &at = fill[b];
+        if (!k) ft->ids[at++] = unk_id;
+        for (uint64_t y = 0; y < k; ++y) ft->ids[at++] = ids[y];
+    });
+    return ft;
+}
+
+// the fused pipeline's array of one result per cluster
+struct ClusterTokensFree {
+    size_t n;
+    void operator()(gtars_fragment_tokens_t **p) const {
+        for (size_t i = 0; i < n; ++i) gtars_fragment_tokens_free(p[i]);
+        free(p);
+    }
+};
+using ClusterTokens = std::unique_ptr<gtars_fragment_tokens_t *, ClusterTokensFree>;
+ClusterTokens new_cluster_tokens(size_t n) {
+    return ClusterTokens((gtars_fragment_tokens_t **)or_bad_alloc(calloc(n ? n : 1, sizeof(gtars_fragment_tokens_t *))), ClusterTokensFree{n});
+}
 
 }  // namespace
 
@@ -661,20 +720,9 @@ static gtars_status gtars_regionset_from_bed_impl(const char *path, gtars_region
     };
     unsigned nt = host_thread_budget(32);
     nt = (unsigned)std::min<size_t>(nt, data.size() / (1u << 20) + 1);
-    std::vector<size_t> cut(nt + 1, data.size());
-    cut[0] = 0;
-    for (unsigned i = 1; i < nt; ++i) {
-        const size_t nl = data.find('\n', data.size() / nt * i);
-        cut[i] = nl == std::string::npos ? data.size() : nl + 1;
-    }
-    for (unsigned i = 1; i <= nt; ++i) cut[i] = std::max(cut[i], cut[i - 1]);
+    const std::vector<size_t> cut = gtars::cut_at_lines(data.data(), data.size(), nt);
     std::vector<Chunk> chunks(nt);
-    {
-        std::vector<std::thread> th;
-        for (unsigned i = 1; i < nt; ++i) th.emplace_back([&, i] { parse_chunk(cut[i], cut[i + 1], false, chunks[i]); });
-        parse_chunk(cut[0], cut[1], true, chunks[0]);
-        for (auto &t : th) t.join();
-    }
+    gtars::parallel_for(nt, nt, 1, [&](size_t i) { parse_chunk(cut[i], cut[i + 1], i == 0, chunks[i]); });
     std::string header;
     size_t n = 0;
     for (unsigned i = 0; i < nt; ++i) {
@@ -1734,24 +1782,10 @@ gtars_status gtars_gtf_read(const char *path, int filter_protein_coding, int con
         // cut at line starts into up to 16 chunks of >= 1 MiB
         const size_t n = text.size();
         const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_thread_budget(16), n >> 20));
-        std::vector<size_t> cut{0};
-        for (unsigned k = 1; k < nt; ++k) {
-            size_t at = std::max(cut.back(), n / nt * k);
-            const char *nl = at < n ? (const char *)memchr(text.data() + at, '\n', n - at) : nullptr;
-            at = nl ? (size_t)(nl - text.data()) + 1 : n;
-            cut.push_back(at);
-        }
-        cut.push_back(n);
-        std::vector<GtfChunk> chunks(cut.size() - 1);
+        const std::vector<size_t> cut = gtars::cut_at_lines(text.data(), n, nt);
+        std::vector<GtfChunk> chunks(nt);
         const bool pc = filter_protein_coding != 0, cv = convert_ensembl_ucsc != 0;
-        if (chunks.size() == 1) {
-            gtf_scan(text, 0, n, pc, cv, chunks[0]);
-        } else {
-            std::vector<std::thread> th;
-            for (size_t k = 0; k < chunks.size(); ++k)
-                th.emplace_back([&, k] { gtf_scan(text, cut[k], cut[k + 1], pc, cv, chunks[k]); });
-            for (std::thread &t : th) t.join();
-        }
+        gtars::parallel_for(nt, nt, 1, [&](size_t k) { gtf_scan(text, cut[k], cut[k + 1], pc, cv, chunks[k]); });
         for (const GtfChunk &c : chunks)
             if (!c.err.empty()) return fail(GTARS_ERR_PARSE, c.err);  // the first in file order
         auto rs = std::make_unique<gtars_regionset>();
@@ -2713,22 +2747,11 @@ gtars_status read_fragment_table(const char *path, FragTable &ft, bool check_sup
     if (!read_all(path, data, err)) return fail(GTARS_ERR_IO, err);
     unsigned nt = host_thread_budget(32);
     nt = (unsigned)std::min<size_t>(nt, data.size() / (1u << 20) + 1);
-    std::vector<size_t> cut(nt + 1, data.size());
-    cut[0] = 0;
-    for (unsigned i = 1; i < nt; ++i) {
-        size_t pos = data.size() / nt * i;
-        const size_t nl = data.find('\n', pos);
-        cut[i] = nl == std::string::npos ? data.size() : nl + 1;
-    }
-    for (unsigned i = 1; i <= nt; ++i) cut[i] = std::max(cut[i], cut[i - 1]);
+    const std::vector<size_t> cut = gtars::cut_at_lines(data.data(), data.size(), nt);
     std::vector<FragChunk> chunks(nt);
-    {
-        std::vector<std::thread> th;
-        for (unsigned i = 1; i < nt; ++i)
-            th.emplace_back([&, i] { parse_fragment_chunk(data.data() + cut[i], data.data() + cut[i + 1], chunks[i], check_support); });
-        parse_fragment_chunk(data.data() + cut[0], data.data() + cut[1], chunks[0], check_support);
-        for (auto &t : th) t.join();
-    }
+    gtars::parallel_for(nt, nt, 1, [&](size_t i) {
+        parse_fragment_chunk(data.data() + cut[i], data.data() + cut[i + 1], chunks[i], check_support);
+    });
     size_t line0 = 0, total = 0;
     for (unsigned i = 0; i < nt; ++i) {
         if (chunks[i].err) {
@@ -2751,24 +2774,18 @@ gtars_status read_fragment_table(const char *path, FragTable &ft, bool check_sup
     ft.c.resize(total); ft.s.resize(total); ft.e.resize(total); ft.b.resize(total);
     std::vector<size_t> base(nt + 1, 0);
     for (unsigned i = 0; i < nt; ++i) base[i + 1] = base[i] + chunks[i].c.size();
-    {
-        auto merge = [&](unsigned i) {
-            const FragChunk &ck = chunks[i];
-            const size_t o = base[i], m = ck.c.size();
-            for (size_t k = 0; k < m; ++k) {
-                ft.c[o + k] = mapc[i][ck.c[k]];
-                ft.b[o + k] = mapb[i][ck.b[k]];
-            }
-            if (m) {
-                memcpy(&ft.s[o], ck.s.data(), m * sizeof(uint32_t));
-                memcpy(&ft.e[o], ck.e.data(), m * sizeof(uint32_t));
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned i = 1; i < nt; ++i) th.emplace_back(merge, i);
-        merge(0);
-        for (auto &t : th) t.join();
-    }
+    gtars::parallel_for(nt, nt, 1, [&](size_t i) {
+        const FragChunk &ck = chunks[i];
+        const size_t o = base[i], m = ck.c.size();
+        for (size_t k = 0; k < m; ++k) {
+            ft.c[o + k] = mapc[i][ck.c[k]];
+            ft.b[o + k] = mapb[i][ck.b[k]];
+        }
+        if (m) {
+            memcpy(&ft.s[o], ck.s.data(), m * sizeof(uint32_t));
+            memcpy(&ft.e[o], ck.e.data(), m * sizeof(uint32_t));
+        }
+    });
     ft.chroms.assign(gc.names.begin(), gc.names.end());
     ft.barcodes.assign(gb.names.begin(), gb.names.end());
     return GTARS_OK;
@@ -2821,21 +2838,9 @@ gtars_status read_bed3_lines(const char *path, FragTable &ft) {
     if (!read_all(path, data, err)) return fail(GTARS_ERR_IO, err);
     unsigned nt = host_thread_budget(32);
     nt = (unsigned)std::min<size_t>(nt, data.size() / (1u << 20) + 1);
-    std::vector<size_t> cut(nt + 1, data.size());
-    cut[0] = 0;
-    for (unsigned i = 1; i < nt; ++i) {
-        const size_t nl = data.find('\n', data.size() / nt * i);
-        cut[i] = nl == std::string::npos ? data.size() : nl + 1;
-    }
-    for (unsigned i = 1; i <= nt; ++i) cut[i] = std::max(cut[i], cut[i - 1]);
+    const std::vector<size_t> cut = gtars::cut_at_lines(data.data(), data.size(), nt);
     std::vector<FragChunk> chunks(nt);
-    {
-        std::vector<std::thread> th;
-        for (unsigned i = 1; i < nt; ++i)
-            th.emplace_back([&, i] { parse_bed3_chunk(data.data() + cut[i], data.data() + cut[i + 1], chunks[i]); });
-        parse_bed3_chunk(data.data() + cut[0], data.data() + cut[1], chunks[0]);
-        for (auto &t : th) t.join();
-    }
+    gtars::parallel_for(nt, nt, 1, [&](size_t i) { parse_bed3_chunk(data.data() + cut[i], data.data() + cut[i + 1], chunks[i]); });
     size_t line0 = 0, total = 0;
     for (unsigned i = 0; i < nt; ++i) {
         if (chunks[i].err) {
@@ -2906,10 +2911,7 @@ static gtars_status gtars_tokenizer_tokenize_fragment_file_impl(const gtars_toke
     if (!t || !path || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
     FragTable frag;
-    {
-        gtars_status st0 = read_fragment_table(path, frag);
-        if (st0) return st0;
-    }
+    if (const gtars_status e = read_fragment_table(path, frag)) return e;
     // the file's chromosome dictionary -> the tokenizer's
     std::vector<uint32_t> cmap(frag.chroms.size());
     for (size_t i = 0; i < cmap.size(); ++i) {
@@ -2920,36 +2922,13 @@ static gtars_status gtars_tokenizer_tokenize_fragment_file_impl(const gtars_toke
     for (uint32_t &v : qc) v = cmap[v];
     const uint64_t n = qc.size();
     std::vector<uint64_t> off(n + 1, 0);
-    uint32_t *ids = nullptr;
+    uint32_t *got = nullptr;
     uint64_t h = 0;
-    gtars_status st = gtars_tokenize(t->index, qc.data(), qs.data(), qe.data(), n, off.data(), &ids, &h);
-    if (st) return st;
-    // one tokenize() per fragment: a fragment without hits contributes exactly one unk id
-    const uint64_t nb = frag.barcodes.size();
-    std::vector<uint64_t> cnt(nb + 1, 0);
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t k = off[i + 1] - off[i];
-        cnt[bc[i] + 1] += k ? k : 1;
-    }
-    for (uint64_t b = 0; b < nb; ++b) cnt[b + 1] += cnt[b];
-    auto *ft = (gtars_fragment_tokens_t *)calloc(1, sizeof(gtars_fragment_tokens_t));
-    ft->n_barcodes = nb;
-    ft->barcodes = (char **)calloc(nb ? nb : 1, sizeof(char *));
-    ft->offsets = (uint64_t *)malloc((nb + 1) * sizeof(uint64_t));
-    ft->ids = (uint32_t *)malloc((cnt[nb] ? cnt[nb] : 1) * sizeof(uint32_t));
-    memcpy(ft->offsets, cnt.data(), (nb + 1) * sizeof(uint64_t));
-    for (uint64_t b = 0; b < nb; ++b) ft->barcodes[b] = dup_cstr(frag.barcodes[b]);
-    std::vector<uint64_t> fill(cnt.begin(), cnt.end() - 1);
-    for (uint64_t i = 0; i < n; ++i) {
-        uint64_t &w = fill[bc[i]];
-        if (off[i + 1] == off[i]) {
-            ft->ids[w++] = t->unk_id;
-        } else {
-            for (uint64_t k = off[i]; k < off[i + 1]; ++k) ft->ids[w++] = ids[k];
-        }
-    }
-    gtars_free(ids);
-    *out = ft;
+    if (const gtars_status e = gtars_tokenize(t->index, qc.data(), qs.data(), qe.data(), n, off.data(), &got, &h)) return e;
+    const std::unique_ptr<uint32_t, GtarsFree> ids(got);
+    *out = tokens_by_barcode(frag.barcodes, t->unk_id, [&](auto &&f) {
+               for (uint64_t i = 0; i < n; ++i) f(bc[i], ids.get() + off[i], off[i + 1] - off[i]);
+           }).release();
     return GTARS_OK;
 }
 
@@ -3166,18 +3145,7 @@ static gtars_status gtars_igddb_from_bed_files_impl(const char *const *paths, ui
     if (!out || (n_paths && !paths)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
     std::vector<IgdBedFile> parsed(n_paths);
-    {
-        unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(host_thread_budget(64), n_paths));
-        std::atomic<uint64_t> next{0};
-        auto work = [&] {
-            for (uint64_t i = next.fetch_add(1); i < n_paths; i = next.fetch_add(1))
-                parse_igd_bed_file(paths[i] ? paths[i] : "", parsed[i]);
-        };
-        std::vector<std::thread> th;
-        for (unsigned i = 1; i < nt; ++i) th.emplace_back(work);
-        work();
-        for (auto &t : th) t.join();
-    }
+    gtars::parallel_for((size_t)n_paths, host_thread_budget(64), 1, [&](size_t i) { parse_igd_bed_file(paths[i] ? paths[i] : "", parsed[i]); });
     auto *db = new gtars_igddb();
     uint64_t total = 0;
     for (const IgdBedFile &f : parsed) total += f.c.size();
@@ -3864,23 +3832,14 @@ gtars_status stream_text_files(const std::vector<std::string> &files, const gtar
             cvx.notify_all();
         }
     };
-    std::vector<std::thread> th;
-    for (unsigned k = 0; k < nt; ++k) th.emplace_back(loader);
-    struct Join {
-        std::vector<std::thread> &th;
-        std::mutex &mx;
-        std::condition_variable &cvx;
-        bool &stop;
-        ~Join() {
-            {
-                std::lock_guard<std::mutex> lk(mx);
-                stop = true;
-            }
-            cvx.notify_all();
-            for (auto &t : th)
-                if (t.joinable()) t.join();
+    gtars::JoinedThreads loaders([&] {
+        {
+            std::lock_guard<std::mutex> lk(mx);
+            stop = true;
         }
-    } join{th, mx, cvx, stop};
+        cvx.notify_all();
+    });
+    loaders.start(nt, loader);
     gtars_status st = GTARS_OK;
     size_t lo = 0;
     while (lo < n) {
@@ -3931,19 +3890,401 @@ gtars_status for_each_split_wave(const std::vector<std::string> &files, const gt
     for (size_t base = 0; base < files.size(); base += wave) {
         const size_t n = std::min(wave, files.size() - base);
         std::vector<SplitFile> res(n);
-        std::atomic<size_t> next{0};
-        auto work = [&] {
-            for (size_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) split_one_file(files[base + i], m, want_text, res[i], chroms);
-        };
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < nt; ++k) th.emplace_back(work);
-        work();
-        for (auto &t : th) t.join();
+        gtars::parallel_for(n, nt, 1, [&](size_t i) { split_one_file(files[base + i], m, want_text, res[i], chroms); });
         for (size_t i = 0; i < n; ++i)
             if (res[i].st) return fail(res[i].st, res[i].err);
         gtars_status st = sink(base, res);
         if (st) return st;
     }
+    return GTARS_OK;
+}
+
+// ------------------------------------------------------------ the fused pipeline (fragsplit + tokenize): one route per call
+// A call runs wholly on one of two routes.  DEVICE: the host threads only inflate; line splitting, field parsing, barcode and
+// chromosome lookup, the grouping by cluster and the tokenizer run on the GPU (fragparse.hip).  HOST: the host threads parse and
+// route as well, and the device tokenizes.  Either way the files travel in waves through a WaveQueue, so that a wave is on the
+// device while the next one is being read.
+
+thread_local double g_frag_stages[12];  // gtars_fragsplit_last_stages
+
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// Where a call's time went, filled by either route: the twelve doubles of gtars_fragsplit_last_stages (bench.py's stage report)
+// and, with GTARS_HOST_TIMING, the stderr lines (tools/fragsplit_bench.py).
+struct FragStages {
+    bool on_device = false;
+    uint64_t n_fragments = 0;
+    double t_enter = now_s(), t_begin = 0, t_split_done = 0, t_tok_done = 0;  // clock readings
+    double t_append = 0;              // host route: the per-cluster appends between two waves
+    double td[5] = {0, 0, 0, 0, 0};   // device route: the waves' five device stages
+    // t_tok: the wave workers' busy seconds
+    void publish(size_t n_files, size_t n_waves, size_t n_clusters, double t_tok) const {
+        const double t_end = now_s();
+        double *g = g_frag_stages;
+        g[0] = on_device ? 1 : 0;
+        g[1] = (double)n_waves;
+        g[2] = t_split_done - t_begin - t_append;  // read + inflate (host route: + parse + route)
+        g[3] = t_append;
+        g[4] = t_tok;
+        g[5] = t_tok_done - t_split_done;  // ... of which behind the last wave's files
+        g[6] = t_end - t_tok_done;         // regroup by barcode
+        for (int k = 0; k < 5; ++k) g[7 + k] = td[k];
+        if (!cfg_get("GTARS_HOST_TIMING")) return;
+        fprintf(stderr, "[gtars host timing] fragsplit_tokenize: %zu files in %zu wave(s), %s %.3f s, per-cluster append %.3f s, %s %.3f s (of which %.3f s after the last wave was read; %llu fragments), regroup of %zu clusters %.3f s\n",
+                n_files, n_waves, on_device ? "gunzip (host threads)" : "gunzip + parse + route", g[2], t_append,
+                on_device ? "device waves (text in, parse, group, tokenize, results out)" : "tokenizer calls", t_tok, g[5],
+                (unsigned long long)n_fragments, n_clusters, g[6]);
+        fprintf(stderr, "[gtars host timing]   since the call was entered: %.3f s (set-up before the first wave %.3f s)\n", t_end - t_enter, t_begin - t_enter);
+        if (on_device)
+            fprintf(stderr, "[gtars host timing]   device waves: text to the device %.3f s, line split + parse + sort by cluster %.3f s, gather %.3f s, tokenize %.3f s, results to the host %.3f s\n",
+                    td[0], td[1], td[2], td[3], td[4]);
+    }
+};
+
+// The waves of a call on their way through its worker threads: the producer pushes a wave and goes on reading while the workers
+// `run` the queued ones.  A Wave has `gtars_status st` and `std::string err`.  A worker lets no exception out: what run() throws
+// ends ITS wave with a status and a message -- the pipeline's one catch ladder -- and failed() tells the producer to stop.  The
+// workers are stopped and joined by close(), or by the destructor on any other way out; they finish what is queued first.
+template <class Wave>
+class WaveQueue {
+  public:
+    // `device`: the index's (HIP's current device belongs to the thread and starts at 0)
+    template <class Run>
+    WaveQueue(unsigned threads, int device, Run run)
+        : threads_(threads), workers_([this] {
+              std::lock_guard<std::mutex> lk(mu_);
+              closing_ = true;
+              cv_.notify_all();
+          }) {
+        workers_.start(threads, [this, device, run] { work(device, run); });
+    }
+    void push(Wave *w) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            jobs_.push_back(w);
+            ++in_flight_;
+        }
+        cv_.notify_all();
+    }
+    void wait_idle() {  // until a worker has nothing queued and nothing running
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return in_flight_ < threads_; });
+    }
+    bool failed() {  // a wave has ended with an error
+        std::lock_guard<std::mutex> lk(mu_);
+        return failed_;
+    }
+    void close() { workers_.stop_and_join(); }
+    double busy_seconds() const { return busy_; }  // the workers' time inside run(), all of them together; read after close()
+
+  private:
+    template <class Run>
+    void work(int device, const Run &run) noexcept {
+        (void)gtars::frag_select_device(device);
+        for (;;) {
+            Wave *w = nullptr;
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] { return closing_ || !jobs_.empty(); });
+                if (jobs_.empty()) return;
+                w = jobs_.front();
+                jobs_.pop_front();
+            }
+            const double t0 = now_s();
+            try {  // (run() allocates: an exception on this thread must end the wave with a status, not the process)
+                run(*w);
+            } catch (const std::bad_alloc &) {
+                end_with(*w, "out of host memory", "");
+            } catch (const std::exception &ex) {
+                end_with(*w, "internal error: ", ex.what());
+            }
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                busy_ += now_s() - t0;
+                --in_flight_;
+                if (w->st) failed_ = true;
+            }
+            cv_.notify_all();
+        }
+    }
+    static void end_with(Wave &w, const char *what, const char *detail) noexcept {
+        w.st = GTARS_ERR_INTERNAL;
+        try {
+            w.err = std::string(what) + detail;
+        } catch (...) {  // (no memory for the message either: the status stands)
+        }
+    }
+    const unsigned threads_;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::deque<Wave *> jobs_;
+    size_t in_flight_ = 0;  // waves queued or running
+    bool closing_ = false, failed_ = false;
+    double busy_ = 0;
+    gtars::JoinedThreads workers_;  // (the last member: joined before the state above goes)
+};
+
+// ---- the device route
+
+// a (file, barcode) run of regrouped ids in a device wave's answer: which line opens it, the file and the barcode's slot in the
+// file's table, where the run lies in the wave's id array
+struct FragRun {
+    uint32_t line, file, slot, start, len;
+};
+
+// One wave of the device route: the wave's files as text until the GPU has them, afterwards their barcode tables; and the answer.
+struct DeviceWave {
+    size_t first_file = 0;
+    std::vector<TextFile> tf;
+    gtars::FragWaveOut dev;  // the device's answer: ids regrouped by (file, barcode), where every run starts, which line opens it
+    // ... cut into its runs per cluster, in line order: made by the device thread that received the answer, while later waves are
+    // still inflating (round 6: this pass over every slot of every file ran on the calling thread behind the last wave --
+    // 11 ms of a 38-ms call on a folder of 1000 files)
+    std::vector<std::vector<FragRun>> runs;  // [n_clusters]
+    uint64_t n = 0, reads = 0;               // tokenized fragments, lines
+    double td[5] = {0, 0, 0, 0, 0};
+    gtars_status st = GTARS_OK;
+    std::string err;
+};
+
+// the answer's runs per cluster (they lie in slot order: one ends where the next present one starts), by line
+void cut_device_runs(DeviceWave &w, size_t nc) {
+    w.runs.assign(nc, {});
+    const gtars::FragWaveOut &d = w.dev;
+    if (!d.n) return;
+    size_t pc = nc, pi = 0;
+    for (uint32_t f = 0; f + 1 < (uint32_t)d.slot_off.size(); ++f)
+        for (uint32_t g = d.slot_off[f]; g < d.slot_off[f + 1]; ++g) {
+            const uint32_t st0 = d.run_start[g];
+            if (st0 == 0xFFFFFFFFu) continue;
+            if (pc < nc) w.runs[pc][pi].len = st0 - w.runs[pc][pi].start;
+            const uint32_t c = w.tf[f].slots[g - d.slot_off[f]].value;
+            w.runs[c].push_back(FragRun{d.run_line[g], f, g - d.slot_off[f], st0, 0});
+            pc = c, pi = w.runs[c].size() - 1;
+        }
+    if (pc < nc) w.runs[pc][pi].len = (uint32_t)d.n_ids - w.runs[pc][pi].start;
+    for (auto &rc : w.runs) std::sort(rc.begin(), rc.end(), [](const FragRun &a, const FragRun &b) { return a.line < b.line; });
+}
+
+// one wave through the device, on a worker of the route's queue
+void run_device_wave(const gtars_tokenizer *t, const gtars::FragChroms *d_chroms, const std::vector<std::string> &files,
+                     const gtars_barcode_map &m, DeviceWave &w) {
+    const size_t nc = m.labels.size();
+    std::vector<gtars::FragFileIn> in;
+    for (TextFile &f : w.tf)
+        in.push_back({f.data.data(), f.data.size(), f.slots.data(), (uint32_t)f.slots.size(), f.keys.data(), (uint32_t)f.keys.size(),
+                      f.members.data(), (uint32_t)f.members.size()});
+    gtars::FragWaveOut o;
+    w.st = gtars::frag_wave_device(t->index, d_chroms, in, (uint32_t)nc, t->unk_id, o);
+    if (w.st) {  // (GTARS_ERR_CAPACITY: more ids than the device route's 32-bit positions -- the whole call on the host route)
+        w.err = gtars_last_error();
+    } else if (o.first_error_file >= 0) {
+        // a line the reference fails on: its message from the host parser, on that one file
+        SplitFile again;
+        split_one_file(files[w.first_file + (size_t)o.first_error_file], m, false, again, &t->chroms);
+        w.st = again.st ? again.st : GTARS_ERR_INTERNAL;
+        w.err = again.st ? again.err : "fragment pipeline: the device parser rejected a line that the host parser accepts";
+    } else {
+        w.n = o.n;
+        for (uint64_t r : o.n_reads) w.reads += r;
+        w.td[0] = o.t_h2d, w.td[1] = o.t_parse, w.td[2] = o.t_group, w.td[3] = o.t_tok, w.td[4] = o.t_d2h;
+        w.dev = std::move(o);
+        cut_device_runs(w, nc);
+    }
+    for (TextFile &f : w.tf) f.data.release();  // the text is on the device (or no longer needed): the block back to the pool
+}
+
+// *redo_on_host: this input is not for the device route (a file beyond its text limit, a wave with more ids than its 32-bit
+// positions hold); the status returned is an error then
+gtars_status fragsplit_tokenize_device(const gtars_tokenizer *t, const std::vector<std::string> &files, const gtars_barcode_map *m,
+                                       gtars_fragment_tokens_t ***out, uint64_t *n_reads, bool *redo_on_host) {
+    *redo_on_host = false;
+    FragStages rep;
+    rep.on_device = true;
+    const size_t nc = m->labels.size();
+    gtars::FragChroms *d_chroms = nullptr;  // (the tokenizer's: calls of several threads on one tokenizer share it read-only)
+    if (const gtars_status e = t->device_chroms(&d_chroms)) return e;
+    const int device = t->device();  // the INDEX's device (round 5: the calling thread's current device)
+    rep.t_begin = now_s();
+    std::deque<DeviceWave> waves;
+    // TWO workers, each with a stream of its own (fragparse.hip): a batch's text goes to the device while the previous batch's
+    // kernels run and its results come back -- on one thread a batch is copy in, kernels, copy out, one after the other, 10.5 ms of
+    // device time per 48 files of which 5 are the text's way over PCIe.  (They sleep in their waits.)
+    const char *nth = cfg_get("GTARS_FRAG_DEVICE_THREADS");
+    WaveQueue<DeviceWave> queue((unsigned)std::max(1, std::min(4, atoi(nth ? nth : "2"))), device,
+                                [&](DeviceWave &w) { run_device_wave(t, d_chroms, files, *m, w); });
+    const char *cap_mb = cfg_get("GTARS_FRAG_DEVICE_WAVE_MB");  // (test hook: a small limit)
+    const uint64_t byte_limit = (cap_mb ? (uint64_t)atoll(cap_mb) : 3500ull) << 20;  // the device route's 32-bit text positions
+    bool too_large = false;
+    const gtars_status st = stream_text_files(
+        files, *m, byte_limit, device,
+        [&](size_t base, std::vector<TextFile> &tf) -> gtars_status {
+            waves.emplace_back();
+            DeviceWave &w = waves.back();
+            w.first_file = base;
+            w.tf = std::move(tf);
+            queue.push(&w);
+            return GTARS_OK;
+        },
+        [&] { queue.wait_idle(); }, [&] { return queue.failed(); }, &too_large);
+    *redo_on_host = too_large;
+    rep.t_split_done = now_s();
+    queue.close();
+    for (const DeviceWave &w : waves)
+        if (w.st == GTARS_ERR_CAPACITY) {
+            *redo_on_host = true;
+            return fail(GTARS_ERR_INTERNAL, "fragment pipeline: a device wave with more than 4e9 token ids");
+        }
+    for (const DeviceWave &w : waves)  // (in file order: a wave's error lies in front of whatever stopped the producer)
+        if (w.st) return fail(w.st, w.err);
+    if (st) return st;
+    rep.t_tok_done = now_s();
+    uint64_t reads = 0;
+    for (const DeviceWave &w : waves) {
+        reads += w.reads;
+        rep.n_fragments += w.n;
+        for (int k = 0; k < 5; ++k) rep.td[k] += w.td[k];
+    }
+    // Every cluster regrouped by barcode.  The waves arrive regrouped by (file, barcode) (FragWaveOut): what is left is, per cluster,
+    // the runs in the order their first lines appear -- wave after wave, and inside a wave by line number: the first-seen barcode
+    // order of one pass over the cluster's file -- a dictionary lookup per run (the same barcode string of several files is ONE
+    // barcode of the cluster) and a copy per run.
+    ClusterTokens arr = new_cluster_tokens(nc);
+    gtars::parallel_for(nc, host_thread_budget(64), 1, [&](size_t c) {
+        ViewDict barcodes;
+        size_t n_runs = 0;
+        for (const DeviceWave &w : waves) n_runs += w.runs[c].size();
+        std::vector<uint32_t> run_id;
+        run_id.reserve(n_runs);
+        std::vector<uint64_t> cnt{0};  // [barcode + 1]: its ids, then the inclusive sums
+        for (const DeviceWave &w : waves)
+            for (const FragRun &r : w.runs[c]) {
+                const TextFile &f = w.tf[r.file];
+                const gtars::FragSlot &sl = f.slots[r.slot];
+                const uint32_t id = barcodes.get_or_add(f.keys.data() + sl.off, sl.len);
+                if (id + 1 >= cnt.size()) cnt.resize((size_t)id + 2, 0);
+                cnt[id + 1] += r.len;
+                run_id.push_back(id);
+            }
+        for (size_t b = 1; b < cnt.size(); ++b) cnt[b] += cnt[b - 1];
+        FragmentTokensPtr ft = new_fragment_tokens(barcodes.names, cnt);
+        // (a barcode's runs in (wave, line) order = file order: the fragments of a cluster lie file after file)
+        std::vector<uint64_t> fill(cnt.begin(), cnt.end() - 1);
+        size_t x = 0;
+        for (const DeviceWave &w : waves) {
+            const uint32_t *src = w.dev.ids.get();
+            for (const FragRun &r : w.runs[c]) {
+                uint64_t &at = fill[run_id[x++]];
+                memcpy(ft->ids + at, src + r.start, (size_t)r.len * sizeof(uint32_t));
+                at += r.len;
+            }
+        }
+        arr.get()[c] = ft.release();
+    });
+    *out = arr.release();
+    if (n_reads) *n_reads = reads;
+    rep.publish(files.size(), waves.size(), nc, queue.busy_seconds());
+    return GTARS_OK;
+}
+
+// ---- the host route (GTARS_FRAG_HOST_PARSE=1: A/B and tests; and whatever the device route hands back)
+
+// one wave's routed fragments as tokenizer input, cluster after cluster, and what the tokenizer made of them
+struct HostWave {
+    std::vector<uint64_t> coff;  // [n_clusters + 1]
+    uint64_t n = 0;              // fragments
+    // columns and CSR offsets [n + 1]: plain allocations -- a std::vector would zero 20 bytes per fragment on the thread that
+    // sits between two waves (10 waves of 2.4M fragments: 60 of the 100 ms that stage took)
+    std::unique_ptr<uint32_t[]> c, s, e;
+    std::unique_ptr<uint64_t[]> off;
+    std::unique_ptr<uint32_t, GtarsFree> ids;  // the tokenizer's answer: released with the wave
+    gtars_status st = GTARS_OK;
+    std::string err;
+};
+
+gtars_status fragsplit_tokenize_host(const gtars_tokenizer *t, const std::vector<std::string> &files, const gtars_barcode_map *m,
+                                     gtars_fragment_tokens_t ***out, uint64_t *n_reads) {
+    FragStages rep;
+    const size_t nc = m->labels.size();
+    // per cluster: fragment columns in the order the cluster file would have them (files in order, lines in order),
+    // chromosome ids of the TOKENIZER's dictionary, barcode ids in first-seen order
+    struct Cluster {
+        std::vector<uint32_t> b;  // barcode ids (the cluster's first-seen order) of its fragments, wave after wave
+        ViewDict barcodes;
+    };
+    std::vector<Cluster> cl(nc);
+    std::deque<HostWave> waves;
+    uint64_t reads = 0;
+    rep.t_begin = now_s();
+    // The tokenizer calls (one per wave: copy in, kernel, copy out) run on ONE worker, so that a wave is tokenized while the next
+    // one is being inflated and parsed (folders of more files than one wave holds: the config's 10,000).
+    WaveQueue<HostWave> queue(1, t->device(), [&](HostWave &w) {
+        uint32_t *ids = nullptr;
+        uint64_t h = 0;
+        w.st = gtars_tokenize(t->index, w.c.get(), w.s.get(), w.e.get(), w.n, w.off.get(), &ids, &h);
+        w.ids.reset(ids);
+        if (w.st) w.err = gtars_last_error();
+    });
+    const gtars_status st = for_each_split_wave(files, *m, false, &t->chroms, [&](size_t, std::vector<SplitFile> &res) -> gtars_status {
+        const double t_a = now_s();
+        waves.emplace_back();
+        HostWave &w = waves.back();
+        w.coff.assign(nc + 1, 0);
+        for (size_t c = 0; c < nc; ++c) {
+            uint64_t add = 0;
+            for (SplitFile &f : res) add += f.cols[c].c.size();
+            w.coff[c + 1] = w.coff[c] + add;
+        }
+        const uint64_t n = w.n = w.coff[nc];
+        w.c.reset(new uint32_t[n + 1]);
+        w.s.reset(new uint32_t[n + 1]);
+        w.e.reset(new uint32_t[n + 1]);
+        w.off.reset(new uint64_t[n + 1]);
+        w.off[0] = 0;  // (a wave without routed fragments is not sent to the tokenizer)
+        // the wave's files, in file order, behind every cluster: column copies; the file-local barcode ids mapped through the
+        // cluster's dictionary (one lookup per distinct barcode of a file, in its first-seen order, so the cluster's order is
+        // what one pass over the cluster file would see)
+        gtars::parallel_for(nc, host_thread_budget(64), 1, [&](size_t c) {
+            Cluster &k = cl[c];
+            k.b.reserve(k.b.size() + (size_t)(w.coff[c + 1] - w.coff[c]));
+            uint64_t at = w.coff[c];
+            std::vector<uint32_t> map;
+            for (SplitFile &f : res) {
+                SplitFile::Cols &q = f.cols[c];
+                map.resize(q.barcodes.names.size());
+                for (size_t i = 0; i < map.size(); ++i) map[i] = k.barcodes.get_or_add(q.barcodes.names[i].data(), q.barcodes.names[i].size());
+                std::copy(q.c.begin(), q.c.end(), w.c.get() + at);
+                std::copy(q.s.begin(), q.s.end(), w.s.get() + at);
+                std::copy(q.e.begin(), q.e.end(), w.e.get() + at);
+                at += q.c.size();
+                for (uint32_t lb : q.b) k.b.push_back(map[lb]);
+            }
+        });
+        for (SplitFile &f : res) reads += f.n_reads;
+        rep.n_fragments += n;
+        if (n) queue.push(&w);
+        rep.t_append += now_s() - t_a;
+        return GTARS_OK;
+    });
+    rep.t_split_done = now_s();
+    queue.close();
+    for (const HostWave &w : waves)  // (in file order: a wave's error lies in front of whatever stopped the producer)
+        if (w.st) return fail(w.st, w.err);
+    if (st) return st;
+    rep.t_tok_done = now_s();
+    // every cluster regrouped by barcode: its fragments' ids wave after wave (= the cluster file's line order)
+    ClusterTokens arr = new_cluster_tokens(nc);
+    gtars::parallel_for(nc, host_thread_budget(64), 1, [&](size_t c) {
+        const Cluster &k = cl[c];
+        arr.get()[c] = tokens_by_barcode(k.barcodes.names, t->unk_id, [&](auto &&f) {
+                           uint64_t i = 0;
+                           for (const HostWave &w : waves)
+                               for (uint64_t r = w.coff[c]; r < w.coff[c + 1]; ++r, ++i) f(k.b[i], w.ids.get() + w.off[r], w.off[r + 1] - w.off[r]);
+                       }).release();
+    });
+    *out = arr.release();
+    if (n_reads) *n_reads = reads;
+    rep.publish(files.size(), waves.size(), nc, queue.busy_seconds());
     return GTARS_OK;
 }
 
@@ -3987,18 +4328,11 @@ static gtars_status gtars_fragsplit_impl(const char *files_dir, const gtars_barc
     uint64_t reads = 0, written = 0;
     st = for_each_split_wave(files, *m, true, nullptr, [&](size_t, std::vector<SplitFile> &res) -> gtars_status {
         // every cluster's stream is compressed by one thread per wave, the wave's files in order
-        std::atomic<size_t> next{0};
         std::atomic<int> bad{0};
-        auto work = [&] {
-            for (size_t c = next.fetch_add(1); c < nc; c = next.fetch_add(1))
-                for (SplitFile &f : res)
-                    if (!f.text[c].empty() && gzwrite(outs[c], f.text[c].data(), (unsigned)f.text[c].size()) <= 0) bad = 1;
-        };
-        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_thread_budget(64), nc));
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < nt; ++k) th.emplace_back(work);
-        work();
-        for (auto &t : th) t.join();
+        gtars::parallel_for(nc, host_thread_budget(64), 1, [&](size_t c) {
+            for (SplitFile &f : res)
+                if (!f.text[c].empty() && gzwrite(outs[c], f.text[c].data(), (unsigned)f.text[c].size()) <= 0) bad = 1;
+        });
         for (SplitFile &f : res) {
             reads += f.n_reads;
             written += f.n_written;
@@ -4012,431 +4346,22 @@ static gtars_status gtars_fragsplit_impl(const char *files_dir, const gtars_barc
     return GTARS_OK;
 }
 
-// the pipeline over an explicit list of files, visited in the order given (the directory form passes its regular files in byte
-// order of their names; a rank of the sharded driver passes its run of that list)
-static thread_local double g_frag_stages[12];
 void gtars_fragsplit_last_stages(double *out12) {
     if (out12) memcpy(out12, g_frag_stages, sizeof g_frag_stages);
 }
 
-static gtars_status fragsplit_tokenize_mode(const gtars_tokenizer_t *t, const std::vector<std::string> &files, const gtars_barcode_map_t *m,
-                                            gtars_fragment_tokens_t ***out, uint64_t *n_reads, bool allow_device, bool *redo_on_host);
-
+// the pipeline over an explicit list of files, visited in the order given (the directory form passes its regular files in byte
+// order of their names; a rank of the sharded driver passes its run of that list)
 static gtars_status fragsplit_tokenize_core(const gtars_tokenizer_t *t, const std::vector<std::string> &files, const gtars_barcode_map_t *m,
                                             gtars_fragment_tokens_t ***out, uint64_t *n_reads) {
-    bool redo = false;
-    gtars_status st = fragsplit_tokenize_mode(t, files, m, out, n_reads, true, &redo);
-    // (a wave of more than 3.5 GiB of text -- beyond the device parser's 32-bit positions: the whole call on the host parser)
-    if (redo) st = fragsplit_tokenize_mode(t, files, m, out, n_reads, false, &redo);
-    return st;
-}
-
-static gtars_status fragsplit_tokenize_mode(const gtars_tokenizer_t *t, const std::vector<std::string> &files, const gtars_barcode_map_t *m,
-                                            gtars_fragment_tokens_t ***out, uint64_t *n_reads, bool allow_device, bool *redo_on_host) {
-    gtars_status st = GTARS_OK;
-    *redo_on_host = false;
-    const double t_enter = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    const size_t nc = m->labels.size();
-    // per cluster: fragment columns in the order the cluster file would have them (files in order, lines in order),
-    // chromosome ids of the TOKENIZER's dictionary, barcode ids in first-seen order
-    struct Cluster {
-        std::vector<uint32_t> b;  // barcode ids (the cluster's first-seen order) of its fragments, wave after wave
-        ViewDict barcodes;
-    };
-    // a (file, barcode) run of regrouped ids in a device wave's answer: which line opens it, the file and the barcode's slot in the
-    // file's table, where the run lies in the wave's id array
-    struct Run {
-        uint32_t line, file, slot, start, len;
-    };
-    // one wave's routed fragments as tokenizer input, cluster after cluster, and what the tokenizer made of them
-    struct Wave {
-        std::vector<uint64_t> coff;     // [n_clusters + 1]
-        uint64_t n = 0;                 // fragments
-        // columns and CSR offsets [n + 1]: plain allocations -- a std::vector would zero 20 bytes per fragment on the thread that
-        // sits between two waves (10 waves of 2.4M fragments: 60 of the 100 ms that stage took)
-        std::unique_ptr<uint32_t[]> c, s, e;
-        std::unique_ptr<uint64_t[]> off;
-        uint32_t *ids = nullptr;
-        gtars_status st = GTARS_OK;
-        std::string err;
-        // device path (fragparse.hip): the wave's files as text until the GPU has them, afterwards their barcode tables; file and
-        // barcode slot of every tokenized fragment (cluster-major like the CSR)
-        bool device = false;
-        size_t first_file = 0;
-        std::vector<TextFile> tf;
-        gtars::FragWaveOut dev;  // the device's answer: ids regrouped by (file, barcode), where every run starts, which line opens it
-        // ... cut into its runs per cluster, in line order: made by the device thread that received the answer, while later waves are
-        // still inflating (round 6: this pass over every slot of every file ran on the calling thread behind the last wave --
-        // 11 ms of a 38-ms call on a folder of 1000 files)
-        std::vector<std::vector<Run>> runs;
-        uint64_t reads = 0;
-        double td[5] = {0, 0, 0, 0, 0};
-    };
-    std::vector<Cluster> cl(nc);
-    std::deque<Wave> waves;
-    // The device path: the host threads only inflate; line splitting, field parsing, barcode and chromosome lookup, the grouping by
-    // cluster and the tokenizer run on the GPU (fragparse.hip).  GTARS_FRAG_HOST_PARSE=1 keeps round 4's host parse (A/B, tests).
-    const bool device_path = allow_device && !cfg_get("GTARS_FRAG_HOST_PARSE") && nc < 65000;
-    gtars::FragChroms *d_chroms = nullptr;  // (the tokenizer's: calls of several threads on one tokenizer share it read-only)
-    if (device_path) {
-        st = t->device_chroms(&d_chroms);
-        if (st) return st;
+    // (the device route takes fewer than 65,000 clusters: fragparse.hip's NO_CLUSTER)
+    if (!cfg_get("GTARS_FRAG_HOST_PARSE") && m->labels.size() < 65000) {
+        bool redo = false;
+        const gtars_status st = fragsplit_tokenize_device(t, files, m, out, n_reads, &redo);
+        // (a file of more than 3.5 GiB of text, or a wave of more than 4e9 ids -- beyond the device route's 32-bit positions)
+        if (!redo) return st;
     }
-    const int pipeline_device = t->device();  // the INDEX's device (round 5: the calling thread's current device)
-    uint64_t reads = 0, n_all = 0;
-    const bool timing = cfg_get("GTARS_HOST_TIMING") != nullptr;  // stderr: seconds per stage (tools/fragsplit_bench.py)
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    double t_append = 0, t_tok = 0;
-    auto over_clusters = [&](auto &&body) {  // body(c) for every cluster, on up to 64 threads
-        std::atomic<size_t> next{0};
-        auto work = [&] {
-            for (size_t c = next.fetch_add(1); c < nc; c = next.fetch_add(1)) body(c);
-        };
-        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_thread_budget(64), nc));
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < nt; ++k) th.emplace_back(work);
-        work();
-        for (auto &tt : th) tt.join();
-    };
-    // The tokenizer calls (one per wave: copy in, kernel, copy out) run on ONE helper thread, so that a wave is tokenized while
-    // the next one is being inflated and parsed (folders of more files than one wave holds: the config's 10,000).
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Wave *> jobs;
-    bool closing = false;
-    bool device_overflow = false;  // a device wave with more than 4e9 ids
-    size_t in_flight = 0;       // waves queued or on the device
-    bool wave_failed = false;   // a wave ended with an error (the producer stops)
-    auto tok_body = [&] {
-        (void)gtars::frag_select_device(pipeline_device);  // (HIP's current device belongs to the thread and starts at 0)
-        for (;;) {
-            Wave *w = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return closing || !jobs.empty(); });
-                if (jobs.empty()) return;
-                w = jobs.front();
-                jobs.pop_front();
-            }
-            const double t0 = now();
-            try {  // (the body allocates: an exception on this thread must end the wave with a status, not the process)
-            if (w->device) {
-                std::vector<gtars::FragFileIn> in;
-                for (TextFile &f : w->tf) {
-                    gtars::FragFileIn x;
-                    x.text = f.data.data();
-                    x.n = f.data.size();
-                    x.slots = f.slots.data();
-                    x.n_slots = (uint32_t)f.slots.size();
-                    x.keys = f.keys.data();
-                    x.n_key_bytes = (uint32_t)f.keys.size();
-                    x.members = f.members.data();
-                    x.n_members = (uint32_t)f.members.size();
-                    in.push_back(x);
-                }
-                gtars::FragWaveOut o;
-                w->st = gtars::frag_wave_device(t->index, d_chroms, in, (uint32_t)nc, t->unk_id, o);
-                if (w->st == GTARS_ERR_CAPACITY) {  // more ids than the device path's 32-bit positions: the whole call on the host parser
-                    std::lock_guard<std::mutex> lk(mu);
-                    device_overflow = true;
-                }
-                if (w->st) {
-                    w->err = gtars_last_error();
-                } else if (o.first_error_file >= 0) {
-                    // a line the reference fails on: its message from the host parser, on that one file
-                    SplitFile again;
-                    split_one_file(files[w->first_file + (size_t)o.first_error_file], *m, false, again, &t->chroms);
-                    w->st = again.st ? again.st : GTARS_ERR_INTERNAL;
-                    w->err = again.st ? again.err : "fragment pipeline: the device parser rejected a line that the host parser accepts";
-                } else {
-                    w->n = o.n;
-                    for (uint64_t r : o.n_reads) w->reads += r;
-                    w->td[0] = o.t_h2d, w->td[1] = o.t_parse, w->td[2] = o.t_group, w->td[3] = o.t_tok, w->td[4] = o.t_d2h;
-                    w->dev = std::move(o);
-                    // the wave's runs per cluster (they lie in slot order: one ends where the next present one starts), by line
-                    w->runs.assign(nc, {});
-                    const gtars::FragWaveOut &d = w->dev;
-                    if (d.n) {
-                        size_t pc = nc, pi = 0;
-                        for (uint32_t f = 0; f + 1 < (uint32_t)d.slot_off.size(); ++f)
-                            for (uint32_t g = d.slot_off[f]; g < d.slot_off[f + 1]; ++g) {
-                                const uint32_t st0 = d.run_start[g];
-                                if (st0 == 0xFFFFFFFFu) continue;
-                                if (pc < nc) w->runs[pc][pi].len = st0 - w->runs[pc][pi].start;
-                                const uint32_t c = w->tf[f].slots[g - d.slot_off[f]].value;
-                                w->runs[c].push_back(Run{d.run_line[g], f, g - d.slot_off[f], st0, 0});
-                                pc = c, pi = w->runs[c].size() - 1;
-                            }
-                        if (pc < nc) w->runs[pc][pi].len = (uint32_t)d.n_ids - w->runs[pc][pi].start;
-                        for (auto &rc : w->runs) std::sort(rc.begin(), rc.end(), [](const Run &a, const Run &b) { return a.line < b.line; });
-                    }
-                }
-                for (TextFile &f : w->tf) f.data.release();  // the text is on the device (or no longer needed): the block back to the pool
-            } else {
-                uint64_t h = 0;
-                w->st = gtars_tokenize(t->index, w->c.get(), w->s.get(), w->e.get(), w->n, w->off.get(), &w->ids, &h);
-                if (w->st) w->err = gtars_last_error();
-            }
-            } catch (const std::bad_alloc &) {
-                w->st = GTARS_ERR_INTERNAL;
-                w->err = "out of host memory";
-            } catch (const std::exception &ex) {
-                w->st = GTARS_ERR_INTERNAL;
-                try {
-                    w->err = std::string("internal error: ") + ex.what();
-                } catch (...) {
-                }
-            }
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                t_tok += now() - t0;
-                --in_flight;
-                if (w->st) wave_failed = true;
-            }
-            cv.notify_all();
-        }
-    };
-    // The device path runs TWO of these threads, each with a stream of its own (fragparse.hip): a batch's text goes to the device
-    // while the previous batch's kernels run and its results come back -- on one thread a batch is copy in, kernels, copy out, one
-    // after the other, 10.5 ms of device time per 48 files of which 5 are the text's way over PCIe.  (They sleep in their waits.)
-    const unsigned n_tok_threads = device_path ? (unsigned)std::max(1, std::min(4, atoi(cfg_get("GTARS_FRAG_DEVICE_THREADS") ? cfg_get("GTARS_FRAG_DEVICE_THREADS") : "2"))) : 1u;
-    std::vector<std::thread> tok_threads;
-    for (unsigned q = 0; q < n_tok_threads; ++q) tok_threads.emplace_back(tok_body);
-    auto finish_tokenizer = [&] {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            closing = true;
-        }
-        cv.notify_all();
-        for (auto &th : tok_threads)
-            if (th.joinable()) th.join();
-    };
-    struct AtExit {  // (an exception on the way -- out of memory -- must not meet a joinable thread)
-        std::function<void()> f;
-        ~AtExit() { f(); }
-    } join_at_exit{finish_tokenizer};
-    auto free_waves = [&] {
-        for (Wave &w : waves)
-            if (!w.device) gtars_free(w.ids);  // (a device wave's ids lie in a block of the pinned pool: Wave::dids)
-    };
-    auto host_sink = [&](size_t, std::vector<SplitFile> &res) -> gtars_status {
-        const double t_a = now();
-        waves.emplace_back();
-        Wave &w = waves.back();
-        w.coff.assign(nc + 1, 0);
-        for (size_t c = 0; c < nc; ++c) {
-            uint64_t add = 0;
-            for (SplitFile &f : res) add += f.cols[c].c.size();
-            w.coff[c + 1] = w.coff[c] + add;
-        }
-        const uint64_t n = w.n = w.coff[nc];
-        w.c.reset(new uint32_t[n + 1]);
-        w.s.reset(new uint32_t[n + 1]);
-        w.e.reset(new uint32_t[n + 1]);
-        w.off.reset(new uint64_t[n + 1]);
-        w.off[0] = 0;  // (a wave without routed fragments is not sent to the tokenizer)
-        // the wave's files, in file order, behind every cluster: column copies; the file-local barcode ids mapped through the
-        // cluster's dictionary (one lookup per distinct barcode of a file, in its first-seen order, so the cluster's order is
-        // what one pass over the cluster file would see)
-        over_clusters([&](size_t c) {
-            Cluster &k = cl[c];
-            k.b.reserve(k.b.size() + (size_t)(w.coff[c + 1] - w.coff[c]));
-            uint64_t at = w.coff[c];
-            std::vector<uint32_t> map;
-            for (SplitFile &f : res) {
-                SplitFile::Cols &q = f.cols[c];
-                map.resize(q.barcodes.names.size());
-                for (size_t i = 0; i < map.size(); ++i) map[i] = k.barcodes.get_or_add(q.barcodes.names[i].data(), q.barcodes.names[i].size());
-                std::copy(q.c.begin(), q.c.end(), w.c.get() + at);
-                std::copy(q.s.begin(), q.s.end(), w.s.get() + at);
-                std::copy(q.e.begin(), q.e.end(), w.e.get() + at);
-                at += q.c.size();
-                for (uint32_t lb : q.b) k.b.push_back(map[lb]);
-            }
-        });
-        for (SplitFile &f : res) reads += f.n_reads;
-        n_all += n;
-        if (n) {
-            std::lock_guard<std::mutex> lk(mu);
-            jobs.push_back(&w);
-            ++in_flight;
-        }
-        cv.notify_all();
-        t_append += now() - t_a;
-        return GTARS_OK;
-    };
-    if (!device_path) {
-        st = for_each_split_wave(files, *m, false, &t->chroms, host_sink);
-    } else {
-        const char *cap_mb = cfg_get("GTARS_FRAG_DEVICE_WAVE_MB");  // (test hook: a small limit)
-        const uint64_t byte_limit = (cap_mb ? (uint64_t)atoll(cap_mb) : 3500ull) << 20;  // the device path's 32-bit text positions
-        bool too_large = false;
-        st = stream_text_files(
-            files, *m, byte_limit, pipeline_device,
-            [&](size_t base, std::vector<TextFile> &tf) -> gtars_status {
-                waves.emplace_back();
-                Wave &w = waves.back();
-                w.device = true;
-                w.first_file = base;
-                w.tf = std::move(tf);
-                w.coff.assign(nc + 1, 0);
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    jobs.push_back(&w);
-                    ++in_flight;
-                }
-                cv.notify_all();
-                return GTARS_OK;
-            },
-            [&] {  // a device thread has nothing queued and nothing running
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return in_flight < n_tok_threads; });
-            },
-            [&] {
-                std::lock_guard<std::mutex> lk(mu);
-                return wave_failed;
-            },
-            &too_large);
-        if (too_large) *redo_on_host = true;
-    }
-    const double t_split_done = now();
-    finish_tokenizer();
-    if (device_overflow) {
-        free_waves();
-        *redo_on_host = true;
-        return fail(GTARS_ERR_INTERNAL, "fragment pipeline: a device wave with more than 4e9 token ids");
-    }
-    for (Wave &w : waves)  // (in file order: a wave's error lies in front of whatever stopped the producer)
-        if (w.st) {
-            const gtars_status e = w.st;
-            const std::string msg = w.err;
-            free_waves();
-            return fail(e, msg);
-        }
-    if (st) {
-        const std::string msg = gtars_last_error();
-        free_waves();
-        return fail(st, msg);
-    }
-    const double t_tok_done = now();
-    if (device_path)
-        for (Wave &w : waves)
-            if (w.device) {
-                reads += w.reads;
-                n_all += w.n;
-            }
-    // every cluster regrouped by barcode: its fragments' ids wave after wave (= the cluster file's line order)
-    auto **arr = (gtars_fragment_tokens_t **)calloc(nc ? nc : 1, sizeof(gtars_fragment_tokens_t *));
-    // Device waves arrive regrouped by (file, barcode) (FragWaveOut): what is left is, per cluster, the runs in the order their first
-    // lines appear -- wave after wave, and inside a wave by line number: the first-seen barcode order of one pass over the cluster's
-    // file -- a dictionary lookup per run (the same barcode string of several files is ONE barcode of the cluster) and a copy per run.
-    std::vector<Wave *> wave_at;
-    for (Wave &w : waves) wave_at.push_back(&w);
-    over_clusters([&](size_t c) {
-        Cluster &k = cl[c];
-        std::vector<uint64_t> cnt;
-        uint64_t i = 0;
-        std::vector<uint32_t> run_id;
-        if (device_path) {
-            // the cluster's runs wave after wave, inside a wave by line: the first-seen barcode order of one pass over its file
-            size_t n_runs = 0;
-            for (Wave *w : wave_at)
-                if (w->device && c < w->runs.size()) n_runs += w->runs[c].size();
-            run_id.reserve(n_runs);
-            std::vector<uint64_t> per;
-            for (Wave *w : wave_at) {
-                if (!w->device || c >= w->runs.size()) continue;
-                for (const Run &r : w->runs[c]) {
-                    const TextFile &f = w->tf[r.file];
-                    const gtars::FragSlot &sl = f.slots[r.slot];
-                    const uint32_t id = k.barcodes.get_or_add(f.keys.data() + sl.off, sl.len);
-                    if (id >= per.size()) per.resize((size_t)id + 1, 0);
-                    per[id] += r.len;
-                    run_id.push_back(id);
-                }
-            }
-            cnt.assign(per.size() + 1, 0);
-            for (size_t b = 0; b < per.size(); ++b) cnt[b + 1] = per[b];
-        }
-        const uint64_t nb = k.barcodes.names.size();
-        if (!device_path) {
-            cnt.assign(nb + 1, 0);
-            for (Wave &w : waves)
-                for (uint64_t r = w.coff[c]; r < w.coff[c + 1]; ++r, ++i) {
-                    const uint64_t hits = w.off[r + 1] - w.off[r];
-                    cnt[k.b[i] + 1] += hits ? hits : 1;  // a fragment without hits contributes one unk id
-                }
-        }
-        for (uint64_t b = 0; b < nb; ++b) cnt[b + 1] += cnt[b];
-        auto *ft = (gtars_fragment_tokens_t *)calloc(1, sizeof(gtars_fragment_tokens_t));
-        ft->n_barcodes = nb;
-        ft->barcodes = (char **)calloc(nb ? nb : 1, sizeof(char *));
-        ft->offsets = (uint64_t *)malloc((nb + 1) * sizeof(uint64_t));
-        ft->ids = (uint32_t *)malloc((cnt[nb] ? cnt[nb] : 1) * sizeof(uint32_t));
-        memcpy(ft->offsets, cnt.data(), (nb + 1) * sizeof(uint64_t));
-        for (uint64_t b = 0; b < nb; ++b) ft->barcodes[b] = dup_cstr(k.barcodes.names[b]);
-        std::vector<uint64_t> fill(cnt.begin(), cnt.end() - 1);
-        if (device_path) {
-            // (a barcode's runs in (wave, line) order = file order: the fragments of a cluster lie file after file)
-            size_t x = 0;
-            for (Wave *w : wave_at) {
-                if (!w->device || c >= w->runs.size()) continue;
-                const uint32_t *src = w->dev.ids.get();
-                for (const Run &r : w->runs[c]) {
-                    uint64_t &at = fill[run_id[x++]];
-                    memcpy(ft->ids + at, src + r.start, (size_t)r.len * sizeof(uint32_t));
-                    at += r.len;
-                }
-            }
-            arr[c] = ft;
-            return;
-        }
-        i = 0;
-        for (Wave &w : waves) {
-            for (uint64_t r = w.coff[c]; r < w.coff[c + 1]; ++r, ++i) {
-                uint64_t &at = fill[k.b[i]];
-                if (w.off[r + 1] == w.off[r]) {
-                    ft->ids[at++] = t->unk_id;
-                } else {
-                    for (uint64_t y = w.off[r]; y < w.off[r + 1]; ++y) ft->ids[at++] = w.ids[y];
-                }
-            }
-        }
-        arr[c] = ft;
-    });
-    free_waves();
-    *out = arr;
-    if (n_reads) *n_reads = reads;
-    {
-        // the stages of this call, for gtars_fragsplit_last_stages (bench.py's stage report)
-        double *g = g_frag_stages;
-        for (int k = 0; k < 12; ++k) g[k] = 0;
-        g[0] = device_path ? 1 : 0;
-        g[1] = (double)waves.size();
-        g[2] = t_split_done - t_begin - t_append;  // read + inflate (host path: + parse + route)
-        g[3] = t_append;
-        g[4] = t_tok;
-        g[5] = t_tok_done - t_split_done;  // ... of which behind the last wave's files
-        g[6] = now() - t_tok_done;         // regroup by barcode
-        for (Wave &w : waves)
-            for (int k = 0; k < 5; ++k) g[7 + k] += w.td[k];
-    }
-    if (timing) {
-        fprintf(stderr, "[gtars host timing] fragsplit_tokenize: %zu files in %zu wave(s), %s %.3f s, per-cluster append %.3f s, %s %.3f s (of which %.3f s after the last wave was read; %llu fragments), regroup of %zu clusters %.3f s\n",
-                files.size(), waves.size(), device_path ? "gunzip (host threads)" : "gunzip + parse + route", t_split_done - t_begin - t_append,
-                t_append, device_path ? "device waves (text in, parse, group, tokenize, results out)" : "tokenizer calls", t_tok,
-                t_tok_done - t_split_done, (unsigned long long)n_all, nc, now() - t_tok_done);
-        fprintf(stderr, "[gtars host timing]   since the call was entered: %.3f s (set-up before the first wave %.3f s)\n", now() - t_enter, t_begin - t_enter);
-        if (device_path) {
-            double td[5] = {0, 0, 0, 0, 0};
-            for (Wave &w : waves)
-                for (int k = 0; k < 5; ++k) td[k] += w.td[k];
-            fprintf(stderr, "[gtars host timing]   device waves: text to the device %.3f s, line split + parse + sort by cluster %.3f s, gather %.3f s, tokenize %.3f s, results to the host %.3f s\n",
-                    td[0], td[1], td[2], td[3], td[4]);
-        }
-    }
-    return GTARS_OK;
+    return fragsplit_tokenize_host(t, files, m, out, n_reads);
 }
 
 static gtars_status gtars_fragsplit_tokenize_impl(const gtars_tokenizer_t *t, const char *files_dir, const gtars_barcode_map_t *m,
@@ -4527,6 +4452,24 @@ gtars_status gtars_bed3_lines_read(const char *path, gtars_fragments_t **out) {
     });
 }
 
+namespace {
+inline void put_u32(std::string &text, uint32_t v) {
+    char buf[16];
+    int k = 0;
+    do { buf[k++] = (char)('0' + v % 10); v /= 10; } while (v);
+    while (k) text.push_back(buf[--k]);
+}
+gtars_status give_text(const std::string &text, char **out_text, uint64_t *out_len) {
+    char *p = (char *)malloc(text.size() + 1);
+    if (!p) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    memcpy(p, text.data(), text.size());
+    p[text.size()] = 0;
+    *out_text = p;
+    *out_len = text.size();
+    return GTARS_OK;
+}
+}  // namespace
+
 // one line  chr<TAB>start<TAB>end  per hit (handlers.rs:141-150), `n` hits, into a malloc'ed buffer (gtars_free)
 gtars_status gtars_format_hit_lines(const char *const *chrom_names, const uint32_t *hit_chrom, const uint32_t *hit_start,
                                     const uint32_t *hit_end, uint64_t n, char **out_text, uint64_t *out_len) {
@@ -4535,27 +4478,15 @@ gtars_status gtars_format_hit_lines(const char *const *chrom_names, const uint32
             return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
         std::string text;
         text.reserve((size_t)n * 24);
-        char buf[16];
-        auto put_u32 = [&](uint32_t v) {
-            int k = 0;
-            do { buf[k++] = (char)('0' + v % 10); v /= 10; } while (v);
-            while (k) text.push_back(buf[--k]);
-        };
         for (uint64_t i = 0; i < n; ++i) {
             text += chrom_names[hit_chrom[i]];
             text.push_back('\t');
-            put_u32(hit_start[i]);
+            put_u32(text, hit_start[i]);
             text.push_back('\t');
-            put_u32(hit_end[i]);
+            put_u32(text, hit_end[i]);
             text.push_back('\n');
         }
-        char *p = (char *)malloc(text.size() + 1);
-        if (!p) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-        memcpy(p, text.data(), text.size());
-        p[text.size()] = 0;
-        *out_text = p;
-        *out_len = text.size();
-        return GTARS_OK;
+        return give_text(text, out_text, out_len);
     });
 }
 
@@ -4602,24 +4533,6 @@ gtars_status gtars_uniwig_nonzero(const uint32_t *opens, const uint32_t *closes,
         return gtars::uniwig_nonzero(opens, closes, n, chrom_size, smoothsize, kind, start_position, position, count, n_out);
     });
 }
-
-namespace {
-inline void put_u32(std::string &text, uint32_t v) {
-    char buf[16];
-    int k = 0;
-    do { buf[k++] = (char)('0' + v % 10); v /= 10; } while (v);
-    while (k) text.push_back(buf[--k]);
-}
-gtars_status give_text(const std::string &text, char **out_text, uint64_t *out_len) {
-    char *p = (char *)malloc(text.size() + 1);
-    if (!p) return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    memcpy(p, text.data(), text.size());
-    p[text.size()] = 0;
-    *out_text = p;
-    *out_len = text.size();
-    return GTARS_OK;
-}
-}  // namespace
 
 gtars_status gtars_uniwig_format_counts(const uint32_t *counts, uint64_t n, char **out_text, uint64_t *out_len) {
     return gtars::guarded([&]() -> gtars_status {

@@ -17,17 +17,16 @@
 // with the reference to floating-point tolerance only (statrs unpinned; the reference's own Brent solve stops
 // at an absolute 1e-8 in omega).
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <limits>
 #include <numeric>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
+#include "host_threads.h"
 
 namespace gtars {
 gtars_status fail(gtars_status st, const std::string &msg);
@@ -223,28 +222,6 @@ inline bool f64_tied(double a, double b) {
 // own order is unspecified there; pValueLog is never NaN on this path)
 inline bool desc_before(double a, double b) { return a > b; }
 
-// f(i) for i in [0, n) on the process's host threads, `chunk` indices at a time (tables differ a lot in cost: small dynamic chunks)
-template <class F>
-void parallel_for(size_t n, size_t chunk, F &&f) {
-    const unsigned nt = (unsigned)std::min<size_t>(gtars_host_threads(64), (n + chunk - 1) / chunk);
-    if (nt <= 1) {
-        for (size_t i = 0; i < n; ++i) f(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    std::vector<std::thread> th;
-    auto body = [&]() {
-        for (;;) {
-            const size_t i0 = next.fetch_add(chunk);
-            if (i0 >= n) return;
-            for (size_t i = i0; i < std::min(n, i0 + chunk); ++i) f(i);
-        }
-    };
-    for (unsigned t = 1; t < nt; ++t) th.emplace_back(body);
-    body();
-    for (auto &x : th) x.join();
-}
-
 // rank_results on one user set's rows (enrichment.rs:353-394): ONE index vector re-sorted three times (stable sorts: ties keep
 // the previous sort's order, as the reference's do), min-ranks, then the combined ranks
 void rank_rows(const double *pv, const double *orr, const uint64_t *sup, size_t n, uint32_t *rnk_pv, uint32_t *rnk_or,
@@ -349,7 +326,9 @@ extern "C" gtars_status gtars_lola_stats(const int64_t *a, const int64_t *b, con
         const size_t total = (size_t)(n_db * n_user_sets);
         const bool enrichment = direction == 0;
         // values (enrichment.rs:226-247): a table with a negative cell gets pValueLog 0 and oddsRatio NaN
-        parallel_for(total, 8, [&](size_t i) {
+        // (tables differ a lot in cost: small dynamic chunks of 8)
+        const unsigned threads = gtars_host_threads(64);
+        gtars::parallel_for(total, threads, 8, [&](size_t i) {
             if (a[i] < 0 || b[i] < 0 || c[i] < 0 || d[i] < 0) {
                 p_value_log[i] = 0.0;
                 odds[i] = std::numeric_limits<double>::quiet_NaN();
@@ -360,7 +339,7 @@ extern "C" gtars_status gtars_lola_stats(const int64_t *a, const int64_t *b, con
             odds[i] = odds_ratio(ua, ub, uc, ud);
         });
         if (!want_ranks) return GTARS_OK;
-        parallel_for((size_t)n_user_sets, 1, [&](size_t us) {
+        gtars::parallel_for((size_t)n_user_sets, threads, 1, [&](size_t us) {
             const size_t base = us * (size_t)n_db;
             // support is u64 in the reference (a count: never negative)
             rank_rows(p_value_log + base, odds + base, reinterpret_cast<const uint64_t *>(a) + base, (size_t)n_db, rnk_pv + base,
@@ -379,7 +358,7 @@ extern "C" gtars_status gtars_lola_stats(const int64_t *a, const int64_t *b, con
         std::vector<std::vector<uint64_t>> by_set((size_t)n_user_sets);
         for (auto &v : by_set) v.reserve((size_t)n_db);
         for (size_t r = 0; r < total; ++r) by_set[(size_t)(order[r] / n_db)].push_back(order[r]);
-        parallel_for((size_t)n_user_sets, 1, [&](size_t us) { bh_rows(p_value_log, by_set[us], q_value); });
+        gtars::parallel_for((size_t)n_user_sets, threads, 1, [&](size_t us) { bh_rows(p_value_log, by_set[us], q_value); });
         return GTARS_OK;
     });
 }

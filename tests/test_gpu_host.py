@@ -962,7 +962,9 @@ def test_fused_fragment_pipeline_gives_the_same_result_under_every_switch(tk, go
     of the pinned pool, in ordinary memory (GTARS_NO_PINNED), in pinned blocks that are never cached (GTARS_PINNED_POOL_MB=0), or in a
     mix of both (GTARS_PINNED_MAX_MB=1: the pool hands out one block and refuses the rest),
     the host parser (GTARS_FRAG_HOST_PARSE).  Same per-cluster result -- barcodes in first-seen order, offsets, ids -- every time,
-    and equal to the oracle's restatement of the two-step pipeline (split.rs:84-131 + fragments.rs:12-56)."""
+    and equal to the oracle's restatement of the two-step pipeline (split.rs:84-131 + fragments.rs:12-56).  Then the cluster
+    count's edges on three small files -- one cluster, and 70 of which 43 stay empty -- under the default, three host threads and
+    the host parser."""
     import gzip
 
     from gtars_amd import _lib
@@ -996,14 +998,44 @@ def test_fused_fragment_pipeline_gives_the_same_result_under_every_switch(tk, go
     switches = [{}, {"GTARS_HOST_THREADS": "1"}, {"GTARS_HOST_THREADS": "2"}, {"GTARS_HOST_THREADS": "5"}, {"GTARS_ZLIB_INFLATE": "1"},
                 {"GTARS_FRAG_HOST_CRC": "1"}, {"GTARS_NO_PINNED": "1"}, {"GTARS_PINNED_POOL_MB": "0"}, {"GTARS_PINNED_MAX_MB": "1"}, {"GTARS_FRAG_HOST_PARSE": "1"},
                 {"GTARS_NO_PINNED": "1", "GTARS_ZLIB_INFLATE": "1", "GTARS_HOST_THREADS": "3"}]
+    # The cluster count's edges (the regroup runs one cluster per index on the host threads): three small files of nine barcodes
+    # each, routed into ONE cluster, and into 70 -- more than the 64 threads the regroup is capped at and more than three threads.
+    # The 27 (file, barcode) pairs fill 27 of the 70; the other 43 labels are carried only by barcodes that occur in no file: each
+    # is an entry without barcodes, offsets [0], no ids (the oracle lists every label of the map, as the product does).
+    fd2 = tmp_path / "frags_few"
+    fd2.mkdir()
+    for fi in range(3):
+        n = 200 + fi
+        text = "".join(f"{peaks[int(k)][0]}\t{int(peaks[int(k)][1]) + int(d)}\t{int(peaks[int(k)][2]) + 5}\tBC{int(b)}\t1\n"
+                       for k, d, b in zip(rng.integers(0, len(peaks), n), rng.integers(0, 50, n), rng.integers(0, 9, n)))
+        (fd2 / f"g{fi}.bed.gz").write_bytes(gzip.compress(text.encode()))
+    pairs = [(fi, b) for fi in range(3) for b in range(9)]
+    filled = {(fi * 9 + b) * 70 // 27 for fi, b in pairs}
+    edge_maps = {
+        "one": [f"g{fi}+BC{b}\tonly" for fi, b in pairs],
+        "seventy": [f"g{fi}+BC{b}\tk{(fi * 9 + b) * 70 // 27:02d}" for fi, b in pairs] +
+                   [f"g0+NOWHERE{c}\tk{c:02d}" for c in range(70) if c not in filled],
+    }
+    edge_inputs = []
+    for name, lines in edge_maps.items():
+        p = tmp_path / f"map_{name}.tsv"
+        p.write_text("\n".join(lines) + "\n")
+        want2 = oracle_fragment_pipeline(list_fragment_files(str(fd2)), oracle.OracleBarcodeMap(str(p)), otok)
+        edge_inputs.append((str(fd2), BarcodeToClusterMap.from_file(str(p)), want2))
+    assert len(edge_inputs[0][2]) == 1 and len(edge_inputs[1][2]) == 70
+    empty = [v for v in edge_inputs[1][2].values() if not v[0]]
+    assert len(empty) == 43 and all(list(v[1]) == [0] and len(v[2]) == 0 for v in empty)
+    assert sum(int(v[1][-1]) for v in edge_inputs[0][2].values()) == sum(int(v[1][-1]) for v in edge_inputs[1][2].values()) >= 603
+    runs = [(str(fd), m, want, sw) for sw in switches]
+    runs += [(d, m2, w2, sw) for d, m2, w2 in edge_inputs for sw in ({}, {"GTARS_HOST_THREADS": "3"}, {"GTARS_FRAG_HOST_PARSE": "1"})]
     try:
-        for sw in switches:
+        for d, m_, want_, sw in runs:
             for k, v in sw.items():
                 monkeypatch.setenv(k, v)
             _lib.lib.gtars_debug_reload_env()
             for _ in range(2):  # (twice: the second call runs on whatever the first one left in the pools)
-                got = fragsplit_tokenize(str(fd), m, tok, as_arrays=True)
-                assert same_cluster_results(got, want), sw
+                got = fragsplit_tokenize(d, m_, tok, as_arrays=True)
+                assert same_cluster_results(got, want_), (sw, len(want_))
             for k in sw:
                 monkeypatch.delenv(k)
     finally:

@@ -573,6 +573,31 @@ def test_inflate_decoder_under_the_sanitizers(tmp_path):
     assert "decoded bit-exact" in run.stdout
 
 
+def test_host_threads_under_the_thread_sanitizer(tmp_path):
+    """tests/soak/host_threads_check.cpp, built with ThreadSanitizer: csrc/host_threads.h alone -- parallel_for visits every index
+    exactly once (n around the thread count and 10,007, chunks of 1 and 8, 1 / 2 / 7 threads), a body's exception arrives on the
+    caller with every thread joined whether a worker's body or the caller's own threw it, of two exceptions one arrives, a throw
+    ends the hand-out of indices; cut_at_lines cuts at line starts; JoinedThreads stops and joins when an exception leaves its
+    scope."""
+    import shutil
+    import subprocess
+
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    exe = tmp_path / "host_threads_check"
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "soak", "host_threads_check.cpp")
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=thread", "-pthread", "-o", str(exe), src],
+                           capture_output=True, text=True)
+    if build.returncode != 0 and "sanitize" in build.stderr:
+        pytest.skip("the host compiler has no sanitizer runtime")
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, (run.stdout + run.stderr)[-2000:]
+    assert "all checks passed" in run.stdout
+    assert "ThreadSanitizer" not in run.stderr, run.stderr[-2000:]
+
+
 def test_bench_traffic_is_each_counters_mean_over_its_own_pass(tmp_path):
     """bench.py's roofline.traffic: FETCH_SIZE and WRITE_SIZE come from two SEPARATE rocprofv3 passes that may launch the kernel
     a different number of times; each counter's bytes per launch is its own sum over its own dispatch count (round 5 divided
