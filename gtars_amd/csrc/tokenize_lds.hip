@@ -2220,6 +2220,7 @@ gtars_status launch_tokenize_sweep(const AccelView &a, const u32 *qc, const u32 
     const i32 min_bp = has_min ? min_overlap : 0;
     ScanWs *ws = (ScanWs *)scan_ws;
     prof_note_fact("tok_build_sweep");
+    if (tpb == 1024) prof_note_fact("tok_sweep_tpb1024");  // (the A/B form ran, not its 256-thread stand-in: tests)
     ProfScope p("k_tok_sweep", st);
 #define GT_SWEEP_CASE(T, N, F, I, V) \
     if (tpb == T && rounds == N && filter == F && impl == I && reverse == V) \

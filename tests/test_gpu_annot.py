@@ -1,5 +1,7 @@
 """TSS / feature distances and gene models on the MI355X (csrc/annot.hip, K10; the stranded reduce on K8's device reduce)
-against the plain-Python restatement tests/annot_ref.py: seeded differentials with exact equality."""
+against the plain-Python restatement tests/annot_ref.py: seeded differentials with exact equality.  The literal cases, the
+interleaved batch and the index sizes around the staged sample are answered by both forms of the distance kernel on ONE index:
+k_tss_dist<true> (the sampled keys staged in LDS, the default) and k_tss_dist<false> (GTARS_TSS_GLOBAL_SEARCH=1)."""
 import gzip
 import os
 import sys
@@ -24,14 +26,30 @@ def _rs(regs):
     return RegionSet.from_vectors([r[0] for r in regs], [r[1] for r in regs], [r[2] for r in regs])
 
 
-def _check(index_regs, query_regs, tss=None):
+@pytest.fixture
+def search_forms(monkeypatch):
+    """-> a generator function: GTARS_TSS_GLOBAL_SEARCH unset, then "1" (the library takes a new snapshot of its switches at
+    every change, so a handle built before the change is answered by the other kernel)"""
+    def forms():
+        monkeypatch.delenv("GTARS_TSS_GLOBAL_SEARCH", raising=False)
+        yield "lds"
+        monkeypatch.setenv("GTARS_TSS_GLOBAL_SEARCH", "1")
+        yield "global"
+        monkeypatch.delenv("GTARS_TSS_GLOBAL_SEARCH")
+
+    return forms
+
+
+def _check(index_regs, query_regs, tss=None, forms=None):
+    """one index (its device image is built once), the queries under every search form of `forms` (default: as the process is)"""
     from gtars.models import TssIndex
 
     tss = tss or TssIndex.from_regionset(_rs(index_regs))
     q = _rs(query_regs)
     want_abs, want_signed = A.distances(A.build_index(index_regs), query_regs)
-    assert tss.calc_tss_distances(q) == want_abs
-    assert tss.feature_distances(q) == want_signed
+    for form in (forms() if forms else ["default"]):
+        assert tss.calc_tss_distances(q) == want_abs, form
+        assert tss.feature_distances(q) == want_signed, form
     return tss
 
 
@@ -47,24 +65,25 @@ def _tuples(c, s, e, order=None):
     return [(str(c[i]), int(s[i]), int(e[i])) for i in idx]
 
 
-def test_literal_cases():
+def test_literal_cases(search_forms):
     from gtars.models import Region, RegionSet, TssIndex
 
     feats = RegionSet.from_regions([Region("chr1", 100, 101)])
     tss = TssIndex.from_regionset(feats)
-    q = RegionSet.from_regions([Region("chr1", 200, 210)])
-    assert tss.calc_tss_distances(q) == [105]
-    assert tss.feature_distances(q) == [-105.0]
-    assert tss.feature_distances(RegionSet.from_regions([Region("chr2", 200, 210)])) == [None]
-    assert tss.calc_tss_distances(RegionSet.from_regions([Region("chr2", 200, 210)])) == [U32]
     # models.rs: dummy.narrowPeak against dummy_tss.bed
     t = TssIndex(os.path.join(GOLD, "dummy_tss.bed"))
     peaks = RegionSet(os.path.join(GOLD, "dummy.narrowPeak"))
-    d = t.calc_tss_distances(peaks)
-    sg = t.feature_distances(peaks)
-    assert len(d) == 9 and min(d) == 2 and [abs(int(v)) for v in sg] == d
+    for form in search_forms():
+        q = RegionSet.from_regions([Region("chr1", 200, 210)])
+        assert tss.calc_tss_distances(q) == [105], form
+        assert tss.feature_distances(q) == [-105.0], form
+        assert tss.feature_distances(RegionSet.from_regions([Region("chr2", 200, 210)])) == [None], form
+        assert tss.calc_tss_distances(RegionSet.from_regions([Region("chr2", 200, 210)])) == [U32], form
+        d = t.calc_tss_distances(peaks)
+        sg = t.feature_distances(peaks)
+        assert len(d) == 9 and min(d) == 2 and [abs(int(v)) for v in sg] == d, form
     _check([(r.chr, r.start, r.end) for r in RegionSet(os.path.join(GOLD, "dummy_tss.bed"))],
-           [(r.chr, r.start, r.end) for r in peaks], t)
+           [(r.chr, r.start, r.end) for r in peaks], t, search_forms)
     import gtars_amd
 
     assert gtars_amd._lib.lib.gtars_tss_index_device(t._h) == 0
@@ -84,13 +103,13 @@ def test_million_queries_sorted_and_shuffled(n_index):
     _check(index, _tuples(qc, qs, qe), tss)
 
 
-def test_interleaved_missing_chromosomes_and_edges():
+def test_interleaved_missing_chromosomes_and_edges(search_forms):
     rng = np.random.default_rng(11)
     index = [("a", 10, 11), ("a", 20, 21), ("a", 20, 21), ("a", 30, 31), ("b", U32 - 3, U32), ("b", 7, 3),
              ("c", 0, 0), ("c", U32, U32), ("d", 5, 9)]
     q = [("b", 0, 1), ("zz", 1, 2), ("a", 15, 16), ("a", 20, 20), ("c", 5, 1), ("a", 24, 26), ("b", U32 - 1, U32),
          ("zz", 9, 9), ("a", 0, 1), ("a", 40, 41), ("c", U32, U32), ("c", 0, 0), ("d", 7, 7), ("d", 6, 8), ("yy", 3, 4)]
-    _check(index, q)
+    _check(index, q, forms=search_forms)
     # random interleaving over few positions: many exact hits, duplicate midpoints, equal-distance ties
     names = ["a", "b", "c", "d", "e", "zz"]
     idx = [(str(rng.choice(names[:4])), int(s), int(s) + int(w)) for s, w in
@@ -102,7 +121,7 @@ def test_interleaved_missing_chromosomes_and_edges():
         if rng.random() < 0.02:
             s, e = U32 - int(rng.integers(0, 5)), int(rng.choice([U32, 3]))
         qq.append((str(rng.choice(names)), s, e))
-    _check(idx, qq)
+    _check(idx, qq, forms=search_forms)
 
 
 def test_empty_query_and_empty_index():
@@ -181,10 +200,10 @@ def test_gene_model_synthetic_200k_rows(tmp_path):
 
 
 @pytest.mark.parametrize("n_index,boundary", E.edge_cases())
-def test_index_sizes_around_the_staged_sample(n_index, boundary):
+def test_index_sizes_around_the_staged_sample(n_index, boundary, search_forms):
     """index sizes on the edges of a lane, a wave, a workgroup and the 2048 sampled keys a workgroup stages, on one
     chromosome and on two whose second begins at index 2048 resp. 2047 of the (chromosome, midpoint) order; 50 000
-    queries with exact hits on the first and the last midpoint of every chromosome"""
+    queries with exact hits on the first and the last midpoint of every chromosome; both search forms on the one index"""
     rng = np.random.default_rng(6000 + n_index)
     ic, is_, ie = _random_regs(rng, n_index, ["chr10"], 3_000_000, (0, 3))
     index = _tuples(ic, is_, ie)
@@ -198,4 +217,4 @@ def test_index_sizes_around_the_staged_sample(n_index, boundary):
     for name in sorted({c for c, _, _ in index}):
         mids = sorted(A.midpoint(s, e) for c, s, e in index if c == name)
         q += [(name, mids[0], mids[0] + 1), (name, mids[-1], mids[-1] + 1), (name, mids[0], mids[0]), (name, mids[-1], mids[-1])]
-    _check(index, q)
+    _check(index, q, forms=search_forms)

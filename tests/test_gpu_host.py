@@ -961,7 +961,10 @@ def test_fused_fragment_pipeline_gives_the_same_result_under_every_switch(tk, go
     (GTARS_ZLIB_INFLATE), the gzip members' CRC-32 on the device or on the host (GTARS_FRAG_HOST_CRC), text and results in blocks
     of the pinned pool, in ordinary memory (GTARS_NO_PINNED), in pinned blocks that are never cached (GTARS_PINNED_POOL_MB=0), or in a
     mix of both (GTARS_PINNED_MAX_MB=1: the pool hands out one block and refuses the rest),
-    the host parser (GTARS_FRAG_HOST_PARSE).  Same per-cluster result -- barcodes in first-seen order, offsets, ids -- every time,
+    the host parser (GTARS_FRAG_HOST_PARSE), the device threads' waves on the null stream instead of a stream per thread
+    (GTARS_FRAG_NULL_STREAM: consulted while a device thread's stream slot is empty, and the device threads are started anew by
+    every call, so the switch takes effect in a process that has run the pipeline before), the wait for a wave as
+    hipStreamSynchronize instead of a blocking event (GTARS_FRAG_SPIN_WAIT).  Same per-cluster result -- barcodes in first-seen order, offsets, ids -- every time,
     and equal to the oracle's restatement of the two-step pipeline (split.rs:84-131 + fragments.rs:12-56).  Then the cluster
     count's edges on three small files -- one cluster, and 70 of which 43 stay empty -- under the default, three host threads and
     the host parser."""
@@ -997,7 +1000,8 @@ def test_fused_fragment_pipeline_gives_the_same_result_under_every_switch(tk, go
     want = oracle_fragment_pipeline(list_fragment_files(str(fd)), om, otok)
     switches = [{}, {"GTARS_HOST_THREADS": "1"}, {"GTARS_HOST_THREADS": "2"}, {"GTARS_HOST_THREADS": "5"}, {"GTARS_ZLIB_INFLATE": "1"},
                 {"GTARS_FRAG_HOST_CRC": "1"}, {"GTARS_NO_PINNED": "1"}, {"GTARS_PINNED_POOL_MB": "0"}, {"GTARS_PINNED_MAX_MB": "1"}, {"GTARS_FRAG_HOST_PARSE": "1"},
-                {"GTARS_NO_PINNED": "1", "GTARS_ZLIB_INFLATE": "1", "GTARS_HOST_THREADS": "3"}]
+                {"GTARS_NO_PINNED": "1", "GTARS_ZLIB_INFLATE": "1", "GTARS_HOST_THREADS": "3"},
+                {"GTARS_FRAG_NULL_STREAM": "1"}, {"GTARS_FRAG_SPIN_WAIT": "1"}]
     # The cluster count's edges (the regroup runs one cluster per index on the host threads): three small files of nine barcodes
     # each, routed into ONE cluster, and into 70 -- more than the 64 threads the regroup is capped at and more than three threads.
     # The 27 (file, barcode) pairs fill 27 of the 70; the other 43 labels are carried only by barcodes that occur in no file: each
@@ -1040,6 +1044,39 @@ def test_fused_fragment_pipeline_gives_the_same_result_under_every_switch(tk, go
                 monkeypatch.delenv(k)
     finally:
         _lib.lib.gtars_debug_reload_env()
+
+
+_KEEP_SCRIPT = r"""
+import sys, numpy as np
+sys.path.insert(0, %r)
+import gtars_amd, oracle
+from gtars_amd import synth
+u = synth.make_universe(30_000)
+g = gtars_amd.OverlapIndex(u["chrom"], u["start"], u["end"], n_chrom=synth.N_CHROM)
+o = oracle.Index(u["chrom"], u["start"], u["end"], None, n_chrom=synth.N_CHROM)
+ok = []
+for k, nq in enumerate((200_000, 1_000, 200_000)):
+    q = synth.make_queries(u, nq, seed=40 + k)
+    off_g, ids_g = g.tokenize(q["chrom"], q["start"], q["end"])
+    off_o, ids_o = o.tokenize(q["chrom"], q["start"], q["end"])
+    ok.append(bool(np.array_equal(off_g, off_o) and np.array_equal(ids_g, ids_o) and len(ids_o) > nq // 2))
+print("KEEP_PARITY", ok)
+"""
+
+
+def test_host_pipeline_staging_trimmed_and_grown_again():
+    """GTARS_PIPE_KEEP_MB=1 (read once per process, hence a child process with a time limit of its own): the host pipeline's
+    device staging (tokenize_pipeline: three query columns, offsets, ids -- 5.6 MB for 200 000 queries, 32 KB for 1 000) is given
+    back after a batch that needed more than 1 MB.  Batches of 200 000, 1 000 and 200 000 queries on one thread: the first is
+    trimmed behind the call, the second allocates afresh and stays, the third grows that allocation again.  Each result is the
+    oracle's."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GTARS_PIPE_KEEP_MB="1")
+    r = subprocess.run([sys.executable, "-c", _KEEP_SCRIPT % root], env=env, capture_output=True, text=True, timeout=300)
+    assert "KEEP_PARITY [True, True, True]" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
 
 
 def test_device_fragment_parser_follows_the_reference_line_rules(tk, golden_dir, tmp_path, monkeypatch):

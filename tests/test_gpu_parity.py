@@ -1637,6 +1637,51 @@ def test_igd_two_level_partition_with_a_sparse_tail(ga, monkeypatch):
         monkeypatch.delenv("GTARS_IGD_NO_HEAVY_PARTS")
 
 
+def test_igd_one_level_split_at_the_two_level_sizes(ga, monkeypatch):
+    """GTARS_MS_ONE_LEVEL: the one-level multisplit (k_ms_scan, k_ms_scatter) on a batch the default hands to the two-level one
+    (k_split_pass: more than 1024 bins and at least 2^20 pairs).  A database of 2.3M records routes over ~1100 owner tiles (more
+    than 1024, far below MS_MAX_BINS = 36 864 bins).  Shuffled batches of 2^20 - 1 queries (one level under both settings) and of
+    2^20 (two levels by default, one with the switch): the count vectors are equal between the settings in full, pairwise and
+    binary, and equal the oracle's, which answers ALL 2^20 queries (every chromosome, ~1 s per vector on the CPU: the sample is
+    the whole batch).  Which split ran is read from the kernel names the profiler records."""
+    rng = np.random.default_rng(2320)
+    n_db, n_chrom, F, span = 2_300_000, 3, 40, 240_000_000
+    c = rng.integers(0, n_chrom, n_db)
+    s = rng.integers(0, span, n_db)
+    e = s + rng.integers(1, 3_000, n_db)
+    f = rng.integers(0, F, n_db)
+    g, o = _igd_pair(ga, c, s, e, f, np.arange(n_db), n_chrom=n_chrom, n_files=F)
+    full = 1 << 20
+    qc, qs, qe = _random_query_set(rng, full, n_chrom, span + 5_000, 800)
+    assert set(np.unique(qc)) >= set(range(n_chrom))
+    _lib = ga._lib
+
+    def run(count, n, one_level):
+        if one_level:
+            monkeypatch.setenv("GTARS_MS_ONE_LEVEL", "1")
+        _lib.lib.gtars_prof_reset()
+        _lib.lib.gtars_prof_enable(1)
+        got = count(qc[:n], qs[:n], qe[:n], 1)
+        names = set(_lib.prof_read())
+        _lib.lib.gtars_prof_enable(0)
+        if one_level:
+            monkeypatch.delenv("GTARS_MS_ONE_LEVEL")
+        return got, names
+
+    for count, ref in ((g.count_set_overlaps, o.count_set_overlaps), (g.count_region_hits, o.count_region_hits)):
+        for n in (full - 1, full):
+            want = ref(qc[:n], qs[:n], qe[:n], 1, n_files=F)
+            default, names_d = run(count, n, False)
+            forced, names_f = run(count, n, True)
+            assert "k_ms_scatter" in names_f and "k_split_pass" not in names_f, (n, sorted(names_f))
+            if n < full:
+                assert "k_ms_scatter" in names_d and "k_split_pass" not in names_d, (n, sorted(names_d))
+            else:
+                assert "k_split_pass" in names_d and "k_ms_scatter" not in names_d, (n, sorted(names_d))
+            assert np.array_equal(default, forced), (n, np.argwhere(default != forced)[:5])
+            assert np.array_equal(forced, want), (n, np.argwhere(forced != want)[:5])
+
+
 def _random_query_set(rng, n, n_chrom, span, wmax, spoiled=0.02):
     """n queries, a few of them unknown chromosomes, inverted, or negative as i32 (rejected or clamped by igd.rs:514-517)"""
     qc = rng.integers(0, n_chrom, n).astype(np.uint32)
@@ -1654,13 +1699,14 @@ def _random_query_set(rng, n, n_chrom, span, wmax, spoiled=0.02):
 
 @pytest.mark.parametrize("n_db,sizes", [(150_000, (400_000, 60_000)), (2_300_000, (1_100_000, 90_000, 0, 7_000)),
                                         (150_000, (300_000, 20_000, 20_000, 20_000, 250_000, 1_000)), (150_000, (3_000, 500))])
-def test_igd_query_sets_share_one_pass(ga, n_db, sizes):
+def test_igd_query_sets_share_one_pass(ga, monkeypatch, n_db, sizes):
     """gtars_igd_count_sets: the count step of run_lola (enrichment.rs:198-221 -- count_region_hits of the universe and of every
     user set over the same Igd).  Up to four sets share one sweep of the database (the partition tags the pairs, one row of
     counters per set); every row must equal what the oracle returns for that set ALONE, pairwise and binary, min_overlap 1
     (pme_file form) and 3 (credited-file-list form); how many passes were shared is read from the profiling facts, not from
     a clock.  Cases: one- and two-level partitions, an empty set in the middle, more than four sets (two groups), sets
-    below the sweep's crossover (counted set by set)."""
+    below the sweep's crossover (counted set by set).  Every case also runs under GTARS_IGD_NO_SHARED_PASS=1 -- one sweep per
+    set: the same rows, and no shared pass among the facts."""
     rng = np.random.default_rng(n_db + len(sizes))
     n_chrom, F, span = 3, 40, 30_000_000 if n_db < 1_000_000 else 240_000_000  # ~15-30 overlapping records per query
     c = rng.integers(0, n_chrom, n_db)
@@ -1674,19 +1720,27 @@ def test_igd_query_sets_share_one_pass(ga, n_db, sizes):
         ref = o.count_region_hits if binary else o.count_set_overlaps
         want = np.stack([ref(qc, qs, qe, mo, n_files=F) for qc, qs, qe in sets])
         g.count_sets(sets[:1], mo, binary)  # builds pme_file outside the profiled call
-        _lib.lib.gtars_prof_reset()
-        _lib.lib.gtars_prof_enable(1)
-        got = g.count_sets(sets, mo, binary)
-        prof = _lib.prof_read()
-        _lib.lib.gtars_prof_enable(0)
-        assert np.array_equal(got, want), (binary, mo, np.argwhere(got != want)[:5])
-        shared = prof.get("igd_sets_shared_pass", {"launches": 0})["launches"]
-        if sizes == (3_000, 500):
-            assert shared == 0  # below the crossover: the per-query kernel, set by set
-        elif len(sizes) == 6:
-            assert shared == 2  # sets 0-3 and sets 4-5
-        else:
-            assert shared == 1
+        for no_shared in (False, True):
+            if no_shared:
+                monkeypatch.setenv("GTARS_IGD_NO_SHARED_PASS", "1")
+            _lib.lib.gtars_prof_reset()
+            _lib.lib.gtars_prof_enable(1)
+            got = g.count_sets(sets, mo, binary)
+            prof = _lib.prof_read()
+            _lib.lib.gtars_prof_enable(0)
+            if no_shared:
+                monkeypatch.delenv("GTARS_IGD_NO_SHARED_PASS")
+            assert np.array_equal(got, want), (binary, mo, no_shared, np.argwhere(got != want)[:5])
+            if no_shared:
+                assert "igd_sets_shared_pass" not in prof, sorted(prof)
+                continue
+            shared = prof.get("igd_sets_shared_pass", {"launches": 0})["launches"]
+            if sizes == (3_000, 500):
+                assert shared == 0  # below the crossover: the per-query kernel, set by set
+            elif len(sizes) == 6:
+                assert shared == 2  # sets 0-3 and sets 4-5
+            else:
+                assert shared == 1
     # the same rows again set by set (what the shared pass replaces)
     os.environ["GTARS_IGD_SWEEP_MIN"] = "1"
     ga.reload_env()
@@ -2279,16 +2333,9 @@ def _tok_device(ga, g, qc, qs, qe, hint, cap_factor=6):
     return off.cpu().numpy().view(np.uint64), ids[:h].cpu().numpy().view(np.uint32)
 
 
-@pytest.mark.parametrize("kind", BOTH)
-@pytest.mark.parametrize("explicit_ids", [False, True])
-def test_sweep_tokenizer_on_batches_in_order(ga, monkeypatch, kind, explicit_ids):
-    """Round 6: GTARS_TOK_SORTED -- the sweep form of the tokenizer (k_tok_sweep) for batches in (chromosome, start) order, what a
-    file-loaded RegionSet is (region_set.rs:182, 502-505).  Same offsets and ids as Bits::find / AIList::find (bits.rs:141-156,
-    433-446; ailist.rs:238-263) and as the default kernel, on: disjoint and overlapping universes with position-derived and
-    explicit ids, several tiles with chromosome boundaries inside tiles (two and more runs per tile), unknown chromosomes
-    inside the batch, zero-length and wide queries (hits beyond the 32-interval mask: the global walk), a universe far beyond
-    k_tok_lds' LDS key budget, min-overlap filters, an id buffer that is too short (offsets complete, GTARS_ERR_CAPACITY)."""
-    rng = np.random.default_rng(17 + kind)
+def sweep_cases(ga, rng, kind, explicit_ids):
+    """the universes and in-order batches of the sweep tokenizer's tests, one after the other (the caller may draw from rng
+    between two of them) -> (n, g, oracle index, (qc, qs, qe), id-buffer factor)"""
     for n, n_chrom, span, wmax, qwmax, nq in ((60_000, 5, 4_000_000, 400, 600, 70_000), (3_000, 40, 100_000, 90, 200, 30_000),
                                               (400_000, 3, 60_000_000, 300, 500, 50_000), (20_000, 2, 1_000_000, 3000, 40_000, 20_000)):
         c = np.sort(rng.integers(0, n_chrom, n)).astype(np.uint32)
@@ -2302,31 +2349,45 @@ def test_sweep_tokenizer_on_batches_in_order(ga, monkeypatch, kind, explicit_ids
             e = np.where(same, np.minimum(e, np.maximum(nxt, s + 1)), e).astype(np.uint32)
         val = rng.permutation(n).astype(np.uint32) if explicit_ids else None
         g, o_ = _pair(ga, c, s, e, val, n_chrom=n_chrom, kind=kind)
-        qc, qs, qe = _sorted_batch(rng, n_chrom, nq, span + 1000, qwmax, unknown=0.01)
+        yield n, g, o_, _sorted_batch(rng, n_chrom, nq, span + 1000, qwmax, unknown=0.01), 2 + qwmax // 40
+
+
+@pytest.mark.parametrize("kind", BOTH)
+@pytest.mark.parametrize("explicit_ids", [False, True])
+def test_sweep_tokenizer_on_batches_in_order(ga, monkeypatch, kind, explicit_ids):
+    """Round 6: GTARS_TOK_SORTED -- the sweep form of the tokenizer (k_tok_sweep) for batches in (chromosome, start) order, what a
+    file-loaded RegionSet is (region_set.rs:182, 502-505).  Same offsets and ids as Bits::find / AIList::find (bits.rs:141-156,
+    433-446; ailist.rs:238-263) and as the default kernel, on: disjoint and overlapping universes with position-derived and
+    explicit ids, several tiles with chromosome boundaries inside tiles (two and more runs per tile), unknown chromosomes
+    inside the batch, zero-length and wide queries (hits beyond the 32-interval mask: the global walk), a universe far beyond
+    k_tok_lds' LDS key budget, min-overlap filters, an id buffer that is too short (offsets complete, GTARS_ERR_CAPACITY)."""
+    rng = np.random.default_rng(17 + kind)
+    for n, g, o_, (qc, qs, qe), cap_factor in sweep_cases(ga, rng, kind, explicit_ids):
+        nq = len(qc)
         want_off, want_ids = o_.tokenize(qc, qs, qe)
         _lib = ga._lib
         _lib.lib.gtars_prof_reset()
         _lib.lib.gtars_prof_enable(1)
-        off, ids = _tok_device(ga, g, qc, qs, qe, g.TOK_SORTED, cap_factor=2 + qwmax // 40)
+        off, ids = _tok_device(ga, g, qc, qs, qe, g.TOK_SORTED, cap_factor=cap_factor)
         prof = _lib.prof_read()
         _lib.lib.gtars_prof_enable(0)
         if kind == KIND_BITS or "tok_build_sweep" in prof:  # (a nested AIList universe has no blocked structure: generic kernel)
             assert "tok_build_sweep" in prof, sorted(prof)
         assert np.array_equal(off, want_off), (n, np.argwhere(off != want_off)[:3])
         assert np.array_equal(ids, want_ids), (n, np.argwhere(ids != want_ids)[:3])
-        off2, ids2 = _tok_device(ga, g, qc, qs, qe, g.TOK_AUTO, cap_factor=2 + qwmax // 40)
+        off2, ids2 = _tok_device(ga, g, qc, qs, qe, g.TOK_AUTO, cap_factor=cap_factor)
         assert np.array_equal(off2, want_off) and np.array_equal(ids2, want_ids)
         # the same batch SHUFFLED under the hint: still right (many runs per tile -> the global path)
         p = rng.permutation(nq)[: 6000]
         w_off, w_ids = o_.tokenize(qc[p], qs[p], qe[p])
-        off3, ids3 = _tok_device(ga, g, qc[p], qs[p], qe[p], g.TOK_SORTED, cap_factor=2 + qwmax // 40)
+        off3, ids3 = _tok_device(ga, g, qc[p], qs[p], qe[p], g.TOK_SORTED, cap_factor=cap_factor)
         assert np.array_equal(off3, w_off) and np.array_equal(ids3, w_ids)
     # forced small budgets: 8 staged blocks per wave (every run beyond -> global memory), one run per wave and round (the second
     # run -> global memory), none; two rounds per tile on a batch this small
     for env, val_ in (("GTARS_TOK_SWEEP_BLOCKS", "8"), ("GTARS_TOK_SWEEP_RUNS", "1"), ("GTARS_TOK_SWEEP_RUNS", "0"),
                       ("GTARS_TOK_SWEEP_ROUNDS", "2")):
         monkeypatch.setenv(env, val_)
-        off5, ids5 = _tok_device(ga, g, qc, qs, qe, g.TOK_SORTED, cap_factor=2 + qwmax // 40)
+        off5, ids5 = _tok_device(ga, g, qc, qs, qe, g.TOK_SORTED, cap_factor=cap_factor)
         monkeypatch.delenv(env)
         assert np.array_equal(off5, want_off) and np.array_equal(ids5, want_ids), env
     # min-overlap filter through count_overlaps is another kernel; the tokenizer's filter form through find_overlaps' values

@@ -1,6 +1,7 @@
 """GC content and dinucleotide counts on the device (csrc/seqstats.hip, K12) against the plain-Python restatement
 (tests/seqstats_ref.py).  Exact equality everywhere: the device counts integers and the divisions are the library's host f64
-arithmetic in the reference's order.  The assembly is loaded both as FASTA and as .fab; every check runs on both."""
+arithmetic in the reference's order.  The assembly is loaded both as FASTA and as .fab; every check runs on both, and every
+device check runs under both lane groupings of k_seq_count (GTARS_SEQ_LANES = 16 and 64: a 256-byte and a 1-KiB step)."""
 import random
 
 import numpy as np
@@ -52,14 +53,28 @@ def genomes(tmp_path_factory):
     return seqs, (fasta, fab)
 
 
+LANES = ("16", "64")  # GTARS_SEQ_LANES: k_seq_count<16, *> and k_seq_count<64, *>
+
+
+@pytest.fixture
+def lane_settings(monkeypatch):
+    """-> a generator function: sets GTARS_SEQ_LANES to each grouping in turn (the library takes a new snapshot of its switches)"""
+    def settings():
+        for lanes in LANES:
+            monkeypatch.setenv("GTARS_SEQ_LANES", lanes)
+            yield lanes
+
+    return settings
+
+
 def _rs(rows):
     from gtars_amd.models import RegionSet
 
     return RegionSet.from_vectors([r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows])
 
 
-def _check(genomes, rows, ignore=False):
-    """both library calls on both assemblies against the restatement; -> the labels and integer rows"""
+def _check(genomes, rows, settings, ignore=False):
+    """both library calls on both assemblies under every lane grouping against the restatement; -> the labels and integer rows"""
     from gtars_amd.seqstats import calc_dinucl_freq, calc_gc_content
 
     seqs, loaded = genomes
@@ -67,35 +82,36 @@ def _check(genomes, rows, ignore=False):
     want_gc = R.calc_gc_content(rows, seqs, ignore)
     labels, counts = R.calc_dinucl_counts(rows, seqs, ignore)
     want_raw = [[float(c) for c in row] for row in counts]
-    for g in loaded:
-        assert calc_gc_content(rs, g, ignore_unk_chroms=ignore) == want_gc
-        got = calc_dinucl_freq(rs, g, raw_counts=True, ignore_unk_chroms=ignore)
-        assert got["region_labels"] == labels
-        assert got["frequencies"] == want_raw
-        assert g.device >= 0
+    for lanes in settings():
+        for g in loaded:
+            assert calc_gc_content(rs, g, ignore_unk_chroms=ignore) == want_gc, lanes
+            got = calc_dinucl_freq(rs, g, raw_counts=True, ignore_unk_chroms=ignore)
+            assert got["region_labels"] == labels, lanes
+            assert got["frequencies"] == want_raw, lanes
+            assert g.device >= 0
     return labels, counts
 
 
-def test_short_regions_at_every_alignment(genomes):
+def test_short_regions_at_every_alignment(genomes, lane_settings):
     rows = [(MID, s, s + w) for s in range(4080, 4112) for w in (0, 1, 2, 3, 15, 16, 17, 31, 32, 33)]
-    _check(genomes, rows)
+    _check(genomes, rows, lane_settings)
 
 
-def test_piece_edges(genomes):
+def test_piece_edges(genomes, lane_settings):
     from gtars_amd.seqstats import SEQ_PIECE as PIECE
 
     assert PIECE >= 16 and 3 * PIECE + 5 + 16 < 100_003
     rows = [(MID, s, s + w) for s in (0, 1, 15, 16) for w in (PIECE - 1, PIECE, PIECE + 1, 2 * PIECE, 3 * PIECE + 5)]
     rows += [(LONG, 1_000_000 - 7, 1_000_000 - 7 + 3 * PIECE + 5)]
-    _check(genomes, rows)
+    _check(genomes, rows, lane_settings)
 
 
-def test_chromosome_ends(genomes):
+def test_chromosome_ends(genomes, lane_settings):
     rows = []
     for name, n in LENGTHS:
         rows += [(name, n - k, n) for k in range(0, 34) if k <= n]
         rows += [(name, 0, n), (name, 0, 0)]
-    labels, counts = _check(genomes, rows)
+    labels, counts = _check(genomes, rows, lane_settings)
     whole = dict(zip(labels, counts))
     assert sum(whole["c1_0_1"]) == 0 and sum(whole["c2_0_2"]) <= 1
 
@@ -113,19 +129,21 @@ def mixed_rows():
     return rows
 
 
-def test_long_and_mixed(genomes, mixed_rows):
+def test_long_and_mixed(genomes, mixed_rows, lane_settings):
     from gtars_amd.seqstats import calc_dinucl_freq, calc_gc_content
 
-    labels, counts = _check(genomes, mixed_rows)
+    labels, counts = _check(genomes, mixed_rows, lane_settings)
     shuffled = dict(zip(labels, ([float(c) for c in row] for row in counts)))
     assert sum(shuffled[f"{LONG}_50000_1950000"]) > 1_000_000  # the long region went through the adding path
     # the same set in sorted order: the same row for every region
     ordered = _rs(sorted(mixed_rows))
-    for g in genomes[1]:
-        got = calc_dinucl_freq(ordered, g, raw_counts=True)
-        assert len(got["region_labels"]) == len(mixed_rows)
-        assert all(shuffled[label] == row for label, row in zip(got["region_labels"], got["frequencies"]))
-        assert sorted(calc_gc_content(ordered, g)) == sorted(R.calc_gc_content(mixed_rows, genomes[0]))
+    want_gc = sorted(R.calc_gc_content(mixed_rows, genomes[0]))
+    for lanes in lane_settings():
+        for g in genomes[1]:
+            got = calc_dinucl_freq(ordered, g, raw_counts=True)
+            assert len(got["region_labels"]) == len(mixed_rows)
+            assert all(shuffled[label] == row for label, row in zip(got["region_labels"], got["frequencies"])), lanes
+            assert sorted(calc_gc_content(ordered, g)) == want_gc, lanes
 
 
 def test_order_and_skipping(genomes):
@@ -167,28 +185,57 @@ def _device_counts(g, mode, rows):
     return out.cpu().numpy().view(np.uint32).reshape(-1, width)
 
 
-def test_device_entry(genomes, mixed_rows):
+def test_device_entry(genomes, mixed_rows, lane_settings):
     from gtars_amd.seqstats import calc_dinucl_freq
 
     seqs, loaded = genomes
+    want_gc = [R.gc_count(seqs[c][s:e]) for c, s, e in mixed_rows]
+    for lanes in lane_settings():
+        for g in loaded:
+            # n == 0: success, nothing touched
+            assert (_device_counts(g, "gc", []).view(np.int32) == -1).all()
+            assert (_device_counts(g, "dinucl", []).view(np.int32) == -1).all()
+            one = [(MID, 4090, 4131)]
+            seq = seqs[MID][4090:4131]
+            assert _device_counts(g, "gc", one).tolist() == [[R.gc_count(seq)]], lanes
+            assert _device_counts(g, "dinucl", one).tolist() == [R.dinucl_counts(seq)], lanes
+        # input order out; equal to the library call's counts row by row
+        g = loaded[0]
+        gc = _device_counts(g, "gc", mixed_rows)[:, 0].tolist()
+        di = _device_counts(g, "dinucl", mixed_rows).tolist()
+        assert gc == want_gc, lanes
+        lib_rows = calc_dinucl_freq(_rs(mixed_rows), g, raw_counts=True)
+        by_label = dict(zip(lib_rows["region_labels"], lib_rows["frequencies"]))
+        assert [[float(c) for c in row] for row in di] == [by_label[f"{c}_{s}_{e}"] for c, s, e in mixed_rows], lanes
+        with pytest.raises(ValueError):  # a row outside its chromosome is refused, never read
+            _device_counts(g, "gc", [(MID, 0, 100_004)])
+
+
+# one step of a lane group is LANES x 16 bytes: 256 bytes for 16 lanes, 1024 for 64
+STEP_WIDTHS = {"16": (255, 256, 257, 271, 272, 273), "64": (1007, 1008, 1009, 1023, 1024, 1025, 1039, 1040, 1041)}
+
+
+def step_edge_rows():
+    """rows on c100k with start in 4080 .. 4096 and widths around one step of each grouping and around the step plus one vector"""
+    return [(MID, s, s + w) for s in range(4080, 4097) for w in STEP_WIDTHS["16"] + STEP_WIDTHS["64"]]
+
+
+@pytest.mark.parametrize("lanes", LANES)
+def test_lane_group_step_edges(genomes, monkeypatch, lanes):
+    """Widths at which the number of aligned 16-byte vectors of a piece, nv, passes LANES and LANES + 1 for both groupings, at
+    every alignment of the start: the last lane of the group (gl == LANES - 1) reads the second byte of its last window with a
+    load of its own; lane 0 of the next step names a window whose first byte the previous step saw; the last vector of a piece
+    is the first vector of a step.  Both modes, through the library calls (both assemblies) and through the device entry."""
+    seqs, loaded = genomes
+    rows = step_edge_rows()
+    first = rows[0][1] & ~15
+    nvs = {((e - first) + 15) // 16 for _, s, e in rows if s == rows[0][1]}
+    assert {16, 17, 18, 64, 65, 66} <= nvs  # LANES, LANES + 1 and one more, for both groupings
+    monkeypatch.setenv("GTARS_SEQ_LANES", lanes)
+    _, counts = _check(genomes, rows, lambda: [lanes])
     for g in loaded:
-        # n == 0: success, nothing touched
-        assert (_device_counts(g, "gc", []).view(np.int32) == -1).all()
-        assert (_device_counts(g, "dinucl", []).view(np.int32) == -1).all()
-        one = [(MID, 4090, 4131)]
-        seq = seqs[MID][4090:4131]
-        assert _device_counts(g, "gc", one).tolist() == [[R.gc_count(seq)]]
-        assert _device_counts(g, "dinucl", one).tolist() == [R.dinucl_counts(seq)]
-    # input order out; equal to the library call's counts row by row
-    g = loaded[0]
-    gc = _device_counts(g, "gc", mixed_rows)[:, 0].tolist()
-    di = _device_counts(g, "dinucl", mixed_rows).tolist()
-    assert gc == [R.gc_count(seqs[c][s:e]) for c, s, e in mixed_rows]
-    lib_rows = calc_dinucl_freq(_rs(mixed_rows), g, raw_counts=True)
-    by_label = dict(zip(lib_rows["region_labels"], lib_rows["frequencies"]))
-    assert [[float(c) for c in row] for row in di] == [by_label[f"{c}_{s}_{e}"] for c, s, e in mixed_rows]
-    with pytest.raises(ValueError):  # a row outside its chromosome is refused, never read
-        _device_counts(g, "gc", [(MID, 0, 100_004)])
+        assert _device_counts(g, "gc", rows)[:, 0].tolist() == [R.gc_count(seqs[c][s:e]) for c, s, e in rows]
+        assert _device_counts(g, "dinucl", rows).tolist() == counts
 
 
 def test_python_surface(genomes):

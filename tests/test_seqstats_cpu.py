@@ -236,3 +236,30 @@ def test_alias_package_has_the_new_names():
 
     assert (GenomeAssembly, BinaryGenomeAssembly, write_fab) == (S.GenomeAssembly, S.BinaryGenomeAssembly, S.write_fab)
     assert calc_gc_content is S.calc_gc_content and calc_dinucl_freq is S.calc_dinucl_freq
+
+
+def test_restatement_on_the_lane_step_rows():
+    """The rows of test_gpu_seqstats.test_lane_group_step_edges (255 rows of at most 1041 bytes around one step of either lane
+    grouping): the plain-Python restatement counts them in well under a second (0.02 s when written) and agrees with a count
+    of the same bytes by numpy table look-ups."""
+    import time
+
+    import numpy as np
+    from test_gpu_seqstats import _make_sequences, step_edge_rows
+
+    seqs, rows = _make_sequences(), step_edge_rows()
+    assert len(rows) == 255 and max(e - s for _, s, e in rows) == 1041
+    t0 = time.perf_counter()
+    gc = R.calc_gc_content(rows, seqs, False)
+    labels, counts = R.calc_dinucl_counts(rows, seqs, False)
+    assert time.perf_counter() - t0 < 1.0
+    code = np.full(256, -1, dtype=np.int64)
+    for k, letter in enumerate("ACGT"):
+        code[ord(letter)] = code[ord(letter.lower())] = k
+    order = [4 * "ACGT".index(d[0].upper()) + "ACGT".index(d[1].upper()) for d in R.DINUCL_ORDER]
+    by_label = dict(zip(labels, counts))
+    for (name, s, e), got_gc in zip(rows, gc):
+        b = code[np.frombuffer(seqs[name][s:e], dtype=np.uint8)]
+        assert got_gc == int(((b == 1) | (b == 2)).sum()) / (e - s)
+        pair = np.where((b[:-1] >= 0) & (b[1:] >= 0), 4 * b[:-1] + b[1:], -1)
+        assert by_label[f"{name}_{s}_{e}"] == [int((pair == o).sum()) for o in order]
