@@ -92,6 +92,7 @@ _SIG = {
     "gtars_pad_sets_device": (C.c_int, [vp, vp, u64, u64, u32, C.c_int, vp, vp, vp]),
     "gtars_histogram_u32_device": (C.c_int, [vp, u64, u32, vp, vp]),
     "gtars_histogram_rows_device": (C.c_int, [vp, vp, vp, u64, u32, u32, u32, vp, vp]),
+    "gtars_count_matrix_csr_device": (C.c_int, [vp, vp, vp, u64, u32, u32, vp, vp, vp, u64, pu64, vp]),
     "gtars_tokenize": (C.c_int, [vp, vp, vp, vp, u64, vp, pp, pu64]),
     "gtars_tokenize_into": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, u64, pu64]),
     "gtars_count_overlaps_device": (C.c_int, [vp, vp, vp, vp, u64, C.c_int, i32, vp, vp]),

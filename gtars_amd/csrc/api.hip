@@ -17,6 +17,7 @@
 #include <unordered_map>
 
 #include "common.h"
+#include "countmat.h"
 #include "pipeline.h"
 #include "../../include/gtars_amd_debug.h"
 
@@ -1309,6 +1310,20 @@ gtars_status gtars_histogram_rows_device(const uint64_t *d_offsets, const uint32
     gtars_status st = require_device();
     if (st) return st;
     return launch_hist_rows(d_offsets, d_ids, d_row, nq, row0, n_rows, n_cols, d_mat, (hipStream_t)stream);
+}
+
+gtars_status gtars_count_matrix_csr_device(const uint64_t *d_offsets, const uint32_t *d_ids, const uint32_t *d_row, uint64_t nq,
+                                           uint32_t n_rows, uint32_t n_cols, uint64_t *d_indptr, uint32_t *d_indices, uint32_t *d_data,
+                                           uint64_t capacity, uint64_t *nnz, void *stream) {
+    return guarded([&]() -> gtars_status {
+        if (!nnz || !d_indptr) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        if (nq && (!d_offsets || !d_row)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (capacity && (!d_indices || !d_data)) return fail(GTARS_ERR_INVALID_ARG, "NULL output");
+        if (n_rows > COUNTMAT_MAX_ROWS)
+            return fail(GTARS_ERR_INVALID_ARG, "too many rows for one count matrix (" + std::to_string(n_rows) + ")");
+        GT_TRY(require_device());
+        return count_matrix_csr(d_offsets, d_ids, d_row, nq, n_rows, n_cols, d_indptr, d_indices, d_data, capacity, nnz, stream);
+    });
 }
 
 static gtars_status fill_device(const gtars_index_t *ix, const uint32_t *d_qc, const uint32_t *d_qs, const uint32_t *d_qe, uint64_t nq,

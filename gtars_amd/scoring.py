@@ -8,12 +8,15 @@ ATAC mode probes the cut sites  [start+4, start+5)  and the INVERTED interval  [
 (Interval::overlap, gtars-core/src/models/interval.rs:47-50); ChIP mode probes the fragment itself.
 Fragment files are read by the C++ in-place parser; every file's probes go through one batched tokenization on
 the device and their token ids are scatter-added into the file's row of a device-resident matrix.
+``barcode_count_matrix`` is the single-cell form as a sparse matrix: the hits of one tokenization become a CSR barcode x peak
+matrix on the device (``gtars_count_matrix_csr_device``) -- ``SparseCounts``.
 """
 from __future__ import annotations
 
 import ctypes as C
 import glob as _glob
-from typing import Dict, Sequence, Union
+import os
+from typing import Dict, List, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -168,6 +171,159 @@ def barcode_scoring_from_fragments(fragment_file: str, consensus: Union[str, Con
         for ri, ki, v in zip(r.tolist(), k.tolist(), m[r, k].tolist()):
             out.setdefault(barcodes[row0 + ri], {})[ki] = v
     return out
+
+
+class SparseCounts:
+    """A barcode x peak count matrix in CSR: row ``i`` (labelled ``barcodes[i]``) holds the peaks ``indices[indptr[i]:indptr[i + 1]]``
+    in ascending order with the counts ``data[...]``.  ``indptr`` is int64, ``indices`` int32 and ``data`` the u32 counts viewed as
+    int32 (bit-identical), as numpy arrays or -- from ``barcode_count_matrix(..., device=True)`` -- as torch tensors on the device;
+    the methods below bring a device-resident matrix to the host first."""
+
+    def __init__(self, barcodes: Sequence[str], indptr, indices, data, shape: Tuple[int, int]):
+        self.barcodes: List[str] = list(barcodes)
+        self.indptr, self.indices, self.data = indptr, indices, data
+        self.shape = (int(shape[0]), int(shape[1]))
+        if len(self.barcodes) != self.shape[0] or len(indptr) != self.shape[0] + 1 or len(indices) != len(data):
+            raise ValueError("SparseCounts: labels, indptr and shape disagree")
+
+    @property
+    def nnz(self) -> int:
+        return int(len(self.data))
+
+    def _host(self):
+        """-> (indptr int64, indices int64, counts as unsigned int64) on the host"""
+        a = [x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x) for x in (self.indptr, self.indices, self.data)]
+        return a[0].astype(np.int64), a[1].astype(np.int64), np.ascontiguousarray(a[2], dtype=np.int32).view(np.uint32).astype(np.int64)
+
+    def to_dict(self) -> Dict[str, Dict[int, int]]:
+        """barcode -> {peak index -> count}, the form of ``barcode_scoring_from_fragments``; a row kept without any count
+        (``keep_empty=True``) is an empty dict."""
+        indptr, indices, data = (x.tolist() for x in self._host())
+        return {bc: dict(zip(indices[indptr[i]:indptr[i + 1]], data[indptr[i]:indptr[i + 1]])) for i, bc in enumerate(self.barcodes)}
+
+    def to_scipy(self):
+        """-> ``scipy.sparse.csr_matrix`` of uint32 counts"""
+        from scipy.sparse import csr_matrix
+
+        indptr, indices, data = self._host()
+        return csr_matrix((data.astype(np.uint32), indices.astype(np.int32), indptr), shape=self.shape)
+
+    def write_mtx(self, output_prefix: str) -> None:
+        """The three files of ``write_sparse_counts_to_mtx(self.to_dict(), n_peaks, prefix)``, written from the arrays: rows in the
+        bytewise order of their labels, triplets by (row, column), 1-based."""
+        import gzip
+
+        indptr, indices, data = self._host()
+        order = sorted(range(len(self.barcodes)), key=lambda i: self.barcodes[i].encode())  # Rust's String order is byte order
+        with gzip.open(f"{output_prefix}_matrix.mtx.gz", "wt", compresslevel=6, newline="\n") as fh:
+            fh.write("%%MatrixMarket matrix coordinate integer general\n")
+            fh.write(f"{self.shape[0]} {self.shape[1]} {len(data)}\n")
+            for ri, i in enumerate(order):
+                a, b = int(indptr[i]), int(indptr[i + 1])
+                if a < b:
+                    fh.write("".join(f"{ri + 1} {c + 1} {v}\n" for c, v in zip(indices[a:b].tolist(), data[a:b].tolist())))
+        with gzip.open(f"{output_prefix}_barcodes.tsv.gz", "wt", compresslevel=6, newline="\n") as fh:
+            fh.write("".join(f"{self.barcodes[i]}\n" for i in order))
+        with gzip.open(f"{output_prefix}_features.tsv.gz", "wt", compresslevel=6, newline="\n") as fh:
+            fh.write("".join(f"peak_{i}\n" for i in range(self.shape[1])))
+
+
+def _stem(path: str) -> str:
+    """the file name without ANY extension (remove_all_extensions, gtars-core/src/utils.rs:372-387), as gtars_fragsplit forms
+    its ``{stem}+{barcode}`` keys"""
+    stem = os.path.basename(str(path))
+    while True:
+        dot = stem.rfind(".")
+        if dot <= 0:
+            return stem
+        stem = stem[:dot]
+
+
+def count_matrix_csr_device(d_offsets: int, d_ids: int, d_row: int, nq: int, n_rows: int, n_cols: int, d_indptr: int, d_indices: int,
+                            d_data: int, capacity: int, stream: int = 0) -> int:
+    """``gtars_count_matrix_csr_device`` on device pointers (include/gtars_amd.h); -> nnz.  ``CapacityError.needed`` is the
+    number of entries when ``capacity`` is too small."""
+    nnz = C.c_uint64()
+    check(lib.gtars_count_matrix_csr_device(d_offsets, d_ids, d_row, nq, n_rows, n_cols, d_indptr, d_indices, d_data, capacity,
+                                            C.byref(nnz), stream))
+    return int(nnz.value)
+
+
+def barcode_count_matrix(fragments: Union[str, Sequence[str]], consensus: Union[str, ConsensusSet], scoring_mode: str = "chip",
+                         keep_empty: bool = False, device: bool = False) -> SparseCounts:
+    """The barcode x peak counts of one fragment file (rows = its barcodes) or of several (one matrix, rows labelled
+    ``{stem}+{barcode}``) as a CSR matrix built on the device; rows in the bytewise order of their labels.
+
+    ``"chip"`` probes the fragment itself, as ``barcode_scoring_from_fragments`` does; ``"atac"`` its two cut sites.  All files go
+    through ONE tokenization (``gtars_tokenize_device``) and one CSR build (``gtars_count_matrix_csr_device``: sort of the (row,
+    peak) pairs, run lengths); the rank of every barcode in the sorted order is computed here and uploaded as the probes' rows.
+    ``keep_empty``: keep the barcodes without any count as empty rows.  ``device``: leave indptr / indices / data on the device."""
+    import torch
+
+    mode = scoring_mode.lower()
+    if mode not in ("atac", "chip"):
+        raise ValueError(f"Invalid scoring mode: {scoring_mode}")
+    single = isinstance(fragments, (str, os.PathLike))
+    files = [str(fragments)] if single else [str(f) for f in fragments]
+    cons = consensus if isinstance(consensus, ConsensusSet) else ConsensusSet(consensus)
+    n_peaks = len(cons)
+    # the global barcode dictionary: every file's labels, ranked in byte order
+    parts, labels = [], []
+    for path in files:
+        c, s, e, b, names = _read_fragments(path, cons)
+        labels.append(names if single else [f"{_stem(path)}+{nm}" for nm in names])
+        parts.append((c, s, e, b))
+    ordered = sorted({lb for ls in labels for lb in ls}, key=lambda x: x.encode())
+    rank = {lb: i for i, lb in enumerate(ordered)}
+    qc, qs, qe, qr = [], [], [], []
+    for (c, s, e, b), ls in zip(parts, labels):
+        if len(c) == 0:
+            continue
+        ps, pe, k = _probes(s, e, mode)
+        row_of = np.asarray([rank[lb] for lb in ls], dtype=np.uint32)
+        qc.append(np.repeat(c, k))
+        qs.append(ps)
+        qe.append(pe)
+        qr.append(np.repeat(row_of[b], k))
+    n_rows = len(ordered)
+    nq = sum(len(x) for x in qc)
+
+    def finish(indptr, indices, data, host_indptr):
+        barcodes = ordered
+        if not keep_empty:
+            keep = host_indptr[1:] > host_indptr[:-1]
+            barcodes = [bc for bc, k in zip(ordered, keep.tolist()) if k]
+            host_indptr = np.concatenate([host_indptr[:1], host_indptr[1:][keep]])
+            indptr = torch.from_numpy(host_indptr).to(indices.device) if device else host_indptr
+        return SparseCounts(barcodes, indptr, indices, data, (len(barcodes), n_peaks))
+
+    if nq == 0 or n_peaks == 0 or n_rows == 0:
+        zi, z32 = np.zeros(n_rows + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
+        if device:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            return finish(torch.from_numpy(zi).to(dev), torch.from_numpy(z32).to(dev), torch.from_numpy(z32).to(dev), zi)
+        return finish(zi, z32, z32.copy(), zi)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream().cuda_stream
+    d = [torch.from_numpy(np.ascontiguousarray(np.concatenate(x)).view(np.int32)).to(dev) for x in (qc, qs, qe, qr)]
+    offsets = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    ids = torch.empty(2 * nq + 1024, dtype=torch.int32, device=dev)
+    try:
+        h = cons.index.tokenize_device(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), nq, offsets.data_ptr(), ids.data_ptr(),
+                                       ids.numel(), stream, sync=True)
+    except _lib.CapacityError as err:  # more than two peaks per probe on average: once more with the exact size
+        ids = torch.empty(err.needed, dtype=torch.int32, device=dev)
+        h = cons.index.tokenize_device(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), nq, offsets.data_ptr(), ids.data_ptr(),
+                                       ids.numel(), stream, sync=True)
+    indptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+    indices = torch.empty(max(h, 1), dtype=torch.int32, device=dev)  # nnz <= h: no retry
+    data = torch.empty(max(h, 1), dtype=torch.int32, device=dev)
+    nnz = count_matrix_csr_device(offsets.data_ptr(), ids.data_ptr(), d[3].data_ptr(), nq, n_rows, n_peaks, indptr.data_ptr(),
+                                  indices.data_ptr(), data.data_ptr(), h, stream)
+    host_indptr = indptr.cpu().numpy()
+    if device:
+        return finish(indptr, indices[:nnz].clone(), data[:nnz].clone(), host_indptr)
+    return finish(host_indptr, indices[:nnz].cpu().numpy(), data[:nnz].cpu().numpy(), host_indptr)
 
 
 def write_sparse_counts_to_mtx(barcode_counts: Dict[str, Dict[int, int]], num_peaks: int, output_prefix: str) -> None:

@@ -228,6 +228,18 @@ gtars_status gtars_histogram_u32_device(const uint32_t *d_ids, uint64_t n, uint3
 gtars_status gtars_histogram_rows_device(const uint64_t *d_offsets, const uint32_t *d_ids, const uint32_t *d_row, uint64_t nq,
                                          uint32_t row0, uint32_t n_rows, uint32_t n_cols, uint32_t *d_mat, void *stream);
 
+/* The same hits as a SPARSE count matrix in CSR (K16): d_indptr[n_rows + 1], and per row the occupied columns in ascending
+ * order (d_indices) with their counts (d_data): d_data[k] = the number of hits (q, id) with d_row[q] == r and id ==
+ * d_indices[k], k in [d_indptr[r], d_indptr[r + 1]).  A hit with id >= n_cols and every hit of a query with d_row[q] >= n_rows
+ * is dropped, as gtars_histogram_rows_device drops them.  Device pointers; the inputs are only read; the stream is drained on
+ * return.  d_indices / d_data have room for `capacity` entries; *nnz never exceeds d_offsets[nq], so a caller that allocates
+ * that many never retries.  capacity < *nnz: GTARS_ERR_CAPACITY with *nnz set, nothing written to d_indices / d_data
+ * (d_indptr may be).  nq == 0 or no hits: *nnz = 0, d_indptr all zero.  GTARS_ERR_INVALID_ARG: 2^32 - 4096 hits or more (one
+ * lane per hit, a 32-bit sort), n_rows >= 2^31 - 1, a NULL where a length is not zero. */
+gtars_status gtars_count_matrix_csr_device(const uint64_t *d_offsets, const uint32_t *d_ids, const uint32_t *d_row, uint64_t nq,
+                                           uint32_t n_rows, uint32_t n_cols, uint64_t *d_indptr, uint32_t *d_indices,
+                                           uint32_t *d_data, uint64_t capacity, uint64_t *nnz, void *stream);
+
 /* ------------------------------------------------------------------------
  * Counts / any / find with the optional min-overlap filter.
  * Replaces MultiChromOverlapper::count_overlaps / any_overlaps /
