@@ -11,14 +11,16 @@ reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats``
 ``GenomeAssembly``, ``BinaryGenomeAssembly``, ``calc_gc_content`` and ``calc_dinucl_freq``, which the reference keeps in
 ``gtars.models`` and ``gtars.genomic_distributions``; ``gtars.signal`` likewise holds ``SignalMatrix`` and
 ``calc_summary_signal``, and ``gtars.partitions`` holds ``PartitionList``, ``calc_partitions`` and ``calc_expected_partitions``.
+``gtars.bam`` holds ``BamFile``, ``read_bam_header`` and the BAM QC of ``gtars uniwig bamqc`` (``compute_bam_qc``, ``run_bam_qc``,
+``write_bam_qc_tsv``).
 """
 import sys as _sys
 
 import gtars_amd as _impl
-from gtars_amd import fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils  # noqa: F401
+from gtars_amd import bam, fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils  # noqa: F401
 
-for _name in ("tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions"):
+for _name in ("bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions"):
     _sys.modules[f"{__name__}.{_name}"] = getattr(_sys.modules[__name__], _name)
 
 __version__ = _impl.__version__
-__all__ = ["tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions"]
+__all__ = ["bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions"]

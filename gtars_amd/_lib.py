@@ -308,6 +308,21 @@ _HOST_SIG = {
     "gtars_lola_fdr": (C.c_int, [vp, vp, u64, vp]),
     "gtars_lola_fisher_pvalue": (C.c_double, [u64, u64, u64, u64, C.c_int]),
     "gtars_lola_odds_ratio": (C.c_double, [u64, u64, u64, u64]),
+    "gtars_bam_open": (C.c_int, [cstr, pp]),
+    "gtars_bam_close": (None, [vp]),
+    "gtars_bam_header_text": (cstr, [vp]),
+    "gtars_bam_n_ref": (u32, [vp]),
+    "gtars_bam_ref_name": (cstr, [vp, u32]),
+    "gtars_bam_ref_len": (u32, [vp, u32]),
+    "gtars_bam_n_blocks": (u64, [vp]),
+    "gtars_bam_n_bytes": (u64, [vp]),
+    "gtars_bam_first_record": (u64, [vp]),
+    "gtars_bam_block_table": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "gtars_bam_inflate": (C.c_int, [vp, u64, u64, vp, u64, u32]),
+    "gtars_bam_record_offsets": (C.c_int, [vp, vp, u64, u64, C.c_int, pp, pu64, pu64]),
+    "gtars_bam_decode": (C.c_int, [vp, u64, u64, u64, u32, pp, pu64]),
+    "gtars_bam_qc": (C.c_int, [vp, u64, u32, vp]),
+    "gtars_bam_last_stages": (None, [vp]),
 }
 
 # include/gtars_amd_debug.h: test / A-B / diagnostics hooks, not part of the drop-in boundary

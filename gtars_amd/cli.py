@@ -12,6 +12,8 @@
                              [--outputtype wig|bedGraph|npy] [--counttype all|start|end|core] [--wigstep fixed|variable]
       gtars-cli/src/uniwig/cli.rs:38-178, handlers.rs:48-160 for BED input: the coverage tracks of gtars_amd.uniwig.  BAM
       input (--filetype bam) and bigWig output (--outputtype bw) are not provided and exit with a message.
+  python -m gtars_amd uniwig bamqc --input X.bam --output Y.tsv [--threads N]
+      gtars-cli/src/uniwig/cli.rs, gtars-uniwig/src/bamqc.rs: the library-complexity QC of a coordinate-sorted BAM as a TSV.
 
 Same rules as the reference: fields are split on TAB only, coordinates must parse as u32 (``+5`` is accepted, blanks and
 signs are not), every line counts (no header skipping in overlaprs).  The whole query file is ONE batch on the device.
@@ -173,7 +175,23 @@ def run_uniwig(a) -> int:
     return 0
 
 
+def bamqc_parser() -> argparse.ArgumentParser:
+    q = argparse.ArgumentParser(prog="python -m gtars_amd uniwig bamqc", description="Library-complexity QC of a coordinate-sorted BAM file")
+    q.add_argument("--input", "-i", required=True, help="Path to the BAM file")
+    q.add_argument("--output", "-o", required=True, help="Path of the TSV to write")
+    q.add_argument("--threads", "-t", type=int, default=1, help="Host threads that inflate")
+    return q
+
+
 def main(argv: Sequence[str] = None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    # `uniwig bamqc` is a command of its own under uniwig: uniwig's own options are all required, so it cannot be one of them
+    if argv[:2] == ["uniwig", "bamqc"]:
+        a = bamqc_parser().parse_args(argv[2:])
+        from .bam import run_bam_qc
+
+        run_bam_qc(a.input, a.output, a.threads)
+        return 0
     ap = argparse.ArgumentParser(prog="python -m gtars_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     o = sub.add_parser("overlaprs", help="Find overlaps between a query file and a universe file")

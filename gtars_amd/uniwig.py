@@ -23,6 +23,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from ._lib import as_u32, check, lib, ptr, take_u32
+from .bam import read_bam_header  # noqa: F401  (reading.rs:279-319 lives beside the BED readers)
 
 KINDS = {"start": 0, "end": 1, "core": 2}
 WIG_CHUNK = 1 << 22  # entries formatted per call of the C++ writer

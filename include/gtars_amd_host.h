@@ -705,6 +705,50 @@ gtars_status gtars_lola_fdr(const double *p_value_log, const uint64_t *user_set,
 double gtars_lola_fisher_pvalue(uint64_t a, uint64_t b, uint64_t c, uint64_t d, int direction);
 double gtars_lola_odds_ratio(uint64_t a, uint64_t b, uint64_t c, uint64_t d);
 
+/* ------------------------------------------------------------------------
+ * BAM input and BAM QC  (K17; gtars-uniwig/src/reading.rs:279-319, bamqc.rs:68-245)
+ * ---------------------------------------------------------------------- */
+/* A BAM file: its BGZF block table (one pass over the file, nothing decoded), its header, and the entry points that read
+ * its records.  Coordinate-sorted files only (refID never descends, unplaced records last); no .bai is needed or read.
+ * Host threads only inflate; the records are decoded and the QC is computed on the device (GTARS_ERR_NO_DEVICE
+ * without one).  A damaged container or record is GTARS_ERR_PARSE with the block's or the record's index. */
+typedef struct gtars_bam gtars_bam_t;
+typedef struct {
+    uint64_t total_reads; /* joined pairs if any reference held a paired read, else reads - mitochondrial reads */
+    uint64_t distinct, m1, m2, dups, mito_reads;
+    double nrf, pbc1, pbc2;
+} gtars_bam_qc_result;
+
+gtars_status gtars_bam_open(const char *path, gtars_bam_t **out);
+void gtars_bam_close(gtars_bam_t *b);
+const char *gtars_bam_header_text(const gtars_bam_t *b);
+uint32_t gtars_bam_n_ref(const gtars_bam_t *b);
+const char *gtars_bam_ref_name(const gtars_bam_t *b, uint32_t i);
+uint32_t gtars_bam_ref_len(const gtars_bam_t *b, uint32_t i);
+uint64_t gtars_bam_n_blocks(const gtars_bam_t *b);
+uint64_t gtars_bam_n_bytes(const gtars_bam_t *b);      /* inflated */
+uint64_t gtars_bam_first_record(const gtars_bam_t *b); /* inflated offset behind the header */
+/* per block (any array may be NULL): offset and size in the file, ISIZE, CRC-32 and offset in the inflated stream */
+gtars_status gtars_bam_block_table(const gtars_bam_t *b, uint64_t *coff, uint32_t *csize, uint32_t *isize, uint32_t *crc,
+                                   uint64_t *uoff);
+/* blocks [block0, block1) inflated to dst (block k at uoff[k] - uoff[block0]); every block's length and CRC-32 are
+ * checked.  threads: 0 = gtars_host_threads(0), never more than that. */
+gtars_status gtars_bam_inflate(const gtars_bam_t *b, uint64_t block0, uint64_t block1, void *dst, uint64_t capacity,
+                               uint32_t threads);
+/* the offsets (of the block_size fields) of the records in data[begin, n), gtars_free; *consumed: where the first
+ * incomplete record starts (an error when final != 0) */
+gtars_status gtars_bam_record_offsets(const gtars_bam_t *b, const void *data, uint64_t n, uint64_t begin, int final,
+                                      uint64_t **offsets, uint64_t *count, uint64_t *consumed);
+/* records [first, first + count) of the file, decoded on the device: *cols = 7 arrays of *n int32 one behind the other
+ * (refID, pos, end = pos + the CIGAR's reference span, flag, mapq, l_seq, tlen), gtars_free.
+ * max_window_bytes: inflated bytes per device window, 0 = 256 MiB. */
+gtars_status gtars_bam_decode(const gtars_bam_t *b, uint64_t first, uint64_t count, uint64_t max_window_bytes,
+                              uint32_t threads, int32_t **cols, uint64_t *n);
+gtars_status gtars_bam_qc(const gtars_bam_t *b, uint64_t max_window_bytes, uint32_t threads, gtars_bam_qc_result *out);
+/* the calling thread's last gtars_bam_qc / gtars_bam_decode: seconds of open (read + block table + header), inflate,
+ * record walk; windows; records; seconds of the whole call */
+void gtars_bam_last_stages(double *out6);
+
 #ifdef __cplusplus
 }
 #endif
