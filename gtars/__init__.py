@@ -5,22 +5,24 @@ code reads ``from gtars.tokenizers import Tokenizer``, ``from gtars.models impor
 ``from gtars.utils import read_tokens_from_gtok``, ``from gtars.lola import RegionDB, run_lola``.  This package makes
 those imports resolve to the MI355X implementation (gtars_amd.*) without edits to the calling code.
 ``gtars.genomic_distributions`` provides ``consensus`` and ``median_abs_distance``, the functions of that module that need
-nothing beyond region sets.  Sub-modules the hot path does not cover (refget, vrs, reftx) are not provided: importing
+nothing beyond region sets.  Sub-modules the hot path does not cover (refget, reftx) are not provided: importing
 them raises ModuleNotFoundError, not a silent stub.  ``gtars.igd``, ``gtars.scoring`` and ``gtars.fragsplit`` are additive (the
 reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats`` is additive too: it holds
 ``GenomeAssembly``, ``BinaryGenomeAssembly``, ``calc_gc_content`` and ``calc_dinucl_freq``, which the reference keeps in
 ``gtars.models`` and ``gtars.genomic_distributions``; ``gtars.signal`` likewise holds ``SignalMatrix`` and
 ``calc_summary_signal``, and ``gtars.partitions`` holds ``PartitionList``, ``calc_partitions`` and ``calc_expected_partitions``.
 ``gtars.bam`` holds ``BamFile``, ``read_bam_header`` and the BAM QC of ``gtars uniwig bamqc`` (``compute_bam_qc``, ``run_bam_qc``,
-``write_bam_qc_tsv``).
+``write_bam_qc_tsv``).  ``gtars.vrs`` holds the reference's four functions (``vrs_digest``, ``vrs_id``, ``normalize_allele``,
+``location_digest``) and the batch calls on top of the device kernels (``normalize_alleles``, ``vrs_ids``, ``compute_vrs_ids``);
+its ``hgvs`` sub-module is not provided.
 """
 import sys as _sys
 
 import gtars_amd as _impl
-from gtars_amd import bam, fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils  # noqa: F401
+from gtars_amd import bam, fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils, vrs  # noqa: F401
 
-for _name in ("bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions"):
+for _name in ("bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs"):
     _sys.modules[f"{__name__}.{_name}"] = getattr(_sys.modules[__name__], _name)
 
 __version__ = _impl.__version__
-__all__ = ["bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions"]
+__all__ = ["bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs"]

@@ -323,6 +323,18 @@ _HOST_SIG = {
     "gtars_bam_decode": (C.c_int, [vp, u64, u64, u64, u32, pp, pu64]),
     "gtars_bam_qc": (C.c_int, [vp, u64, u32, vp]),
     "gtars_bam_last_stages": (None, [vp]),
+    "gtars_sha512t24u": (C.c_int, [vp, u64, vp]),
+    "gtars_vrs_location_digest": (C.c_int, [cstr, u64, u64, vp]),
+    "gtars_vrs_allele_digest": (C.c_int, [cstr, u64, u64, vp, u64, vp]),
+    "gtars_vrs_normalize": (C.c_int, [vp, u64, u64, vp, u64, vp, u64, pu64, pu64, pp, pu64]),
+    "gtars_assembly_refget_digests": (C.c_int, [vp, u32, pp]),
+    "gtars_vrs_alleles": (C.c_int, [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, C.c_int, u32, vp, vp, vp, vp, pp, pp]),
+    "gtars_vrs_ids_device": (C.c_int, [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+    "gtars_vcf_read_alleles": (C.c_int, [vp, cstr, vp, u32, pp]),
+    "gtars_vrs_from_vcf": (C.c_int, [vp, cstr, vp, C.c_int, u32, pp]),
+    "gtars_vrs_results_free": (None, [vp]),
+    "gtars_vrs_results_len": (u64, [vp]),
+    "gtars_vrs_results_columns": (C.c_int, [vp, pp, pp, pp, pu64, pp, pp, pp, pp, pp]),
 }
 
 # include/gtars_amd_debug.h: test / A-B / diagnostics hooks, not part of the drop-in boundary
@@ -330,6 +342,7 @@ _DEBUG_SIG = {
     "gtars_debug_occupy_device": (C.c_int, [vp, u32, u32, u32]),
     "gtars_debug_reload_env": (None, []),
     "gtars_debug_set_handle_device": (C.c_int, [vp, C.c_int, C.c_int]),
+    "gtars_debug_set_assembly_device": (C.c_int, [vp, C.c_int]),
     "gtars_debug_inflate_streams": (C.c_int, [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
     "gtars_debug_sort_perm": (C.c_int, [vp, vp, vp, u64, u32, vp]),
     "gtars_debug_scan_u32": (C.c_int, [vp, u64, vp]),

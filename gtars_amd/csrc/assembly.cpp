@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
+#include "assembly.h"
 #include "seqstats.h"
 
 namespace gtars {
@@ -23,29 +24,21 @@ gtars_status fail(gtars_status st, const std::string &msg);
 }
 using gtars::fail;
 
-struct gtars_assembly {
-    std::vector<std::string> names;  // chromosome id -> name, ids in order of first appearance
-    std::unordered_map<std::string, uint32_t> id;
-    std::string blob;                // FASTA: the records' sequences back to back; .fab: the file
-    std::vector<uint64_t> off, len;  // per chromosome id: its bytes in blob (the LAST record / entry of the name)
-    std::mutex mu;                   // guards the lazy device image
-    gtars::Assembly *dev = nullptr;
-    ~gtars_assembly() { gtars::assembly_free(dev); }
-    void put(const std::string &name, uint64_t o, uint64_t l) {
-        auto it = id.find(name);
-        if (it == id.end()) {
-            id.emplace(name, (uint32_t)names.size());
-            names.push_back(name);
-            off.push_back(o);
-            len.push_back(l);
-        } else {
-            off[it->second] = o;
-            len[it->second] = l;
-        }
+// the handle's device image, built at the first call on the device current then
+gtars_status gtars::assembly_device_image(gtars_assembly *a, gtars::Assembly **out) {
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (!a->dev) {
+        std::vector<const uint8_t *> seq(a->names.size());
+        for (size_t c = 0; c < seq.size(); ++c) seq[c] = (const uint8_t *)a->blob.data() + a->off[c];
+        if (const gtars_status e = gtars::assembly_build(seq.data(), a->len.data(), (uint32_t)seq.size(), &a->dev)) return e;
     }
-};
+    *out = a->dev;
+    return GTARS_OK;
+}
 
 namespace {
+
+using gtars::assembly_device_image;
 
 template <class F>
 gtars_status guarded(F &&f) {
@@ -222,24 +215,12 @@ gtars_status select_rows(const gtars_assembly *a, const gtars_regionset_t *rs, b
     return GTARS_OK;
 }
 
-// the handle's device image, built at the first call on the device current then
-gtars_status device_image(gtars_assembly *a, gtars::Assembly **out) {
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (!a->dev) {
-        std::vector<const uint8_t *> seq(a->names.size());
-        for (size_t c = 0; c < seq.size(); ++c) seq[c] = (const uint8_t *)a->blob.data() + a->off[c];
-        if (const gtars_status e = gtars::assembly_build(seq.data(), a->len.data(), (uint32_t)seq.size(), &a->dev)) return e;
-    }
-    *out = a->dev;
-    return GTARS_OK;
-}
-
 gtars_status counts_of(gtars_assembly *a, const Rows &r, int mode, std::vector<uint32_t> &counts) {
     const uint64_t n = r.src.size();
     counts.assign(n * (mode == GTARS_SEQ_GC ? 1 : 16), 0);
     if (!n) return GTARS_OK;
     gtars::Assembly *dev;
-    if (const gtars_status e = device_image(a, &dev)) return e;
+    if (const gtars_status e = assembly_device_image(a, &dev)) return e;
     return gtars::seqstats_counts(*dev, r.chrom.data(), r.start.data(), r.end.data(), n, mode, counts.data());
 }
 
@@ -366,6 +347,14 @@ int gtars_assembly_device(const gtars_assembly_t *a) {
     return gtars::assembly_device(a->dev);
 }
 
+// include/gtars_amd_debug.h: forge the device id the image records (tests of the device-affinity checks on a one-GPU box)
+int gtars_debug_set_assembly_device(void *assembly, int device) {
+    gtars_assembly_t *a = (gtars_assembly_t *)assembly;
+    if (!a) return -1;
+    std::lock_guard<std::mutex> lk(a->mu);
+    return a->dev ? gtars::assembly_set_device(a->dev, device) : -1;
+}
+
 uint32_t gtars_seqstats_piece_bytes(void) { return gtars::SEQ_PIECE; }
 
 gtars_status gtars_seqstats_counts_device(gtars_assembly_t *a, const uint32_t *d_chrom, const uint32_t *d_start,
@@ -376,7 +365,7 @@ gtars_status gtars_seqstats_counts_device(gtars_assembly_t *a, const uint32_t *d
             return fail(GTARS_ERR_INVALID_ARG, "seqstats: unknown mode " + std::to_string(mode));
         if (!n) return GTARS_OK;
         gtars::Assembly *dev;
-        if (const gtars_status e = device_image(a, &dev)) return e;
+        if (const gtars_status e = assembly_device_image(a, &dev)) return e;
         return gtars::seqstats_counts_device(*dev, d_chrom, d_start, d_end, n, mode, d_out, stream);
     });
 }

@@ -249,7 +249,8 @@ bool inflate_gzip_members_raw(const unsigned char *p, size_t n, Out &out, std::v
     return true;
 }
 
-bool read_all(const std::string &path, std::string &out, std::string &err) {
+// by_magic: gunzip whatever starts with the gzip magic, whatever the extension (open_vcf, gtars-vrs/src/vcf.rs:56-73)
+bool read_all(const std::string &path, std::string &out, std::string &err, bool by_magic = false) {
     out.clear();
     std::string raw;
     size_t n_raw = 0;
@@ -257,7 +258,7 @@ bool read_all(const std::string &path, std::string &out, std::string &err) {
         err = "Failed to open file: \"" + path + "\": " + strerror(errno);
         return false;
     }
-    if (extension_of(path) != "gz" || n_raw < 2 || (unsigned char)raw[0] != 0x1f || (unsigned char)raw[1] != 0x8b) {
+    if ((!by_magic && extension_of(path) != "gz") || n_raw < 2 || (unsigned char)raw[0] != 0x1f || (unsigned char)raw[1] != 0x8b) {
         raw.resize(n_raw);
         out.swap(raw);  // plain text (or a ".gz" without the magic: zlib's transparent mode)
         return true;
@@ -342,6 +343,16 @@ bool read_all(const std::string &path, std::string &out, std::string &err) {
     out.resize(out_done);
     return true;
 }
+
+}  // namespace
+
+namespace gtars {
+// the file's bytes for vrs.cpp: plain, gzip or BGZF by the magic bytes
+bool read_file_by_magic(const std::string &path, std::string &out, std::string &err) { return read_all(path, out, err, true); }
+unsigned host_threads_for(unsigned cap) { return host_thread_budget(cap); }
+}  // namespace gtars
+
+namespace {
 
 // BufRead::lines(): split on '\n', strip one trailing '\r'; no empty last line after a final '\n'
 struct LineIter {

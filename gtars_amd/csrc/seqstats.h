@@ -22,6 +22,16 @@ struct Assembly;
 gtars_status assembly_build(const uint8_t *const *seq, const uint64_t *len, uint32_t n_chrom, Assembly **out);
 void assembly_free(Assembly *a);
 int assembly_device(const Assembly *a);
+// the image's parts for the other kernels that read it (vrs.hip): device pointers, valid while the image lives
+struct AssemblyParts {
+    const uint8_t *seq;   // the packed bytes
+    const uint64_t *off;  // [n_chrom] offset of every chromosome in seq
+    const uint64_t *len;  // [n_chrom]
+    uint32_t n_chrom;
+    int device;
+};
+AssemblyParts assembly_parts(const Assembly &a);
+int assembly_set_device(Assembly *a, int device);  // test hook (gtars_debug_set_assembly_device): -> the id recorded before
 
 // d_chrom / d_start / d_end: n device rows, chromosome ids of the assembly, every row with start <= end <= len (a row
 // that is not fails the call with GTARS_ERR_INVALID_ARG and is never read from the image).

@@ -315,6 +315,14 @@ void assembly_free(Assembly *a) {
 
 int assembly_device(const Assembly *a) { return a ? a->device : -1; }
 
+AssemblyParts assembly_parts(const Assembly &a) { return AssemblyParts{a.seq.p, a.off.p, a.len.p, a.n_chrom, a.device}; }
+
+int assembly_set_device(Assembly *a, int device) {
+    const int before = a->device;
+    a->device = device;
+    return before;
+}
+
 gtars_status seqstats_counts_device(const Assembly &a, const uint32_t *d_chrom, const uint32_t *d_start, const uint32_t *d_end,
                                     uint64_t n, int mode, uint32_t *d_out, void *stream) {
     GT_TRY(check_call(a, n, mode));

@@ -96,6 +96,15 @@ class _Assembly:
         check(lib.gtars_assembly_sequence(self._h, str(chr).encode("utf-8"), _u64(start), _u64(end), C.byref(p)))
         return C.string_at(p, int(end) - int(start))
 
+    def refget_digests(self, threads: int = 0) -> Dict[str, str]:
+        """chromosome name -> sha512t24u of its upper-cased bytes (the GA4GH refget digest, without "SQ."): computed once per
+        assembly, one chromosome per host task, and kept on the handle; what ``gtars.vrs`` names a chromosome by"""
+        p = C.c_void_p()
+        check(lib.gtars_assembly_refget_digests(self._h, int(threads), C.byref(p)))
+        names = self.chrom_names
+        blob = C.string_at(p, 33 * len(names))
+        return {name: blob[33 * k:33 * k + 32].decode("ascii") for k, name in enumerate(names)}
+
     @property
     def device(self) -> int:
         """the device that holds the packed image; -1 until the first counting call"""

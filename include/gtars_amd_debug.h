@@ -29,6 +29,9 @@ void gtars_debug_reload_env(void);
  * to switch to that device, which is what tests/test_gpu_parity.py asserts on a one-GPU box.  Put the real id back before
  * any other use. */
 int gtars_debug_set_handle_device(void *handle, int is_igd, int device);
+/* The same for the device image of an assembly handle (gtars_assembly_t *, include/gtars_amd_host.h): -1 when the image
+ * is not built yet.  tests/test_gpu_vrs.py. */
+int gtars_debug_set_assembly_device(void *assembly, int device);
 
 /* Test / measurement entry of the device-side DEFLATE decoder (csrc/inflate_dev.hip; the fused fragment pipeline's input stage,
  * gtars-fragsplit/src/split.rs:84-131 reads its files through flate2's MultiGzDecoder): n_streams raw DEFLATE streams (RFC 1951, no

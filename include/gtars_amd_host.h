@@ -749,6 +749,70 @@ gtars_status gtars_bam_qc(const gtars_bam_t *b, uint64_t max_window_bytes, uint3
  * record walk; windows; records; seconds of the whole call */
 void gtars_bam_last_stages(double *out6);
 
+/* ------------------------------------------------------------------------
+ * VRS allele identifiers  (K18; gtars-vrs/src/normalize.rs:362-441, digest.rs:52-86, vcf_core.rs:35-189, vcf.rs:56-73;
+ * gtars-python/src/vrs/funcs.rs)
+ * ---------------------------------------------------------------------- */
+/* The scalar calls: host code, no device.  out33: 32 characters and a NUL.
+ * sha512t24u: the first 24 bytes of SHA-512 in base64url without padding.  The two digests hash the canonical texts of
+ * digest.rs:60-81 with `accession` written as given ("SQ." included) and the sequence as a literal state; neither is
+ * JSON-escaped (accessions are base64url, sequences nucleotide letters).
+ * gtars_vrs_normalize: normalize() over the caller's sequence bytes, which are read upper-cased; allele bytes are used as
+ * given.  *allele: gtars_free.  A failure is GTARS_ERR_INVALID_ARG with NormalizeError's text. */
+gtars_status gtars_sha512t24u(const void *data, uint64_t n, char *out33);
+gtars_status gtars_vrs_location_digest(const char *accession, uint64_t start, uint64_t end, char *out33);
+gtars_status gtars_vrs_allele_digest(const char *accession, uint64_t start, uint64_t end, const char *sequence,
+                                     uint64_t sequence_len, char *out33);
+gtars_status gtars_vrs_normalize(const uint8_t *sequence, uint64_t sequence_len, uint64_t start, const uint8_t *ref,
+                                 uint64_t ref_len, const uint8_t *alt, uint64_t alt_len, uint64_t *new_start, uint64_t *new_end,
+                                 uint8_t **allele, uint64_t *allele_len);
+/* sha512t24u of every chromosome's upper-cased bytes, one chromosome per host task (threads: 0 = as many as
+ * gtars_host_threads allows), computed once and kept on the handle.  *out: borrowed, 33 bytes per chromosome id (32
+ * characters and a NUL). */
+gtars_status gtars_assembly_refget_digests(gtars_assembly_t *a, uint32_t threads, const char **out);
+
+/* A batch of alleles as columns.  Allele i: chromosome id chrom[i] of the assembly, 0-based interbase start[i], REF =
+ * pool[ref_off[i], ref_off[i] + ref_len[i]), ALT likewise (rows may share pool bytes).  accessions: 32 digest characters per
+ * chromosome id, a row of zero bytes = none (its alleles get status 4); NULL: the assembly's own refget digests.
+ * Per allele (any output may be NULL): status -- 0, or 1 start + len(REF) overflows, 2 REF reaches past the chromosome's
+ * end (a start beyond the chromosome too), 3 REF differs from the assembly (the three kinds of NormalizeError), 4 unknown
+ * chromosome id / no accession, 5 allele bytes outside the pool --, the normalized interval, and the 32 characters of the
+ * Allele digest (zero bytes for a failed allele; "ga4gh:VA." is the caller's).  A call never fails for data.
+ * seq_offsets / seq_bytes (both or neither; gtars_free each): the normalized sequences as a byte CSR of n + 1 offsets.
+ * on_host != 0: the library's host path on `threads` threads (0 = gtars_host_threads), no device; otherwise the kernels
+ * of csrc/vrs.hip on the assembly's device (GTARS_ERR_NO_DEVICE without one). */
+gtars_status gtars_vrs_alleles(gtars_assembly_t *a, const char *accessions, const uint32_t *chrom, const uint64_t *start,
+                               const uint8_t *pool, uint64_t pool_bytes, const uint32_t *ref_off, const uint32_t *ref_len,
+                               const uint32_t *alt_off, const uint32_t *alt_len, uint64_t n, int on_host, uint32_t threads,
+                               uint8_t *status, uint64_t *new_start, uint64_t *new_end, char *digests, uint64_t **seq_offsets,
+                               uint8_t **seq_bytes);
+/* The same for columns, pool and outputs that are device memory (d_digests: n * 32 bytes, 8-byte aligned; any output may
+ * be NULL), queued on `stream`, which is drained before the call returns.  The current device must be the assembly's:
+ * anything else is refused, as by the other handle-taking device entries. */
+gtars_status gtars_vrs_ids_device(gtars_assembly_t *a, const char *accessions, const uint32_t *d_chrom, const uint64_t *d_start,
+                                  const uint8_t *d_pool, uint64_t pool_bytes, const uint32_t *d_ref_off, const uint32_t *d_ref_len,
+                                  const uint32_t *d_alt_off, const uint32_t *d_alt_len, uint64_t n, uint8_t *d_status,
+                                  uint64_t *d_new_start, uint64_t *d_new_end, char *d_digests, void *stream);
+
+/* The alleles of a VCF file: plain text, gzip or BGZF by the magic bytes, not the extension.  Lines: trailing CR / LF
+ * stripped; empty lines, lines starting with '#', lines with fewer than 5 tab-separated fields and lines whose POS is no
+ * u64 or is 0 are skipped; ALT is split on ',' and a piece is kept unless it is empty, starts with '<', or is "*" or ".";
+ * a row whose chromosome the assembly (or the accession table) lacks is skipped.  File order, ALTs in their order.
+ * gtars_vcf_read_alleles parses only (host); gtars_vrs_from_vcf also computes the digests and fails with
+ * "Failed to normalize variant at <chrom>:<POS>: <cause>" for the first allele in file order that does not normalize. */
+typedef struct gtars_vrs_results gtars_vrs_results_t;
+gtars_status gtars_vcf_read_alleles(gtars_assembly_t *a, const char *path, const char *accessions, uint32_t threads,
+                                    gtars_vrs_results_t **out);
+gtars_status gtars_vrs_from_vcf(gtars_assembly_t *a, const char *path, const char *accessions, int on_host, uint32_t threads,
+                                gtars_vrs_results_t **out);
+void gtars_vrs_results_free(gtars_vrs_results_t *r);
+uint64_t gtars_vrs_results_len(const gtars_vrs_results_t *r);
+/* borrowed columns of the results: chromosome ids, 0-based positions, the pool and the four allele columns, 32 digest
+ * characters per allele (*digests NULL after gtars_vcf_read_alleles) */
+gtars_status gtars_vrs_results_columns(const gtars_vrs_results_t *r, const uint32_t **chrom, const uint64_t **pos,
+                                       const uint8_t **pool, uint64_t *pool_bytes, const uint32_t **ref_off, const uint32_t **ref_len,
+                                       const uint32_t **alt_off, const uint32_t **alt_len, const char **digests);
+
 #ifdef __cplusplus
 }
 #endif
