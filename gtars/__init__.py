@@ -5,8 +5,8 @@ code reads ``from gtars.tokenizers import Tokenizer``, ``from gtars.models impor
 ``from gtars.utils import read_tokens_from_gtok``, ``from gtars.lola import RegionDB, run_lola``.  This package makes
 those imports resolve to the MI355X implementation (gtars_amd.*) without edits to the calling code.
 ``gtars.genomic_distributions`` provides ``consensus`` and ``median_abs_distance``, the functions of that module that need
-nothing beyond region sets.  Sub-modules the hot path does not cover (refget, reftx) are not provided: importing
-them raises ModuleNotFoundError, not a silent stub.  ``gtars.igd``, ``gtars.scoring`` and ``gtars.fragsplit`` are additive (the
+nothing beyond region sets.  The one sub-module that is not provided is refget: importing it raises
+ModuleNotFoundError, not a silent stub.  ``gtars.igd``, ``gtars.scoring`` and ``gtars.fragsplit`` are additive (the
 reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats`` is additive too: it holds
 ``GenomeAssembly``, ``BinaryGenomeAssembly``, ``calc_gc_content`` and ``calc_dinucl_freq``, which the reference keeps in
 ``gtars.models`` and ``gtars.genomic_distributions``; ``gtars.signal`` likewise holds ``SignalMatrix`` and
@@ -14,15 +14,18 @@ reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats``
 ``gtars.bam`` holds ``BamFile``, ``read_bam_header`` and the BAM QC of ``gtars uniwig bamqc`` (``compute_bam_qc``, ``run_bam_qc``,
 ``write_bam_qc_tsv``).  ``gtars.vrs`` holds the reference's four functions (``vrs_digest``, ``vrs_id``, ``normalize_allele``,
 ``location_digest``) and the batch calls on top of the device kernels (``normalize_alleles``, ``vrs_ids``, ``compute_vrs_ids``);
-its ``hgvs`` sub-module is not provided.
+its ``hgvs`` sub-module is not provided.  ``gtars.reftx`` holds the reference's transcript classes (``TxStoreBuilder``,
+``ReadonlyTxStore``, ``CoordinateMapper``, ``Transcript``, ``Exon``, ``ManeStatus``, ``Strand``, ``MappingError``, ``TxStoreError``) and, additive,
+the batch mapping calls and the spliced mRNA of every transcript on the device (``mature_mrna``, ``mature_mrnas``,
+``transcript_accessions``); ``ReftxProvider`` is not provided.
 """
 import sys as _sys
 
 import gtars_amd as _impl
-from gtars_amd import bam, fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils, vrs  # noqa: F401
+from gtars_amd import bam, fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils, vrs, reftx  # noqa: F401
 
-for _name in ("bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs"):
+for _name in ("bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs", "reftx"):
     _sys.modules[f"{__name__}.{_name}"] = getattr(_sys.modules[__name__], _name)
 
 __version__ = _impl.__version__
-__all__ = ["bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs"]
+__all__ = ["bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs", "reftx"]

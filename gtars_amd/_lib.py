@@ -335,6 +335,32 @@ _HOST_SIG = {
     "gtars_vrs_results_free": (None, [vp]),
     "gtars_vrs_results_len": (u64, [vp]),
     "gtars_vrs_results_columns": (C.c_int, [vp, pp, pp, pp, pu64, pp, pp, pp, pp, pp]),
+    "gtars_txbuilder_new": (C.c_int, [pp]),
+    "gtars_txbuilder_free": (None, [vp]),
+    "gtars_txbuilder_len": (u64, [vp]),
+    "gtars_txbuilder_add": (C.c_int, [vp, cstr, cstr, cstr, C.c_int, u32, u32, u32, vp, u64]),
+    "gtars_txbuilder_add_chrom_mapping": (C.c_int, [vp, cstr, cstr]),
+    "gtars_txbuilder_add_mane": (C.c_int, [vp, cstr, u32]),
+    "gtars_txbuilder_add_cdot": (C.c_int, [vp, cstr, cstr, cstr, i64, u32, u32, vp, u64, C.POINTER(C.c_int)]),
+    "gtars_txbuilder_bytes": (C.c_int, [vp, pp, pu64]),
+    "gtars_txbuilder_build": (C.c_int, [vp, cstr]),
+    "gtars_txstore_open": (C.c_int, [cstr, pp]),
+    "gtars_txstore_from_bytes": (C.c_int, [vp, u64, pp]),
+    "gtars_txstore_free": (None, [vp]),
+    "gtars_txstore_len": (u64, [vp]),
+    "gtars_txstore_has_mane": (C.c_int, [vp]),
+    "gtars_txstore_lookup": (i64, [vp, cstr]),
+    "gtars_txstore_lookup_mane": (i64, [vp, cstr]),
+    "gtars_txstore_lookup_many": (C.c_int, [vp, vp, vp, u64, u32, vp]),
+    "gtars_txstore_record": (C.c_int, [vp, u64, pp, pp, vp, C.POINTER(C.c_int), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
+                                       C.POINTER(u32), pp, pu64]),
+    "gtars_txstore_map": (C.c_int, [vp, vp, vp, vp, vp, vp, u64, u32, vp, vp]),
+    "gtars_txbind_new": (C.c_int, [vp, vp, u32, pp]),
+    "gtars_txbind_free": (None, [vp]),
+    "gtars_txbind_map": (C.c_int, [vp, vp, vp, vp, vp, vp, u64, C.c_int, u32, vp, vp]),
+    "gtars_txbind_sequences": (C.c_int, [vp, vp, u64, C.c_int, u32, vp, vp, pp, pp]),
+    "gtars_tx_map_device": (C.c_int, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+    "gtars_tx_digests_device": (C.c_int, [vp, vp, u64, vp, vp, vp]),
 }
 
 # include/gtars_amd_debug.h: test / A-B / diagnostics hooks, not part of the drop-in boundary

@@ -813,6 +813,87 @@ gtars_status gtars_vrs_results_columns(const gtars_vrs_results_t *r, const uint3
                                        const uint8_t **pool, uint64_t *pool_bytes, const uint32_t **ref_off, const uint32_t **ref_len,
                                        const uint32_t **alt_off, const uint32_t **alt_len, const char **digests);
 
+/* ------------------------------------------------------------------------
+ * Transcripts  (K19; gtars-refget/src/transcripts/{models,builder,store,mapper,sequence}.rs, gtars-python/src/reftx/mod.rs)
+ * ---------------------------------------------------------------------- */
+/* A builder stages transcripts.  Exons are (start, end) pairs of u32, 0-based half-open, in genomic order; a CDS end that
+ * is 0xFFFFFFFF is "none"; strand is +1 or -1; mane_flags: bit 0 MANE Select, bit 1 MANE Plus Clinical.  A chromosome is
+ * named by its refget accession, "SQ." + base64url of 24 bytes ("SQ." optional); anything else is GTARS_ERR_INVALID_ARG
+ * with the text of reftx/mod.rs:282-300.
+ * add_cdot applies the skip rules of builder.rs:146-208 to one cdot transcript: *added = 0 for a contig without a
+ * mapping, a strand that is not +1 / -1 or an empty exon list; MANE flags by full accession, then by base accession.
+ * add_mane records the flags of one accession under its full and its base form (builder.rs:114-125).
+ * bytes: the .reftx v2 image (gtars_free); build: the image written to a temporary file in the destination's directory
+ * and renamed onto `path`; GTARS_ERR_EMPTY "No transcripts to write" for an empty builder; an accession or gene longer
+ * than 255 bytes, or more than 65535 exons, is GTARS_ERR_INVALID_ARG. */
+typedef struct gtars_txbuilder gtars_txbuilder_t;
+gtars_status gtars_txbuilder_new(gtars_txbuilder_t **out);
+void gtars_txbuilder_free(gtars_txbuilder_t *b);
+uint64_t gtars_txbuilder_len(const gtars_txbuilder_t *b);
+gtars_status gtars_txbuilder_add(gtars_txbuilder_t *b, const char *accession, const char *gene, const char *chrom_accession, int strand,
+                                 uint32_t cds_start, uint32_t cds_end, uint32_t mane_flags, const uint32_t *exons, uint64_t n_exons);
+gtars_status gtars_txbuilder_add_chrom_mapping(gtars_txbuilder_t *b, const char *name, const char *chrom_accession);
+gtars_status gtars_txbuilder_add_mane(gtars_txbuilder_t *b, const char *accession, uint32_t flags);
+gtars_status gtars_txbuilder_add_cdot(gtars_txbuilder_t *b, const char *id, const char *gene, const char *contig, int64_t strand,
+                                      uint32_t cds_start, uint32_t cds_end, const uint32_t *exons, uint64_t n_exons, int *added);
+gtars_status gtars_txbuilder_bytes(const gtars_txbuilder_t *b, uint8_t **out, uint64_t *n);
+gtars_status gtars_txbuilder_build(const gtars_txbuilder_t *b, const char *path);
+
+/* A read-only store: the file is read whole and every record decoded when it is opened.  Bad magic, another version, an
+ * index or a record that does not fit the bytes: GTARS_ERR_PARSE, never a read past the buffer.  Transcripts are numbered
+ * in the file's index order.  lookup / lookup_mane (gene, ASCII case-insensitive): the transcript's index, -1: none.
+ * lookup_many: accession i is pool[offsets[i], offsets[i + 1]); idx[i] = its index or 2^32 - 1.
+ * record: borrowed strings and exon pairs, the chromosome digest as 32 characters and a NUL (without "SQ.").
+ * map: the host path of the mapping columns, see gtars_txbind_map. */
+typedef struct gtars_txstore gtars_txstore_t;
+gtars_status gtars_txstore_open(const char *path, gtars_txstore_t **out);
+gtars_status gtars_txstore_from_bytes(const uint8_t *data, uint64_t n, gtars_txstore_t **out);
+void gtars_txstore_free(gtars_txstore_t *s);
+uint64_t gtars_txstore_len(const gtars_txstore_t *s);
+int gtars_txstore_has_mane(const gtars_txstore_t *s);
+int64_t gtars_txstore_lookup(const gtars_txstore_t *s, const char *accession);
+int64_t gtars_txstore_lookup_mane(const gtars_txstore_t *s, const char *gene);
+gtars_status gtars_txstore_lookup_many(const gtars_txstore_t *s, const uint8_t *pool, const uint64_t *offsets, uint64_t n, uint32_t threads,
+                                       uint32_t *idx);
+gtars_status gtars_txstore_record(const gtars_txstore_t *s, uint64_t i, const char **accession, const char **gene, char *chrom33, int *strand,
+                                  uint32_t *mane_flags, uint32_t *cds_start, uint32_t *cds_end, uint32_t *length, uint32_t *cds_length,
+                                  const uint32_t **exons, uint64_t *n_exons);
+gtars_status gtars_txstore_map(const gtars_txstore_t *s, const uint32_t *tx, const uint8_t *kind, const int64_t *pos, const int64_t *offset,
+                               const uint8_t *star, uint64_t n, uint32_t threads, uint64_t *out, uint8_t *status);
+
+/* A store bound to an assembly: every distinct chromosome digest of the store is matched against the assembly's refget
+ * digests.  The store and the assembly must outlive the binding.  The mapping tables go to the assembly's device at the
+ * first device call and stay there.
+ * map: query i is (transcript index tx[i], kind[i] 0 = c. / 1 = n. / 2 = genomic -> mature-mRNA offset, pos[i],
+ * intronic offset[i], star[i] != 0 for c.*N); offset and star may be NULL (all zero).  out[i]: the 0-based genomic
+ * position (kinds 0, 1) or the 0-based transcript offset (kind 2), 0 unless status[i] is 0.  status: 1 transcript not
+ * found, 2 non-coding, 3 outside CDS, 4 outside transcript, 5 / 6 5' / 3' UTR overflow, 7 invalid intronic offset
+ * (mapper.rs:19-50), 8 the genomic position lies in no exon, 9 unknown kind, 10 the transcript's exons are not ascending
+ * and disjoint.  A call never fails for data.
+ * sequences: row i is transcript idx[i]; status 0, 1 not found, 2 the assembly has no chromosome with the transcript's
+ * digest, 3 an exon reaches past the chromosome's end, 4 exons not ascending and disjoint (rows that fail are never read
+ * from the assembly); digests: the 32 characters of sha512t24u of the mature mRNA per row (zero bytes for a failed row;
+ * "SQ." is the caller's); seq_offsets / seq_bytes (both or neither, gtars_free each): the mature mRNAs as a byte CSR --
+ * forward transcripts are the assembly's bytes upper-cased, reverse ones reversed and complemented, any byte outside
+ * ACGTN becoming N (sequence.rs:36-53).
+ * on_host != 0: the library's host path on `threads` threads, no device; otherwise the kernels of csrc/reftx.hip on the
+ * assembly's device (GTARS_ERR_NO_DEVICE without one).
+ * The _device forms take columns and outputs that are device memory (d_digests: n * 32 bytes, 8-byte aligned), queued on
+ * `stream`, which is drained before the call returns.  The current device must be the assembly's: anything else is
+ * refused, as by the other handle-taking device entries. */
+typedef struct gtars_txbind gtars_txbind_t;
+gtars_status gtars_txbind_new(const gtars_txstore_t *s, gtars_assembly_t *a, uint32_t threads, gtars_txbind_t **out);
+void gtars_txbind_free(gtars_txbind_t *b);
+gtars_status gtars_txbind_map(gtars_txbind_t *b, const uint32_t *tx, const uint8_t *kind, const int64_t *pos, const int64_t *offset,
+                              const uint8_t *star, uint64_t n, int on_host, uint32_t threads, uint64_t *out, uint8_t *status);
+gtars_status gtars_txbind_sequences(gtars_txbind_t *b, const uint32_t *idx, uint64_t n, int on_host, uint32_t threads, uint8_t *status,
+                                    char *digests, uint64_t **seq_offsets, uint8_t **seq_bytes);
+gtars_status gtars_tx_map_device(gtars_txbind_t *b, const uint32_t *d_tx, const uint8_t *d_kind, const int64_t *d_pos,
+                                 const int64_t *d_offset, const uint8_t *d_star, uint64_t n, uint64_t *d_out, uint8_t *d_status,
+                                 void *stream);
+gtars_status gtars_tx_digests_device(gtars_txbind_t *b, const uint32_t *d_idx, uint64_t n, uint8_t *d_status, char *d_digests,
+                                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
