@@ -14,7 +14,9 @@ reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats``
 ``gtars.bam`` holds ``BamFile``, ``read_bam_header`` and the BAM QC of ``gtars uniwig bamqc`` (``compute_bam_qc``, ``run_bam_qc``,
 ``write_bam_qc_tsv``).  ``gtars.vrs`` holds the reference's four functions (``vrs_digest``, ``vrs_id``, ``normalize_allele``,
 ``location_digest``) and the batch calls on top of the device kernels (``normalize_alleles``, ``vrs_ids``, ``compute_vrs_ids``);
-its ``hgvs`` sub-module is not provided.  ``gtars.reftx`` holds the reference's transcript classes (``TxStoreBuilder``,
+its ``hgvs`` sub-module (``gtars.vrs.hgvs``, also ``gtars.hgvs``) holds the reference's HGVS parser classes, ``parse_hgvs``,
+``HgvsError`` and ``hgvs_to_vrs_id`` over an assembly and a transcript store, and, additive, the batch bridge on the device
+(``hgvs_to_vrs_ids``); the transcript-anchored bridge is not provided.  ``gtars.reftx`` holds the reference's transcript classes (``TxStoreBuilder``,
 ``ReadonlyTxStore``, ``CoordinateMapper``, ``Transcript``, ``Exon``, ``ManeStatus``, ``Strand``, ``MappingError``, ``TxStoreError``) and, additive,
 the batch mapping calls and the spliced mRNA of every transcript on the device (``mature_mrna``, ``mature_mrnas``,
 ``transcript_accessions``); ``ReftxProvider`` is not provided.
@@ -22,10 +24,12 @@ the batch mapping calls and the spliced mRNA of every transcript on the device (
 import sys as _sys
 
 import gtars_amd as _impl
-from gtars_amd import bam, fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils, vrs, reftx  # noqa: F401
+from gtars_amd import bam, fragsplit, genomic_distributions, igd, lola, models, partitions, scoring, seqstats, signal, tokenizers, utils, vrs, reftx, hgvs  # noqa: F401
 
-for _name in ("bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs", "reftx"):
+for _name in ("bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs", "reftx", "hgvs"):
     _sys.modules[f"{__name__}.{_name}"] = getattr(_sys.modules[__name__], _name)
 
+_sys.modules[f"{__name__}.vrs.hgvs"] = hgvs  # (gtars-python/src/vrs/mod.rs registers the sub-module under vrs)
+
 __version__ = _impl.__version__
-__all__ = ["bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs", "reftx"]
+__all__ = ["bam", "tokenizers", "models", "utils", "lola", "igd", "scoring", "fragsplit", "genomic_distributions", "seqstats", "signal", "partitions", "vrs", "reftx", "hgvs"]

@@ -361,6 +361,12 @@ _HOST_SIG = {
     "gtars_txbind_sequences": (C.c_int, [vp, vp, u64, C.c_int, u32, vp, vp, pp, pp]),
     "gtars_tx_map_device": (C.c_int, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
     "gtars_tx_digests_device": (C.c_int, [vp, vp, u64, vp, vp, vp]),
+    "gtars_hgvs_status_name": (cstr, [u32]),
+    "gtars_hgvs_parse": (C.c_int, [vp, u64, vp, vp, pu64, vp, u64]),
+    "gtars_hgvs_looks_like_gene_symbol": (C.c_int, [cstr]),
+    "gtars_hgvs_resolve": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, u64, u32, vp]),
+    "gtars_hgvs_to_vrs": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, u64, vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "gtars_hgvs_ids_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 # include/gtars_amd_debug.h: test / A-B / diagnostics hooks, not part of the drop-in boundary

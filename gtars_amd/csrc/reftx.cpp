@@ -113,6 +113,11 @@ T *malloc_copy(const T *src, size_t n) {
 
 }  // namespace
 
+namespace gtars {
+TxBindParts tx_bind_parts(gtars_txbind *b) { return TxBindParts{&b->store->data, b->assembly, &b->tables, b->h_seq.data()}; }
+gtars_status tx_bind_device(gtars_txbind *b, Assembly **image, TxDevice **dev) { return device_tables(b, image, dev); }
+}  // namespace gtars
+
 extern "C" {
 
 gtars_status gtars_txbuilder_new(gtars_txbuilder_t **out) {

@@ -15,6 +15,7 @@ namespace gtars {
 struct TxDevice;
 gtars_status tx_device_build(const Assembly &a, const TxHostTables &h, TxDevice **out);
 void tx_device_free(TxDevice *d);
+TxTables tx_device_view(const TxDevice &d);  // the tables as device pointers, for the other kernels that map (hgvs.hip)
 
 // One batch of mapping queries (tx_map_one, reftx_core.h).  The columns and the outputs are device memory of the image's
 // device (on_device) or host memory; off and star may be null (all zero).
@@ -48,5 +49,16 @@ struct TxSeqCall {
     unsigned threads = 1;
 };
 gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &call);
+
+// reftx.cpp, for the host layers on top of a binding (hgvs.cpp): what a gtars_txbind holds, and its device tables (built
+// at the first call that asks)
+struct TxBindParts {
+    const TxStoreData *store;
+    gtars_assembly *assembly;
+    const TxHostTables *tables;      // chrom / seq_status are the binding's
+    const uint8_t *const *h_seq;     // [n_chrom] the chromosomes' bytes
+};
+TxBindParts tx_bind_parts(gtars_txbind *b);
+gtars_status tx_bind_device(gtars_txbind *b, Assembly **image, TxDevice **dev);
 
 }  // namespace gtars

@@ -181,6 +181,7 @@ gtars_status tx_device_build(const Assembly &a, const TxHostTables &h, TxDevice 
 }
 
 void tx_device_free(TxDevice *d) { delete d; }
+TxTables tx_device_view(const TxDevice &d) { return d.view(); }
 
 gtars_status tx_map_run(const Assembly &a, const TxDevice &d, const TxMapCall &call) {
     const AssemblyParts ap = assembly_parts(a);

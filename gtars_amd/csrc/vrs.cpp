@@ -231,6 +231,17 @@ void text33(const char digest[32], char *out33) {
 
 }  // namespace
 
+namespace gtars {
+void vrs_run_on_host(const gtars_assembly *a, const VrsCall &call) {
+    const Columns k{call.chrom, call.start, call.pool, call.pool_bytes, call.ref_off, call.ref_len, call.alt_off, call.alt_len, call.n};
+    alleles_on_host(a, call.accessions, k, call.threads, call.status, call.new_start, call.new_end, call.digest, nullptr);
+}
+gtars_status vrs_accession_table(gtars_assembly *a, const char *given, unsigned threads, std::vector<char> &tab) {
+    return accession_table(a, given, threads, tab);
+}
+gtars_status vrs_check_lengths(const gtars_assembly *a) { return check_lengths(a); }
+}  // namespace gtars
+
 extern "C" {
 
 gtars_status gtars_sha512t24u(const void *data, uint64_t n, char *out33) {

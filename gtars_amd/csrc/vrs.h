@@ -41,4 +41,11 @@ struct VrsCall {
 // (the current device must be the image's), the image's device is selected for host columns
 gtars_status vrs_run(const Assembly &a, const VrsCall &call);
 
+// vrs.cpp, for the host layers on top of K18 (hgvs.cpp): the library's own host path of a batch -- host columns; the call's
+// accessions, threads, status, new_start, new_end and digest are used --, the accession table of a call (the caller's 32
+// characters per chromosome, or the assembly's refget digests), and the length rule every entry applies
+void vrs_run_on_host(const gtars_assembly *a, const VrsCall &call);
+gtars_status vrs_accession_table(gtars_assembly *a, const char *given, unsigned threads, std::vector<char> &tab);
+gtars_status vrs_check_lengths(const gtars_assembly *a);
+
 }  // namespace gtars

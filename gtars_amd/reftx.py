@@ -12,7 +12,7 @@ DESIGN.md section 3, K19): one lane per query, one lane per transcript digest, e
 sequences.  ``on_host=True`` runs the library's own host path on its host threads instead: the same results, no device.
 Without a device the default calls raise NoDeviceError; there is no silent fallback.
 
-``ReftxProvider`` and everything HGVS are not part of this module.
+``ReftxProvider`` is not part of this module.  HGVS expressions over a store are ``gtars_amd.hgvs`` (``gtars.vrs.hgvs``).
 """
 from __future__ import annotations
 

@@ -8,8 +8,9 @@ against the chromosome and computes the two SHA-512 digests.  ``on_host=True`` r
 host threads instead: the same results, no device.  Without a device the default calls raise NoDeviceError; there is no
 silent fallback.
 
-Only literal sequence states are computed.  The HGVS parser and bridge, ``ReferenceLengthExpression`` states,
-transcripts, the refget store and sequence collections are not part of this module.
+Only literal sequence states are computed.  ``ReferenceLengthExpression`` states, the refget store and sequence
+collections are not part of this module.  The HGVS parser and the HGVS-to-VRS bridge are ``gtars_amd.hgvs``, which is
+reachable from here as ``vrs.hgvs`` (``gtars.vrs.hgvs``), as in the reference; transcripts are ``gtars_amd.reftx``.
 """
 from __future__ import annotations
 
@@ -242,3 +243,12 @@ def compute_vrs_ids(vcf_path, genome, accessions: Optional[Dict[str, str]] = Non
     check(lib.gtars_vrs_from_vcf(_genome_handle(genome), os.fspath(vcf_path).encode("utf-8"), _accession_table(genome, accessions),
                                  1 if on_host else 0, int(threads), C.byref(r)))
     return _take_results(genome, r)
+
+
+# gtars.vrs.hgvs: the reference keeps the HGVS module under vrs and registers it in sys.modules (gtars-python/src/vrs/mod.rs);
+# this file stays a single module, so the sub-module is registered by hand
+import sys as _sys  # noqa: E402
+
+from . import hgvs  # noqa: E402,F401
+
+_sys.modules[__name__ + ".hgvs"] = hgvs

@@ -894,6 +894,78 @@ gtars_status gtars_tx_map_device(gtars_txbind_t *b, const uint32_t *d_tx, const 
 gtars_status gtars_tx_digests_device(gtars_txbind_t *b, const uint32_t *d_idx, uint64_t n, uint8_t *d_status, char *d_digests,
                                      void *stream);
 
+/* ------------------------------------------------------------------------
+ * HGVS expressions  (K20; gtars-vrs/src/hgvs/{ast,parser,bridge}.rs, gtars-python/src/vrs/hgvs.rs)
+ * ---------------------------------------------------------------------- */
+/* One parsed expression.  Accession, gene, ref and alt are (offset, length) spans into the text that was parsed; nothing is
+ * copied.  ref_type: 0 g, 1 c, 2 n, 3 m, 4 r, 5 p.  loc: 0 single, 1 range, 2 whole sequence, 3 / 4 / 5 a range whose
+ * start / end / both are uncertain.  pos[0]: the start or its low bound, pos[1]: the start's high bound, pos[2]: the end or
+ * its low bound, pos[3]: the end's high bound; present = 0 for a position the kind does not have and for "?"; datum: 0
+ * sequence start, 1 CDS start, 2 CDS end (c.*N).  edit: 0 substitution, 1 deletion, 2 duplication, 3 insertion, 4 delins,
+ * 5 inversion, 6 identity, 7 unknown, 8 copy (count), 9 repeat (its unit in the ref span, count).  flags: bit 0 a gene in
+ * parentheses, bit 1 a reference allele, bit 2 uncertain. */
+typedef struct gtars_hgvs_position {
+    int64_t base, offset;
+    uint8_t datum, present;
+    uint8_t reserved[6];
+} gtars_hgvs_position;
+typedef struct gtars_hgvs_row {
+    uint32_t acc_off, acc_len, gene_off, gene_len, ref_off, ref_len, alt_off, alt_len;
+    gtars_hgvs_position pos[4];
+    uint32_t count;
+    uint8_t ref_type, loc, edit, flags;
+} gtars_hgvs_row;
+/* Parsed rows as columns of n entries, host or device memory.  pre: 0, or the status parsing and the accession lookup
+ * left; kind / loc / edit as in a row; flags: bit 1 a reference allele, bit 2 uncertain, bit 3 / bit 4 the first / second
+ * position is c.*N; tx: the transcript's index in the store for c. and n., the chromosome id of the assembly for g.
+ * (2^32 - 1: unknown); base1 / off1: the single position or the range's start, base2 / off2: the range's end; the alleles
+ * of row i are text[text_off[i] + ref_off[i], + ref_len[i]) and text[text_off[i] + alt_off[i], + alt_len[i]). */
+typedef struct gtars_hgvs_columns {
+    uint8_t *pre, *kind, *loc, *edit, *flags;
+    uint32_t *tx;
+    int64_t *base1, *off1, *base2, *off2;
+    uint64_t *text_off;
+    uint32_t *ref_off, *ref_len, *alt_off, *alt_len;
+    const uint8_t *text;
+    uint64_t text_bytes;
+    uint64_t n;
+} gtars_hgvs_columns;
+
+/* Row statuses: 0 ok, 1 parse error, 2 unsupported reference type (m. r. p.), 3 unsupported edit (inv, unknown, copy,
+ * repeat, whole-sequence, uncertain position range), 4 transcript not found, 5 no MANE transcript, 6 unknown chromosome,
+ * 7 mapping error (detail: the status of gtars_txbind_map), 8 out of bounds, 9 inconsistent edit, 10 ref mismatch,
+ * 11 normalize error (detail: the status of gtars_vrs_alleles).  status_name: NULL past the last one.
+ * parse: the nucleotide grammar of parser.rs over text[0, len); *status 0, 1 (then *err_pos is the byte position and
+ * err_text, of err_cap bytes, the message of the error) or 2 for a protein expression, whose positions and edit are not
+ * parsed.  looks_like_gene_symbol: bridge.rs:552-589. */
+const char *gtars_hgvs_status_name(uint32_t status);
+gtars_status gtars_hgvs_parse(const char *text, uint64_t len, gtars_hgvs_row *row, uint8_t *status, uint64_t *err_pos, char *err_text,
+                              uint64_t err_cap);
+int gtars_hgvs_looks_like_gene_symbol(const char *accession);
+/* The batch calls on a bound store.  Expression i is text[offsets[i], offsets[i + 1]).  The strings are parsed and their
+ * accessions looked up on `threads` host threads (0 = gtars_host_threads): a gene symbol through the store's MANE index,
+ * the accession of a c. / n. expression through the store's index, the accession of a g. expression as a chromosome name
+ * of the assembly or as alias i = alias_pool[alias_offsets[i], alias_offsets[i + 1]) for chromosome id alias_chrom[i]
+ * (n_alias may be 0).  resolve stops there and fills the caller's columns (out->text, text_bytes and n are set by it).
+ * to_vrs goes on: the span of every row, REF read from the assembly and ALT made from the text, then normalization and the
+ * digests of K18.  accessions as for gtars_vrs_alleles.  Outputs of n entries, any may be NULL: status, detail, warnings
+ * (bit 0: uncertain expression), the chromosome id (2^32 - 1 for a row that failed), the normalized interval and the 32
+ * characters of the Allele digest (zero bytes for a row that failed).  A call never fails for data.
+ * on_host != 0: the library's host path, no device; otherwise the kernels of csrc/hgvs.hip and csrc/vrs.hip on the
+ * assembly's device (GTARS_ERR_NO_DEVICE without one).
+ * ids_device: the same from resolved columns, text and outputs that are device memory (d_digests: n * 32 bytes, 8-byte
+ * aligned), queued on `stream`, which is drained before the call returns.  The current device must be the assembly's. */
+gtars_status gtars_hgvs_resolve(gtars_txbind_t *b, const uint8_t *text, const uint64_t *offsets, uint64_t n, const uint8_t *alias_pool,
+                                const uint64_t *alias_offsets, const uint32_t *alias_chrom, uint64_t n_alias, uint32_t threads,
+                                gtars_hgvs_columns *out);
+gtars_status gtars_hgvs_to_vrs(gtars_txbind_t *b, const uint8_t *text, const uint64_t *offsets, uint64_t n, const uint8_t *alias_pool,
+                               const uint64_t *alias_offsets, const uint32_t *alias_chrom, uint64_t n_alias, const char *accessions,
+                               int on_host, uint32_t threads, uint8_t *status, uint8_t *detail, uint8_t *warnings, uint32_t *chrom,
+                               uint64_t *start, uint64_t *end, char *digests);
+gtars_status gtars_hgvs_ids_device(gtars_txbind_t *b, const gtars_hgvs_columns *d_cols, const char *accessions, uint8_t *d_status,
+                                   uint8_t *d_detail, uint8_t *d_warnings, uint32_t *d_chrom, uint64_t *d_start, uint64_t *d_end,
+                                   char *d_digests, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
