@@ -247,7 +247,7 @@ void prof_note_fact(const char *name) {
 //    back afterwards:   GT_ON_DEVICE_OF(h);
 //  * `*_device` entry points take the CALLER's device pointers and stream, which belong to the caller's current device: a handle
 //    that lives elsewhere is an argument error, not a memory fault:   GT_SAME_DEVICE_AS(h);
-static gtars_status require_handle_device(int handle_device) {
+gtars_status require_handle_device(int handle_device) {
     int cur = -1;
     hipError_t e = hipGetDevice(&cur);
     if (e != hipSuccess) return hip_fail(e, "query the current device", __FILE__, __LINE__);

@@ -17,12 +17,11 @@
 
 #include "../../include/gtars_amd_host.h"
 #include "assembly.h"
+#include "guard.h"
 #include "seqstats.h"
 
-namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
-}
 using gtars::fail;
+using gtars::guarded;
 
 // the handle's device image, built at the first call on the device current then
 gtars_status gtars::assembly_device_image(gtars_assembly *a, gtars::Assembly **out) {
@@ -39,17 +38,6 @@ gtars_status gtars::assembly_device_image(gtars_assembly *a, gtars::Assembly **o
 namespace {
 
 using gtars::assembly_device_image;
-
-template <class F>
-gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
 
 inline bool is_ws(char ch) { return ch == ' ' || (ch >= '\t' && ch <= '\r'); }
 

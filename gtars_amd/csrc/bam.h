@@ -8,10 +8,9 @@
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
+#include "guard.h"
 
 namespace gtars {
-
-gtars_status fail(gtars_status st, const std::string &msg);
 
 constexpr uint32_t BGZF_MAX_ISIZE = 65536;
 

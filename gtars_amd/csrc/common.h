@@ -12,6 +12,7 @@
 
 #include "../../include/gtars_amd.h"
 #include "frag_device.h"
+#include "guard.h"
 
 namespace gtars {
 
@@ -23,7 +24,6 @@ using i64 = int64_t;
 
 // ---- error plumbing --------------------------------------------------------
 void set_error(const std::string &msg);
-gtars_status fail(gtars_status st, const std::string &msg);
 gtars_status hip_fail(hipError_t e, const char *what, const char *file, int line);
 
 #define GT_HIP(expr)                                                            \
@@ -40,18 +40,9 @@ gtars_status hip_fail(hipError_t e, const char *what, const char *file, int line
     } while (0)
 
 gtars_status require_device();
-
-// runs f(), turning C++ exceptions into a status (nothing may unwind through the extern "C" boundary)
-template <class F>
-inline gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
+// GTARS_OK when the calling thread's current device is `handle_device`; INVALID_ARG otherwise: a `*_device` entry point takes
+// the CALLER's device pointers and stream, and a handle that lives elsewhere is an argument error, not a memory fault
+gtars_status require_handle_device(int handle_device);
 
 // the calling thread's current device for the scope: `want`, and what it was before again afterwards
 struct DeviceScope {

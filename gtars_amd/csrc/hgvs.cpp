@@ -9,6 +9,7 @@
 
 #include "../../include/gtars_amd_host.h"
 #include "assembly.h"
+#include "guard.h"
 #include "hgvs.h"
 #include "hgvs_core.h"
 #include "host_threads.h"
@@ -16,26 +17,15 @@
 #include "vrs_core.h"
 
 namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
 unsigned host_threads_for(unsigned cap);
 }  // namespace gtars
 using gtars::fail;
+using gtars::guarded;
 
 static_assert(sizeof(gtars_hgvs_row) == sizeof(gtars::HgvsRow) && sizeof(gtars_hgvs_position) == sizeof(gtars::HgvsPosition),
               "the row of the C ABI is the parser's");
 
 namespace {
-
-template <class F>
-gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
 
 unsigned threads_of(uint32_t threads) {
     const unsigned most = gtars::host_threads_for(0xFFFFFFFFu);

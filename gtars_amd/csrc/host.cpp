@@ -39,23 +39,11 @@
 #include "annot.h"
 #include "uniwig.h"
 #include "tokbatch.h"
+#include "guard.h"
 #include "host_threads.h"
 
 namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
 const char *cfg_get(const char *name);  // snapshot of the GTARS_* environment (common.h)
-
-// runs f(), turning C++ exceptions into a status (nothing may unwind through the extern "C" boundary)
-template <class F>
-static gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
 }
 using gtars::cfg_get;
 using gtars::fail;

@@ -26,13 +26,14 @@
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
+#include "guard.h"
 #include "host_threads.h"
 
 namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
 const char *cfg_get(const char *name);
 }
 extern "C" uint32_t gtars_host_threads(uint32_t cap);
+using gtars::guarded;
 
 namespace {
 
@@ -268,17 +269,6 @@ void bh_rows(const double *p_value_log, std::vector<uint64_t> &idx, double *q_va
     for (size_t i = n - 1; i-- > 0;) {
         q = std::min(std::min(p[i] * (double)n / (double)(i + 1), q), 1.0);
         q_value[idx[i]] = q;
-    }
-}
-
-template <class F>
-gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return gtars::fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return gtars::fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
     }
 }
 

@@ -10,12 +10,11 @@
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
+#include "guard.h"
 #include "partitions.h"
 
-namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
-}
 using gtars::fail;
+using gtars::guarded;
 
 struct gtars_partition_list {
     struct Part {
@@ -31,17 +30,6 @@ struct gtars_partition_list {
 };
 
 namespace {
-
-template <class F>
-gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
 
 // the handle's device index, built at the first count on the device current then
 gtars_status device_index(gtars_partition_list *pl, gtars::PartDevice **out) {

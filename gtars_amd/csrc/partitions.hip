@@ -260,11 +260,7 @@ gtars_status part_count_device(const PartDevice *d, const uint32_t *d_chrom, con
     std::fill(out, out + d->n_part + 1, 0);
     if (!n) return GTARS_OK;
     if (!d_chrom || !d_start || !d_end) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    int cur = -1;
-    GT_HIP(hipGetDevice(&cur));
-    if (cur != d->device)
-        return fail(GTARS_ERR_INVALID_ARG, "handle lives on device " + std::to_string(d->device) + ", current device is " +
-                                               std::to_string(cur) + ": device pointers and stream must belong to the handle's device");
+    GT_TRY(require_handle_device(d->device));
     StreamFrame fr((hipStream_t)stream);
     GT_TRY(count_on(fr, *d, d_chrom, d_start, d_end, n, nullptr, 0, bp, out, d_assign));
     return fr.drain();

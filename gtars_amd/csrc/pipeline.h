@@ -1,5 +1,7 @@
-// pipeline.h -- the steps the region-set pipelines (setops.hip, annot.hip, uniwig.hip) share.  The host-side ones queue
-// their work on a StreamFrame's stream and leave what they allocate with the frame.
+// pipeline.h -- the steps the device pipelines share: the region-set ones (setops.hip, annot.hip, uniwig.hip) and the ones
+// over the packed genome image (seqstats.hip, vrs.hip, reftx.hip, hgvs.hip; their call frame is image_call.h, their
+// byte-CSR fill byte_csr.h).  The host-side steps queue their work on a StreamFrame's stream and leave what they allocate
+// with the frame.
 #pragma once
 
 #include "common.h"
@@ -12,6 +14,7 @@ inline unsigned grid_for(u64 n, u32 per = 256, u32 cap = 1u << 16) {
 }
 
 // first position p in [lo, hi) with x[p] >= key (first_gt: > key), hi if none; x ascends.  P: any indexable, global or LDS
+// (their sibling last_le -- the row of an element in a scanned offset table -- is in byte_csr.h: host programs compile it too)
 template <class P>
 __device__ __forceinline__ u32 first_ge(P x, u32 lo, u32 hi, u32 key) {
     while (lo < hi) {

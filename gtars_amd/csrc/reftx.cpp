@@ -18,15 +18,16 @@
 
 #include "../../include/gtars_amd_host.h"
 #include "assembly.h"
+#include "guard.h"
 #include "host_threads.h"
 #include "reftx.h"
 #include "reftx_core.h"
 
 namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
 unsigned host_threads_for(unsigned cap);
 }  // namespace gtars
 using gtars::fail;
+using gtars::guarded;
 
 struct gtars_txbuilder {
     std::vector<gtars::TxRecord> recs;
@@ -50,17 +51,6 @@ struct gtars_txbind {
 };
 
 namespace {
-
-template <class F>
-gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
 
 unsigned threads_of(uint32_t threads) {
     const unsigned most = gtars::host_threads_for(0xFFFFFFFFu);

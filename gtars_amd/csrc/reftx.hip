@@ -6,8 +6,9 @@
 //   * k_tx_map, one lane per query: tx_map_one of reftx_core.h, the same text the host path runs.  The exon of a position is
 //     found by binary search of the transcript's slice; the reference scans the exons, and the answers are the same because
 //     the exons of a transcript the tables accept are ascending and disjoint.
-//   * k_tx_rows + the scan of kernels.hip + k_tx_fill: the mature sequences as a byte CSR, eight output bytes per lane; a
-//     lane finds its row and its exon by search and walks across exon and row ends.
+//   * k_tx_rows + the scan of kernels.hip + the fill of byte_csr.h over TxRowSrc (profiled as k_tx_fill): the mature
+//     sequences as a byte CSR, eight output bytes per lane; a lane finds its row and its exon by search and walks across
+//     exon and row ends.
 //   * k_tx_digest, one lane per transcript: sha512t24u of the mature sequence through sha512_stream (sha512.h) from a source
 //     that walks the exons forward, or backward with the complement.  Nothing is staged in memory.  Lanes take the rows in
 //     ascending order of their lengths (sort_perm), so the 64 transcripts of a wave need about the same number of blocks.
@@ -15,8 +16,10 @@
 //     header on the host threads and writes the results into the device column.
 #include <cstring>
 
+#include "byte_csr.h"
 #include "common.h"
 #include "host_threads.h"
+#include "image_call.h"
 #include "pipeline.h"
 #include "reftx.h"
 #include "sha512.h"
@@ -93,67 +96,34 @@ k_tx_digest(TxTables t, const u8 *__restrict__ seq, const u64 *__restrict__ coff
     }
 }
 
-__global__ void __launch_bounds__(TX_TPB)
-k_tx_fill(TxTables t, const u8 *__restrict__ seq, const u64 *__restrict__ coff, const u32 *__restrict__ idx, u32 n,
-          const u64 *__restrict__ off, u64 total, u8 *__restrict__ out) {
-    const u64 groups = (total + 7) >> 3;
-    for (u64 g = (u64)blockIdx.x * TX_TPB + threadIdx.x; g < groups; g += (u64)gridDim.x * TX_TPB) {
-        const u64 q0 = g << 3;
-        const u64 q_end = min(q0 + 8, total);
-        // the row of byte q0: the last r with off[r] <= q0 whose sequence is not empty
-        u32 lo = 0, hi = n;
-        while (hi - lo > 1) {
-            const u32 m = lo + ((hi - lo) >> 1);
-            if (off[m] <= q0) lo = m;
-            else hi = m;
-        }
-        u32 r = lo, k = 0;
-        bool new_row = true;
-        TxExons x{};
-        const u8 *chrom_seq = nullptr;
-        u64 ts = 0, te = 0, word = 0;
-        for (u64 q = q0; q < q_end; ++q) {
-            while (off[r + 1] <= q) ++r, new_row = true;  // (q < total = off[n]: stops inside the table)
-            const u64 p = q - off[r];
-            if (new_row || p >= te) {
-                if (new_row) {
-                    const u32 tx = idx[r];  // (a row with bytes has status 0: the index and its chromosome are valid)
-                    x = tx_exons(t, tx);
-                    chrom_seq = seq + coff[t.chrom[tx]];
-                    new_row = false;
-                }
-                k = x.at(tx_exon_of(x, p));
-                ts = x.ts[k], te = ts + (x.ge[k] - x.gs[k]);
-            }
-            word |= (u64)tx_base(x, chrom_seq, k, p - ts) << (8 * (q - q0));
-        }
-        if (q_end - q0 == 8) *(u64 *)(out + q0) = word;  // (out comes from the allocator and q0 is a multiple of 8)
-        else
-            for (u64 q = q0; q < q_end; ++q) out[q] = (u8)(word >> (8 * (q - q0)));
+// a row of the CSR: a transcript's mature sequence, read through an exon cursor that moves when k passes the exon's end
+struct TxRowSrc {
+    TxTables t;
+    const u8 *seq;
+    const u64 *coff;
+    const u32 *idx;
+    TxExons x;  // of the open row
+    const u8 *chrom_seq;
+    u32 k;       // the exon that holds transcript positions [ts, te)
+    u64 ts, te;
+    __device__ __forceinline__ void open(u32 r) {
+        const u32 tx = idx[r];  // (a row with bytes has status 0: the index and its chromosome are valid)
+        x = tx_exons(t, tx);
+        chrom_seq = seq + coff[t.chrom[tx]];
+        ts = te = 0;  // (no exon yet: the first byte searches)
     }
-}
-
-template <class T>
-gtars_status bring(StreamFrame &fr, bool on_device, const T *src, size_t n, const T **out) {
-    if (on_device || !src) {
-        *out = src;
-        return GTARS_OK;
+    __device__ __forceinline__ u32 byte(u64 p) {
+        if (p >= te) {
+            k = x.at(tx_exon_of(x, p));
+            ts = x.ts[k], te = ts + (x.ge[k] - x.gs[k]);
+        }
+        return tx_base(x, chrom_seq, k, p - ts);
     }
-    T *d;
-    GT_TRY(fr.upload(&d, src, n));
-    *out = d;
-    return GTARS_OK;
-}
+};
 
 gtars_status check_device(const AssemblyParts &ap, bool on_device) {
     if (ap.device < 0) return fail(GTARS_ERR_INTERNAL, "reftx: the assembly has no device image");
-    if (!on_device) return GTARS_OK;
-    int cur = -1;
-    GT_HIP(hipGetDevice(&cur));
-    if (cur != ap.device)
-        return fail(GTARS_ERR_INVALID_ARG, "handle lives on device " + std::to_string(ap.device) + ", current device is " + std::to_string(cur) +
-                                               ": device pointers and stream must belong to the handle's device");
-    return GTARS_OK;
+    return on_device ? require_handle_device(ap.device) : GTARS_OK;
 }
 
 }  // namespace
@@ -189,34 +159,30 @@ gtars_status tx_map_run(const Assembly &a, const TxDevice &d, const TxMapCall &c
     if (call.n > TX_MAX_N) return fail(GTARS_ERR_INVALID_ARG, "reftx: too many queries (" + std::to_string(call.n) + ")");
     if (!call.n) return GTARS_OK;
     if (!call.tx || !call.kind || !call.pos || !call.out || !call.status) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    DeviceScope on(call.on_device ? -1 : ap.device);
-    GT_TRY(on.st);
-    StreamFrame fr(call.on_device ? (hipStream_t)call.stream : nullptr);
+    ImageCall ic(ap, call.on_device, call.stream);
+    GT_TRY(ic.scope.st);
+    StreamFrame &fr = ic.fr;
     const size_t n = (size_t)call.n;
     const u32 *tx;
     const u8 *kind, *star;
     const i64 *pos, *off;
-    GT_TRY(bring(fr, call.on_device, call.tx, n, &tx));
-    GT_TRY(bring(fr, call.on_device, call.kind, n, &kind));
-    GT_TRY(bring(fr, call.on_device, call.pos, n, &pos));
-    GT_TRY(bring(fr, call.on_device, call.off, n, &off));
-    GT_TRY(bring(fr, call.on_device, call.star, n, &star));
-    u64 *out = call.out;
-    u8 *status = call.status;
-    if (!call.on_device) {
-        GT_TRY(fr.alloc(&out, n));
-        GT_TRY(fr.alloc(&status, n));
-    }
+    GT_TRY(ic.in(call.tx, n, &tx));
+    GT_TRY(ic.in(call.kind, n, &kind));
+    GT_TRY(ic.in(call.pos, n, &pos));
+    GT_TRY(ic.in(call.off, n, &off));
+    GT_TRY(ic.in(call.star, n, &star));
+    u64 *out;
+    u8 *status;
+    GT_TRY(ic.out(call.out, n, &out));
+    GT_TRY(ic.out(call.status, n, &status));
     {
         ProfScope ps("k_tx_map", fr.st);
         hipLaunchKernelGGL(k_tx_map, dim3(grid_for(n, TX_TPB, TX_MAX_BLOCKS)), dim3(TX_TPB), 0, fr.st, d.view(), tx, kind, pos, off, star, (u64)n,
                            out, status);
         GT_HIP(hipGetLastError());
     }
-    if (!call.on_device) {
-        GT_TRY(fr.download(call.out, out, n));
-        GT_TRY(fr.download(call.status, status, n));
-    }
+    GT_TRY(ic.back(call.out, out, n));
+    GT_TRY(ic.back(call.status, status, n));
     return fr.drain();
 }
 
@@ -228,11 +194,10 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
     if (call.seq_off) call.seq_off->assign(1, 0), call.seq_bytes->clear();
     if (!call.n) return GTARS_OK;
     if (!call.idx) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    if (call.on_device && call.digest && ((uintptr_t)call.digest & 7))
-        return fail(GTARS_ERR_INVALID_ARG, "reftx: the device digests must be 8-byte aligned");
-    DeviceScope on(call.on_device ? -1 : ap.device);
-    GT_TRY(on.st);
-    StreamFrame fr(call.on_device ? (hipStream_t)call.stream : nullptr);
+    GT_TRY(digests_aligned("reftx", call.on_device, call.digest));
+    ImageCall ic(ap, call.on_device, call.stream);
+    GT_TRY(ic.scope.st);
+    StreamFrame &fr = ic.fr;
     hipStream_t st = fr.st;
     const size_t n = (size_t)call.n;
     // (a negative or unreadable value is the default; 2^30 bounds the u32 the kernel compares with)
@@ -240,11 +205,10 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
     const u32 host_len = (u32)std::min(host_len_cfg < 0 ? 65536l : host_len_cfg, 0x40000000l);
     const TxTables t = d.view();
     const u32 *idx;
-    GT_TRY(bring(fr, call.on_device, call.idx, n, &idx));
+    GT_TRY(ic.in(call.idx, n, &idx));
     u8 *status;
     u32 *cnt;
-    if (call.on_device && call.status) status = call.status;
-    else GT_TRY(fr.alloc(&status, n));
+    GT_TRY(ic.out(call.status, n, &status));
     GT_TRY(fr.alloc(&cnt, n));
     const unsigned grid = grid_for(n, TX_TPB, TX_MAX_BLOCKS);
     {
@@ -254,8 +218,7 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
     }
     if (call.digest) {
         u64 *d_digest;
-        if (call.on_device) d_digest = (u64 *)call.digest;
-        else GT_TRY(fr.alloc(&d_digest, 4 * n));
+        GT_TRY(ic.digests_out(call.digest, n, &d_digest));
         u32 *perm, *host_list, *n_host;
         GT_TRY(sort_perm(fr, nullptr, cnt, nullptr, (u32)n, 1, &perm));
         GT_TRY(fr.alloc(&host_list, n));
@@ -267,8 +230,8 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
                                host_list, n_host);
             GT_HIP(hipGetLastError());
         }
-        u32 *h_n = (u32 *)fr.host(sizeof(u32));
-        if (!h_n) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+        u32 *h_n;
+        GT_TRY(ic.host_word(&h_n));
         GT_TRY(fr.download(h_n, n_host, 1));
         GT_TRY(fr.drain());
         if (const u32 n_list = *h_n) {
@@ -285,7 +248,7 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
             for (u32 k = 0; k < n_list; ++k) GT_TRY(fr.upload_to((char *)(d_digest + 4 * (size_t)rows[k]), &text[(size_t)k * 32], 32));
             GT_TRY(fr.drain());
         }
-        if (!call.on_device) GT_TRY(fr.download(call.digest, (const char *)d_digest, 32 * n));
+        GT_TRY(ic.digests_back(call.digest, d_digest, n));
     }
     if (call.seq_off) {
         u64 *off, total = 0;
@@ -295,16 +258,11 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
         if (total) {
             u8 *d_bytes;
             GT_TRY(fr.alloc(&d_bytes, (size_t)total));
-            {
-                ProfScope ps("k_tx_fill", st);
-                hipLaunchKernelGGL(k_tx_fill, dim3(grid_for((total + 7) >> 3, TX_TPB, TX_MAX_BLOCKS)), dim3(TX_TPB), 0, st, t, ap.seq, ap.off,
-                                   idx, (u32)n, off, total, d_bytes);
-                GT_HIP(hipGetLastError());
-            }
+            GT_TRY(csr_fill("k_tx_fill", TxRowSrc{t, ap.seq, ap.off, idx}, off, (u32)n, total, d_bytes, st));
             GT_TRY(fr.download(call.seq_bytes->data(), d_bytes, (size_t)total));
         }
     }
-    if (!(call.on_device && call.status) && call.status) GT_TRY(fr.download(call.status, status, n));
+    GT_TRY(ic.back(call.status, status, n));
     return fr.drain();
 }
 

@@ -24,7 +24,9 @@
 #include <cstring>
 #include <memory>
 
+#include "byte_csr.h"
 #include "common.h"
+#include "image_call.h"
 #include "pipeline.h"
 #include "seqstats.h"
 
@@ -101,15 +103,7 @@ __device__ __forceinline__ u32 group_sum(u32 v) {
 }
 
 // first r in [0, n) with off[r + 1] > p (p < off[n])
-__device__ __forceinline__ u32 row_of_piece(const u64 *__restrict__ off, u32 n, u64 p) {
-    u32 lo = 0, hi = n;  // the answer is in [lo, hi)
-    while (hi - lo > 1) {
-        const u32 m = lo + ((hi - lo) >> 1);
-        if (off[m] <= p) lo = m;
-        else hi = m;
-    }
-    return lo;
-}
+__device__ __forceinline__ u32 row_of_piece(const u64 *__restrict__ off, u32 n, u64 p) { return last_le(off, n, p); }
 
 template <int LANES, bool DINUCL>
 __global__ void __launch_bounds__(SEQ_TPB)
@@ -211,11 +205,12 @@ gtars_status launch_count(const Assembly &a, const u32 *chrom, const u32 *start,
 }
 
 // the columns are on the device, the frame's stream is the caller's
-gtars_status counts_on(StreamFrame &fr, const Assembly &a, const u32 *d_chrom, const u32 *d_start, const u32 *d_end, u64 n, int mode,
+gtars_status counts_on(ImageCall &ic, const Assembly &a, const u32 *d_chrom, const u32 *d_start, const u32 *d_end, u64 n, int mode,
                        u32 *d_out) {
+    StreamFrame &fr = ic.fr;
     hipStream_t st = fr.st;
-    u32 *cnt, *bad, *h_bad = (u32 *)fr.host(sizeof(u32));
-    if (!h_bad) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    u32 *cnt, *bad, *h_bad;
+    GT_TRY(ic.host_word(&h_bad));
     GT_TRY(fr.alloc(&cnt, (size_t)n));
     GT_TRY(fr.alloc(&bad, 1));
     GT_HIP(hipMemsetAsync(bad, 0, sizeof(u32), st));
@@ -247,6 +242,31 @@ gtars_status check_call(const Assembly &a, u64 n, int mode) {
     if (n > SEQ_MAX_N) return fail(GTARS_ERR_INVALID_ARG, "seqstats: too many rows (" + std::to_string(n) + ")");
     if (a.device < 0) return fail(GTARS_ERR_INTERNAL, "seqstats: the assembly has no device image");
     return GTARS_OK;
+}
+
+// both entries: the caller's device columns and stream, or host columns on the image's device
+gtars_status counts_call(const Assembly &a, bool on_device, const u32 *chrom, const u32 *start, const u32 *end, u64 n, int mode, u32 *out,
+                         void *stream) {
+    GT_TRY(check_call(a, n, mode));
+    if (!n) return GTARS_OK;
+    if (!chrom || !start || !end || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+    if (on_device) {
+        if (mode == GTARS_SEQ_DINUCL && ((uintptr_t)out & 15))
+            return fail(GTARS_ERR_INVALID_ARG, "seqstats: the device counts must be 16-byte aligned");
+        GT_TRY(require_handle_device(a.device));
+    }
+    ImageCall ic(assembly_parts(a), on_device, stream);
+    GT_TRY(ic.scope.st);
+    const size_t cells = (size_t)n * (mode == GTARS_SEQ_GC ? 1 : 16);
+    const u32 *d_chrom, *d_start, *d_end;
+    u32 *d_out;
+    GT_TRY(ic.in(chrom, (size_t)n, &d_chrom));
+    GT_TRY(ic.in(start, (size_t)n, &d_start));
+    GT_TRY(ic.in(end, (size_t)n, &d_end));
+    GT_TRY(ic.out(out, cells, &d_out));
+    GT_TRY(counts_on(ic, a, d_chrom, d_start, d_end, n, mode, d_out));
+    GT_TRY(ic.back(out, d_out, cells));
+    return ic.fr.drain();
 }
 
 }  // namespace
@@ -325,38 +345,12 @@ int assembly_set_device(Assembly *a, int device) {
 
 gtars_status seqstats_counts_device(const Assembly &a, const uint32_t *d_chrom, const uint32_t *d_start, const uint32_t *d_end,
                                     uint64_t n, int mode, uint32_t *d_out, void *stream) {
-    GT_TRY(check_call(a, n, mode));
-    if (!n) return GTARS_OK;
-    if (!d_chrom || !d_start || !d_end || !d_out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    if (mode == GTARS_SEQ_DINUCL && ((uintptr_t)d_out & 15))
-        return fail(GTARS_ERR_INVALID_ARG, "seqstats: the device counts must be 16-byte aligned");
-    int cur = -1;
-    GT_HIP(hipGetDevice(&cur));
-    if (cur != a.device)
-        return fail(GTARS_ERR_INVALID_ARG, "handle lives on device " + std::to_string(a.device) + ", current device is " +
-                                               std::to_string(cur) + ": device pointers and stream must belong to the handle's device");
-    StreamFrame fr((hipStream_t)stream);
-    GT_TRY(counts_on(fr, a, d_chrom, d_start, d_end, n, mode, d_out));
-    return fr.drain();
+    return counts_call(a, true, d_chrom, d_start, d_end, n, mode, d_out, stream);
 }
 
 gtars_status seqstats_counts(const Assembly &a, const uint32_t *chrom, const uint32_t *start, const uint32_t *end, uint64_t n,
                              int mode, uint32_t *out) {
-    GT_TRY(check_call(a, n, mode));
-    if (!n) return GTARS_OK;
-    if (!chrom || !start || !end || !out) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    DeviceScope on(a.device);
-    GT_TRY(on.st);
-    StreamFrame fr(nullptr);
-    const size_t cols = mode == GTARS_SEQ_GC ? 1 : 16;
-    u32 *d_chrom, *d_start, *d_end, *d_out;
-    GT_TRY(fr.upload(&d_chrom, chrom, (size_t)n));
-    GT_TRY(fr.upload(&d_start, start, (size_t)n));
-    GT_TRY(fr.upload(&d_end, end, (size_t)n));
-    GT_TRY(fr.alloc(&d_out, (size_t)n * cols));
-    GT_TRY(counts_on(fr, a, d_chrom, d_start, d_end, n, mode, d_out));
-    GT_TRY(fr.download(out, d_out, (size_t)n * cols));
-    return fr.drain();
+    return counts_call(a, false, chrom, start, end, n, mode, out, nullptr);
 }
 
 }  // namespace gtars

@@ -16,12 +16,11 @@
 
 #include "../../include/gtars_amd_debug.h"
 #include "../../include/gtars_amd_host.h"
+#include "guard.h"
 #include "signal.h"
 
-namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
-}
 using gtars::fail;
+using gtars::guarded;
 
 struct gtars_signal {
     std::vector<std::string> names;  // chromosome id -> name, ids in order of first appearance
@@ -48,17 +47,6 @@ namespace {
 
 constexpr uint32_t SIGM_MAGIC = 0x5349474D, SIGM_VERSION = 2;
 uint32_t g_sort_elems = gtars::SIGNAL_SORT_ELEMS;  // gtars_debug_signal_sort_elems
-
-template <class F>
-gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
 
 struct Bytes {  // of gtars_read_file
     char *p = nullptr;

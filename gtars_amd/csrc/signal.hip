@@ -326,11 +326,7 @@ gtars_status signal_summary_device(const SignalDevice &s, const uint32_t *d_chro
     GT_TRY(check_call(s, n, sort_elems));
     if (!n) return GTARS_OK;
     if (!d_chrom || !d_start || !d_end) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    int cur = -1;
-    GT_HIP(hipGetDevice(&cur));
-    if (cur != s.device)
-        return fail(GTARS_ERR_INVALID_ARG, "handle lives on device " + std::to_string(s.device) + ", current device is " +
-                                               std::to_string(cur) + ": device pointers and stream must belong to the handle's device");
+    GT_TRY(require_handle_device(s.device));
     StreamFrame fr((hipStream_t)stream);
     return summary_on(fr, s, d_chrom, d_start, d_end, n, want_rows, sort_elems, out);
 }

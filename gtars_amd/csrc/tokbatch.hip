@@ -17,6 +17,7 @@
 //     set's position writes its [unk].
 //   * k_set_pad, a lane per cell of the [B, W] matrix, a row's cells in consecutive lanes: the id, or the pad, and the mask byte.
 //     A row longer than W is reported, never cut.
+#include "byte_csr.h"
 #include "common.h"
 #include "pipeline.h"
 #include "tokbatch.h"
@@ -82,18 +83,6 @@ __global__ void k_set_offsets(const u64 *__restrict__ q_off, const u64 *__restri
         out_off[b] = clip ? scan[b] : q_off[set_off[b]] + scan[b];
 }
 
-// last i in [0, n) with off[i] <= p, given off[0] <= p < off[n]
-template <class P>
-__device__ __forceinline__ u32 last_le(P off, u32 n, u64 p) {
-    u32 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u32 m = lo + ((hi - lo) >> 1);
-        if (off[m] <= p) lo = m;
-        else hi = m;
-    }
-    return lo;
-}
-
 // out[p] for p in [0, total): total = out_off[n_sets] > 0, every set holds at least one position
 __global__ void __launch_bounds__(TB_TPB)
 k_set_pack(const u64 *__restrict__ out_off, const u64 *__restrict__ srcw, const u32 *__restrict__ src, u32 n_sets, u64 total, u32 unk,
@@ -140,16 +129,6 @@ k_set_pad(const u64 *__restrict__ out_off, const u32 *__restrict__ ids, u32 n_se
         input_ids[c] = is_id ? ids[o + (w - lead)] : pad;
         mask[c] = is_id ? 1 : 0;
     }
-}
-
-gtars_status same_device(const gtars_index_t *ix) {
-    int cur = -1;
-    GT_HIP(hipGetDevice(&cur));
-    const int dev = gtars_index_device(ix);
-    if (cur != dev)
-        return fail(GTARS_ERR_INVALID_ARG, "handle lives on device " + std::to_string(dev) + ", current device is " + std::to_string(cur) +
-                                               ": device pointers and stream must belong to the handle's device");
-    return GTARS_OK;
 }
 
 gtars_status too_small(u64 need) { return fail(GTARS_ERR_CAPACITY, "ids buffer too small: need " + std::to_string(need)); }
@@ -351,7 +330,7 @@ gtars_status gtars_tokenize_sets_device(const gtars_index_t *ix, const uint32_t 
         if (!ix) return fail(GTARS_ERR_INVALID_ARG, "NULL handle");
         if (nq && (!d_qchrom || !d_qstart || !d_qend)) return fail(GTARS_ERR_INVALID_ARG, "NULL query arrays");
         if (!d_set_offsets || !d_out_offsets) return fail(GTARS_ERR_INVALID_ARG, "NULL set offsets");
-        GT_TRY(same_device(ix));
+        GT_TRY(require_handle_device(gtars_index_device(ix)));
         u64 t = 0, l = 0;
         StreamFrame fr((hipStream_t)stream);
         const gtars_status st = sets_on(fr, ix, d_qchrom, d_qstart, d_qend, nq, d_set_offsets, n_sets, unk_id, max_length, d_out_offsets,

@@ -9,16 +9,17 @@
 
 #include "../../include/gtars_amd_host.h"
 #include "assembly.h"
+#include "guard.h"
 #include "host_threads.h"
 #include "vrs.h"
 #include "vrs_core.h"
 
 namespace gtars {
-gtars_status fail(gtars_status st, const std::string &msg);
 bool read_file_by_magic(const std::string &path, std::string &out, std::string &err);
 unsigned host_threads_for(unsigned cap);
 }  // namespace gtars
 using gtars::fail;
+using gtars::guarded;
 
 struct gtars_vrs_results {
     std::vector<uint32_t> chrom;  // chromosome id of the assembly
@@ -29,17 +30,6 @@ struct gtars_vrs_results {
 };
 
 namespace {
-
-template <class F>
-gtars_status guarded(F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(GTARS_ERR_INTERNAL, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
 
 unsigned threads_of(uint32_t threads) {
     const unsigned most = gtars::host_threads_for(0xFFFFFFFFu);

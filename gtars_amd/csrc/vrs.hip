@@ -15,11 +15,14 @@
 //     context from the image and the pool.  Nothing is staged in memory, the message schedule is a register ring.
 //     Alleles whose normalized sequence is longer than GTARS_VRS_HOST_LEN bytes are listed for the host instead (one lane
 //     must not hash a megabase serially): vrs_run finishes them with the same header on the host threads.
-//   * k_vrs_lens + the scan of kernels.hip + k_vrs_fill: the normalized sequences as a byte CSR, eight output bytes per lane.
+//   * k_vrs_lens + the scan of kernels.hip + the fill of byte_csr.h over VrsRowSrc (profiled as k_vrs_fill): the normalized
+//     sequences as a byte CSR, eight output bytes per lane.
 #include <cstring>
 
+#include "byte_csr.h"
 #include "common.h"
 #include "host_threads.h"
+#include "image_call.h"
 #include "pipeline.h"
 #include "sha512.h"
 #include "vrs.h"
@@ -339,44 +342,22 @@ __global__ void __launch_bounds__(VRS_TPB) k_vrs_lens(VrsView v, u32 *__restrict
     }
 }
 
-__global__ void __launch_bounds__(VRS_TPB) k_vrs_fill(VrsView v, const u64 *__restrict__ off, u64 total, u8 *__restrict__ out) {
-    const u64 groups = (total + 7) >> 3;
-    for (u64 g = (u64)blockIdx.x * VRS_TPB + threadIdx.x; g < groups; g += (u64)gridDim.x * VRS_TPB) {
-        u64 q = g << 3;
-        const u64 q_end = min(q + 8, total);
-        // the row of byte q: the last r with off[r] <= q whose sequence is not empty
-        u32 lo = 0, hi = v.n;
-        while (hi - lo > 1) {
-            const u32 m = lo + ((hi - lo) >> 1);
-            if (off[m] <= q) lo = m;
-            else hi = m;
-        }
-        u32 r = lo;
-        for (; q < q_end; ++q) {
-            while (off[r + 1] <= q) ++r;  // (q < total = off[n]: stops inside the table)
-            const u64 k = q - off[r];
-            const u8 *seq = v.seq + v.coff[v.chrom[r]];
-            const u32 lroll = v.lroll[r], t_len = v.t_len[r];
-            u32 b;
-            if (k < lroll) b = up(seq[v.ns[r] + k]);
-            else if (k < (u64)lroll + t_len) b = v.pool[v.t_off[r] + (k - lroll)];
-            else b = up(seq[v.ne[r] - v.rroll[r] + (k - lroll - t_len)]);
-            out[q] = (u8)b;
-        }
+// a row of the CSR: the left context upper-cased, the trimmed ALT, the right context upper-cased
+struct VrsRowSrc {
+    VrsView v;
+    const u8 *lctx, *alt, *rctx;  // of the open row
+    u32 lroll, t_len;
+    __device__ __forceinline__ void open(u32 r) {
+        const u8 *seq = v.seq + v.coff[v.chrom[r]];
+        lroll = v.lroll[r], t_len = v.t_len[r];
+        lctx = seq + v.ns[r], alt = v.pool + v.t_off[r], rctx = seq + (v.ne[r] - v.rroll[r]);
     }
-}
-
-template <class T>
-gtars_status bring(StreamFrame &fr, bool on_device, const T *src, size_t n, const T **out) {
-    if (on_device) {
-        *out = src;
-        return GTARS_OK;
+    __device__ __forceinline__ u32 byte(u64 k) const {
+        if (k < lroll) return up(lctx[k]);
+        if (k < (u64)lroll + t_len) return alt[k - lroll];
+        return up(rctx[k - lroll - t_len]);
     }
-    T *d;
-    GT_TRY(fr.upload(&d, src, n));
-    *out = d;
-    return GTARS_OK;
-}
+};
 
 }  // namespace
 
@@ -390,17 +371,11 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
     if (!call.n) return GTARS_OK;
     if (!call.chrom || !call.start || !call.ref_off || !call.ref_len || !call.alt_off || !call.alt_len || (!call.pool && call.pool_bytes))
         return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-    if (call.on_device) {
-        if (call.digest && ((uintptr_t)call.digest & 7)) return fail(GTARS_ERR_INVALID_ARG, "vrs: the device digests must be 8-byte aligned");
-        int cur = -1;
-        GT_HIP(hipGetDevice(&cur));
-        if (cur != ap.device)
-            return fail(GTARS_ERR_INVALID_ARG, "handle lives on device " + std::to_string(ap.device) + ", current device is " +
-                                                   std::to_string(cur) + ": device pointers and stream must belong to the handle's device");
-    }
-    DeviceScope on(call.on_device ? -1 : ap.device);
-    GT_TRY(on.st);
-    StreamFrame fr(call.on_device ? (hipStream_t)call.stream : nullptr);
+    GT_TRY(digests_aligned("vrs", call.on_device, call.digest));
+    if (call.on_device) GT_TRY(require_handle_device(ap.device));
+    ImageCall ic(ap, call.on_device, call.stream);
+    GT_TRY(ic.scope.st);
+    StreamFrame &fr = ic.fr;
     hipStream_t st = fr.st;
     const size_t n = (size_t)call.n;
     const long cap = std::max(1l, std::min(cfg_int("GTARS_VRS_ROLL_CAP", 64), 0x40000000l));
@@ -408,26 +383,22 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
 
     VrsView v{};
     v.seq = ap.seq, v.coff = ap.off, v.clen = ap.len, v.n_chrom = ap.n_chrom, v.n = (u32)n, v.pool_bytes = call.pool_bytes;
-    GT_TRY(bring(fr, call.on_device, call.chrom, n, &v.chrom));
-    GT_TRY(bring(fr, call.on_device, call.start, n, &v.start));
-    GT_TRY(bring(fr, call.on_device, call.ref_off, n, &v.ref_off));
-    GT_TRY(bring(fr, call.on_device, call.ref_len, n, &v.ref_len));
-    GT_TRY(bring(fr, call.on_device, call.alt_off, n, &v.alt_off));
-    GT_TRY(bring(fr, call.on_device, call.alt_len, n, &v.alt_len));
-    GT_TRY(bring(fr, call.on_device, call.pool, (size_t)call.pool_bytes, &v.pool));
+    GT_TRY(ic.in(call.chrom, n, &v.chrom));
+    GT_TRY(ic.in(call.start, n, &v.start));
+    GT_TRY(ic.in(call.ref_off, n, &v.ref_off));
+    GT_TRY(ic.in(call.ref_len, n, &v.ref_len));
+    GT_TRY(ic.in(call.alt_off, n, &v.alt_off));
+    GT_TRY(ic.in(call.alt_len, n, &v.alt_len));
+    GT_TRY(ic.in(call.pool, (size_t)call.pool_bytes, &v.pool));
     if (call.accessions) {
         u8 *d_acc;
         GT_TRY(fr.upload(&d_acc, (const u8 *)call.accessions, (size_t)ap.n_chrom * 32));
         v.acc = d_acc;
     }
     // per-allele results: the caller's device columns where it gave them, the frame's otherwise
-    const bool dev_out = call.on_device;
-    if (dev_out && call.status) v.status = call.status;
-    else GT_TRY(fr.alloc(&v.status, n));
-    if (dev_out && call.new_start) v.ns = call.new_start;
-    else GT_TRY(fr.alloc(&v.ns, n));
-    if (dev_out && call.new_end) v.ne = call.new_end;
-    else GT_TRY(fr.alloc(&v.ne, n));
+    GT_TRY(ic.out(call.status, n, &v.status));
+    GT_TRY(ic.out(call.new_start, n, &v.ns));
+    GT_TRY(ic.out(call.new_end, n, &v.ne));
     GT_TRY(fr.alloc(&v.lroll, n));
     GT_TRY(fr.alloc(&v.rroll, n));
     GT_TRY(fr.alloc(&v.t_off, n));
@@ -450,8 +421,7 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
     }
     if (call.digest) {
         u64 *d_digest;
-        if (dev_out) d_digest = (u64 *)call.digest;
-        else GT_TRY(fr.alloc(&d_digest, 4 * n));
+        GT_TRY(ic.digests_out(call.digest, n, &d_digest));
         VrsHostRec *host_list;
         GT_TRY(fr.alloc(&host_list, n));
         {
@@ -459,8 +429,8 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
             hipLaunchKernelGGL(k_vrs_digest, dim3(grid), dim3(VRS_TPB), 0, st, v, (u32)host_len, d_digest, host_list, counters + 1);
             GT_HIP(hipGetLastError());
         }
-        u32 *h_n = (u32 *)fr.host(sizeof(u32));
-        if (!h_n) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+        u32 *h_n;
+        GT_TRY(ic.host_word(&h_n));
         GT_TRY(fr.download(h_n, counters + 1, 1));
         GT_TRY(fr.drain());
         if (const u32 n_host = *h_n) {
@@ -488,11 +458,11 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
             for (u32 k = 0; k < n_host; ++k) GT_TRY(fr.upload_to((char *)(d_digest + 4 * (size_t)recs[k].idx), &text[(size_t)k * 32], 32));
             GT_TRY(fr.drain());
         }
-        if (!dev_out) GT_TRY(fr.download(call.digest, (const char *)d_digest, 32 * n));
+        GT_TRY(ic.digests_back(call.digest, d_digest, n));
     }
     if (call.seq_off) {
-        u32 *cnt, *h_bad = (u32 *)fr.host(sizeof(u32));
-        if (!h_bad) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+        u32 *cnt, *h_bad;
+        GT_TRY(ic.host_word(&h_bad));
         GT_TRY(fr.alloc(&cnt, n));
         {
             ProfScope ps("k_vrs_lens", st);
@@ -508,17 +478,13 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
         if (total) {
             u8 *d_bytes;
             GT_TRY(fr.alloc(&d_bytes, (size_t)total));
-            ProfScope ps("k_vrs_fill", st);
-            hipLaunchKernelGGL(k_vrs_fill, dim3(grid_for((total + 7) >> 3, VRS_TPB, VRS_MAX_BLOCKS)), dim3(VRS_TPB), 0, st, v, off, total, d_bytes);
-            GT_HIP(hipGetLastError());
+            GT_TRY(csr_fill("k_vrs_fill", VrsRowSrc{v}, off, v.n, total, d_bytes, st));
             GT_TRY(fr.download(call.seq_bytes->data(), d_bytes, (size_t)total));
         }
     }
-    if (!dev_out) {
-        if (call.status) GT_TRY(fr.download(call.status, v.status, n));
-        if (call.new_start) GT_TRY(fr.download(call.new_start, v.ns, n));
-        if (call.new_end) GT_TRY(fr.download(call.new_end, v.ne, n));
-    }
+    GT_TRY(ic.back(call.status, v.status, n));
+    GT_TRY(ic.back(call.new_start, v.ns, n));
+    GT_TRY(ic.back(call.new_end, v.ne, n));
     return fr.drain();
 }
 

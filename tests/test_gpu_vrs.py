@@ -305,6 +305,47 @@ def test_device_path_equals_the_host_path(world, mixed_batch):
     assert V.vrs_ids(g, *cols)["ids"] == V.vrs_ids(g, *cols, on_host=True)["ids"]
 
 
+def test_sequences_at_every_group_offset_and_tail(world):
+    """the byte CSR of the normalized sequences (byte_csr.h over the source of vrs.hip: eight output bytes per lane, whole
+    groups stored as one word): sequences that start at every offset 0 .. 7 of a group, made of left context, ALT and right
+    context or of the ALT alone, one to 1300 bytes long; failing rows -- empty sequences -- first, twice in a row in the middle
+    and last; eight batches that drop 0 .. 7 trailing one-byte rows, so the packed total has every residue mod 8"""
+    from gtars_amd import vrs as V
+
+    seqs, where, loaded, acc = world
+    big = seqs["big"]
+    rng = random.Random(21)
+    failing = _kinds(seqs)[1]
+
+    def mnvs(count, first):
+        return [("big", first + 50 * k) + _mnv(big, first + 50 * k, 1 + k % 11, rng) for k in range(count)]
+
+    head = failing[3:4] + _repeat_rows(where, seqs) + mnvs(90, 10_000) + failing[0:1] + failing[4:5] + _cap_rows(where)[:6] + mnvs(90, 20_000)
+    ones = [("big", 30_000 + 50 * k) + _mnv(big, 30_000 + 50 * k, 1, rng) for k in range(7)]
+    last = failing[1:2]
+    rows = head + ones + last
+    st, _, _, sq, _ = R.alleles(seqs, acc, rows)
+    assert 200 <= len(rows) <= 400
+    n_head = len(head)
+    assert [len(s) for s in sq[n_head:]] == [1] * 7 + [0] and st[-1] != R.OK
+    assert st[0] != R.OK and sq[0] == b"" and any(st[k] != R.OK and st[k + 1] != R.OK and sq[k] == sq[k + 1] == b"" for k in range(1, n_head - 1))
+    starts = np.cumsum([0] + [len(s) for s in sq])[:-1]
+    assert {int(o) % 8 for o, s in zip(starts, sq) if s} == set(range(8))
+    assert {int(o) % 8 for o, s in zip(starts, sq) if len(s) > 8} == set(range(8))  # ... of sequences that cross a group's end, too
+    totals = set()
+    for drop in range(8):
+        keep = list(range(n_head + 7 - drop)) + [len(rows) - 1]
+        batch, want = [rows[k] for k in keep], [sq[k] for k in keep]
+        totals.add(sum(len(s) for s in want) % 8)
+        cols = [[r[k] for r in batch] for k in range(4)]
+        for g in loaded:
+            dev, host = V.normalize_alleles(g, *cols), V.normalize_alleles(g, *cols, on_host=True)
+            assert dev["statuses"].tolist() == [st[k] for k in keep] == host["statuses"].tolist()
+            assert dev["sequences"] == want
+            assert host["sequences"] == want
+    assert totals == set(range(8))
+
+
 def test_file_call(tmp_path):
     """the CPU test's small VCF through compute_vrs_ids, plain and BGZF, row for row; with one REF mismatch the call raises for
     the first failing row in file order"""
