@@ -61,6 +61,34 @@ __device__ __forceinline__ void st_stream2(u64 *p, u64 a, u64 b) {
     __builtin_nontemporal_store(v, reinterpret_cast<u64x2 *>(p));
 }
 
+// The tail of a launch behind its count phase (A/B: profiles/tok_tail/tok_tail_ab.txt):
+#ifndef GTARS_TOK_EARLY0
+#define GTARS_TOK_EARLY0 1  // one-tile-per-workgroup launches (k_tok_lds<.., ONE>): wave 0 stages its round-0 ids BEFORE the scan barrier, where it would only wait for the other waves
+#endif
+#ifndef GTARS_TOK_DENSE_OFF
+#define GTARS_TOK_DENSE_OFF 1  // one-tile-per-workgroup launches (k_tok_lds<.., ONE>): a full wave's offsets leave as two stores of 1 KiB contiguous
+                               // (store_offsets_dense; the two-round builds sit at the register limit and the exchange would spill)
+#endif
+// (Measured and dropped: the dense stores as write-through stores, sc0 sc1 -- 17.16 vs 17.01 us per step of the 1M headline.)
+// A wave's 256 u64 offsets from the lanes' four wave-relative u32 each.  Lane l holds queries 4l .. 4l + 3; two 16-byte stores per
+// lane at a 32-byte lane stride would fill half of each of 16 lines per instruction.  Here store k writes queries [128k, 128k + 128):
+// v_permlane32_swap brings the pairs (o0, o1) and (o2, o3) of source lane m to lanes m and 32 + m (store 0: the lower half's
+// queries, store 1: the upper half's), and ds_bpermute (a lane crossbar: no LDS memory) puts chunk l into lane l.
+__device__ __forceinline__ void store_offsets_dense(u64 *__restrict__ woff, u64 wave_base, const u32 (&o)[4], int lane) {
+    const auto a = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
+    const auto b = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
+    u32 x[2] = {a[0], a[1]}, y[2] = {b[0], b[1]};
+    const int src = (((lane >> 1) + 32 * (lane & 1)) << 2);  // chunk l = queries 2l, 2l + 1 of the store's 128
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        x[k] = (u32)__builtin_amdgcn_ds_bpermute(src, (int)x[k]);
+        y[k] = (u32)__builtin_amdgcn_ds_bpermute(src, (int)y[k]);
+        st_stream2(woff + 128 * k + 2 * lane, wave_base + x[k], wave_base + y[k]);
+    }
+}
+// wave-uniform: the wave's 256 queries (the lane's first is q0) all exist
+__device__ __forceinline__ bool wave_full(u64 q0, u64 nq, int lane) { return q0 - 4u * (u64)lane + 256u <= nq; }
+
 // diagnostic build (tools/build_variant.sh tokstamps "-DGTARS_TOK_STAMPS=1", tools/r03_tok_stamps.py): shader-clock totals per
 // phase of the tile loop, for wave 0 (the look-back wave) and wave 1 of every workgroup, and the look-back's round counts
 #ifndef GTARS_TOK_FILL_U
@@ -881,7 +909,7 @@ template <int QPT, bool FILTER, bool IMPL, bool REV, int RUNS, bool U64 = false>
 __device__ __forceinline__ void write_queries(const AccelView &a, const SearchLds &L, const u32 *__restrict__ qc,
                                               const u32 *__restrict__ qs, const u32 *__restrict__ qe, u64 nq, i32 min_bp,
                                               const TileQ<QPT, IMPL> &t, u64 q0, u64 wave_base, u64 *__restrict__ offsets,
-                                              u32 *__restrict__ ovals, u64 cap, bool off_vec_ok, u32 *stage, u32 stage_cap,
+                                              u32 *__restrict__ ovals, u64 cap, bool off_vec_ok, bool dense_ok, u32 *stage, u32 stage_cap,
                                               int lane) {
     const bool staged = cap && t.wtotal <= stage_cap && wave_base + t.wtotal <= cap;
     u64 o4[QPT];
@@ -902,6 +930,10 @@ __device__ __forceinline__ void write_queries(const AccelView &a, const SearchLd
     }
     if (GTARS_TOK_ABLATE & 4) {
         if (o4[0] == 0xFFFFFFFFFFFFFFFFull) offsets[q0] = o4[QPT - 1];
+    } else if (GTARS_TOK_DENSE_OFF && QPT == 4 && dense_ok && wave_full(q0, nq, lane)) {
+        // (a wave's offsets lie within wave_base + wtotal: 32 bits relative to wave_base)
+        const u32 orel[4] = {(u32)(o4[0] - wave_base), (u32)(o4[1] - wave_base), (u32)(o4[2] - wave_base), (u32)(o4[3] - wave_base)};
+        store_offsets_dense(offsets + (q0 - 4u * (u64)lane), wave_base, orel, lane);
     } else if (QPT >= 2 && off_vec_ok && q0 + QPT <= nq) {
 #pragma unroll
         for (int h = 0; h < QPT / 2; ++h) st_stream2(offsets + q0 + 2 * h, o4[2 * h], o4[2 * h + 1]);
@@ -939,7 +971,7 @@ __device__ __forceinline__ bool stage_queries(const AccelView &a, const SearchLd
 }
 template <int QPT>
 __device__ __forceinline__ void flush_queries(u64 nq, u32 wtotal, const u32 (&orel)[QPT], u64 q0, u64 wave_base,
-                                              u64 *__restrict__ offsets, u32 *__restrict__ ovals, u64 cap, bool off_vec_ok,
+                                              u64 *__restrict__ offsets, u32 *__restrict__ ovals, u64 cap, bool off_vec_ok, bool dense_ok,
                                               const u32 *stage, int lane) {
     if (cap && !(GTARS_TOK_ABLATE & 2)) {
         // within the caller's capacity; 256 bytes per store instruction
@@ -948,6 +980,8 @@ __device__ __forceinline__ void flush_queries(u64 nq, u32 wtotal, const u32 (&or
     }
     if (GTARS_TOK_ABLATE & 4) {
         if (orel[0] == 0xFFFFFFFFu) offsets[q0] = orel[QPT - 1];
+    } else if (GTARS_TOK_DENSE_OFF && QPT == 4 && dense_ok && wave_full(q0, nq, lane)) {
+        store_offsets_dense(offsets + (q0 - 4u * (u64)lane), wave_base, orel, lane);
     } else if (QPT >= 2 && off_vec_ok && q0 + QPT <= nq) {
 #pragma unroll
         for (int h = 0; h < QPT / 2; ++h) st_stream2(offsets + q0 + 2 * h, wave_base + orel[2 * h], wave_base + orel[2 * h + 1]);
@@ -1087,7 +1121,9 @@ __device__ __forceinline__ void group_barrier(u32 *ctr, u32 &phase, u32 members,
     asm volatile("" ::: "memory");
 }
 
-template <int TPB, int QPT, int R, int G, bool FILTER, bool IMPL, bool REV, int RUNS, bool U64 = false>
+// ONE: the build for launches of one tile per workgroup (R = 1, G = 1, tiles <= workgroups; launch_tok_pick) -- nothing is drawn, and the
+// tail behind the count phase is shortened (GTARS_TOK_EARLY0, GTARS_TOK_DENSE_OFF).  Pipelined launches run the build without.
+template <int TPB, int QPT, int R, int G, bool FILTER, bool IMPL, bool REV, int RUNS, bool U64 = false, bool ONE = false>
 __global__ void __launch_bounds__(TPB, TPB / 256)
 k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, const u32 *__restrict__ qe,
           u64 nq, i32 min_bp, u64 *__restrict__ offsets, u32 *__restrict__ ovals, u64 cap, ScanWs *ws,
@@ -1149,7 +1185,13 @@ k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, c
         u32 wbase[R], total, tile;
     } cur, prev;
     bool have_prev = false, loaded = true;
-    const bool draw = num_tiles > first_tiles;  // otherwise one tile per group: nothing to draw
+    static_assert(!ONE || (R == 1 && G == 1), "the one-tile build: one round, one group");
+    const bool draw = !ONE && num_tiles > first_tiles;  // otherwise one tile per group: nothing to draw
+    const bool dense_ok = ONE && GTARS_TOK_DENSE_OFF != 0 && off_vec_ok;  // (store_offsets_dense)
+    constexpr bool EARLY = ONE && GTARS_TOK_EARLY0 != 0;
+    u32 orel_e[QPT] = {};  // wave 0's early staging (below): kept from the tile's count to its write, one iteration later
+    bool pre_e = false;
+    const bool early0 = EARLY && gwave == 0;
 #if GTARS_TOK_STAMPS
     u64 ts_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ts_last = __builtin_amdgcn_s_memtime();
 #endif
@@ -1182,6 +1224,22 @@ k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, c
                 if (lane == 63) s_scan[grp][r * GW + gwave] = inc[r];
             }
             if (draw && gtid == 0) s_tile[grp] = first_tiles + (ticket - ticket_base);
+            if constexpr (EARLY) {
+            // One tile per group: the group's wave 0 -- the oldest wave, first to finish counting -- would wait here for the other
+            // waves, then look back, and only then stage its ids while every other wave waits for IT.  Staging needs nothing of
+            // the scan (excl and wtotal are wave-local) and the wave's buffer is free (no previous tile): it happens now.
+            // (Pipelined launches: the buffer still holds the previous tile's ids until the flush below.)
+            // (the kept offsets are re-defined in every pass: left alone they count as live across the count phase)
+#pragma unroll
+            for (int j = 0; j < QPT; ++j) orel_e[j] = 0;
+            if (early0) {
+                cur.q[0].excl = inc[0] - tsum[0];
+                cur.q[0].wtotal = __builtin_amdgcn_readlane(inc[0], 63);
+                const u64 cur_q0 = (u64)tile * TILE + (u64)gtid * QPT;
+                pre_e = stage_queries<QPT, FILTER, IMPL, REV, RUNS, U64>(a, L, qc, qs, qe, min_bp, cur.q[0], cur_q0, cap, stage, stage_cap, orel_e);
+            }
+            TSTAMP(10);
+            }
             bar();
             TSTAMP(2);
             if (draw) next_tile = s_tile[grp];
@@ -1221,8 +1279,14 @@ k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, c
         }
         TSTAMP(7);
         if (have_prev) {
-            if (gwave == 0)
-                pre0 = stage_queries<QPT, FILTER, IMPL, REV, RUNS, U64>(a, L, qc, qs, qe, min_bp, prev.q[0], prev_q0, cap, stage, stage_cap, orel0);
+            if (gwave == 0) {
+                if (EARLY && early0) {  // staged before the scan barrier of the iteration that counted the tile
+                    pre0 = pre_e;
+#pragma unroll
+                    for (int j = 0; j < QPT; ++j) orel0[j] = orel_e[j];
+                } else
+                    pre0 = stage_queries<QPT, FILTER, IMPL, REV, RUNS, U64>(a, L, qc, qs, qe, min_bp, prev.q[0], prev_q0, cap, stage, stage_cap, orel0);
+            }
             TSTAMP(3);
             bar();
             TSTAMP(4);
@@ -1233,11 +1297,11 @@ k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, c
             for (int r = 0; r < R; ++r) {
                 const u64 q0 = (u64)prev.tile * TILE + (u64)r * ROUND + (u64)gtid * QPT;
                 if (r == 0 && pre0)
-                    flush_queries<QPT>(nq, prev.q[0].wtotal, orel0, q0, s_prefix[grp] + prev.wbase[0], offsets, ovals, cap, off_vec_ok,
+                    flush_queries<QPT>(nq, prev.q[0].wtotal, orel0, q0, s_prefix[grp] + prev.wbase[0], offsets, ovals, cap, off_vec_ok, dense_ok,
                                        stage, lane);
                 else
                     write_queries<QPT, FILTER, IMPL, REV, RUNS, U64>(a, L, qc, qs, qe, nq, min_bp, prev.q[r], q0, s_prefix[grp] + prev.wbase[r],
-                                                          offsets, ovals, cap, off_vec_ok, stage, stage_cap, lane);
+                                                          offsets, ovals, cap, off_vec_ok, dense_ok, stage, stage_cap, lane);
             }
         }
 #if GTARS_TOK_PRIO & 2
@@ -1753,7 +1817,7 @@ k_tok_sweep(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs,
                 const u64 wave_base = s_prefix + prev.wbase[r];
                 const bool staged = r == 0 ? pre0 : stage_round(r);
                 if (staged) {
-                    flush_queries<QPT>(nq, prev.q[r].wtotal, orel, q0, wave_base, offsets, ovals, cap, off_vec_ok, reg, lane);
+                    flush_queries<QPT>(nq, prev.q[r].wtotal, orel, q0, wave_base, offsets, ovals, cap, off_vec_ok, false, reg, lane);
                 } else {
                     u64 o4[QPT];
                     emit_sweep<FILTER, IMPL, REV>(a, qc, qs, qe, min_bp, prev.q[r], q0, wave_base + prev.q[r].excl, cap != 0, o4,
@@ -2010,13 +2074,13 @@ static u32 stage_words(const AccelView &a, int tpb, int per_cu) {
     return w >= 128 ? (u32)w : 0u;
 }
 
-template <int TPB, int QPT, int R, int G, bool FILTER, bool IMPL, bool REV, int RUNS, bool U64 = false>
+template <int TPB, int QPT, int R, int G, bool FILTER, bool IMPL, bool REV, int RUNS, bool U64 = false, bool ONE = false>
 static gtars_status launch_tok_t(const AccelView &a, const u32 *qc, const u32 *qs, const u32 *qe, u64 nq,
                                  i32 min_bp, const EnumOut &out, ScanWs *ws, ScanEpoch &ep, const u64 *d_base, u64 *d_total_out,
                                  hipStream_t st) {
     static KernelSetup setup;
     int dev = 0, cus = 256;
-    gtars_status s0 = setup.get(reinterpret_cast<const void *>(k_tok_lds<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64>), dev, cus);
+    gtars_status s0 = setup.get(reinterpret_cast<const void *>(k_tok_lds<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64, ONE>), dev, cus);
     if (s0) return s0;
     // one 1024-thread workgroup per CU: one LDS copy of the search keys, 16 waves -- what 128 VGPRs admit
     const u32 stage = stage_words(a, TPB, 1);
@@ -2025,13 +2089,26 @@ static gtars_status launch_tok_t(const AccelView &a, const u32 *qc, const u32 *q
     const u64 tile_q = tok_tile_queries(TPB / G, QPT * R);
     const u64 tiles = (nq + tile_q - 1) / tile_q;
     const u64 grid = std::min<u64>((u64)cus, (tiles + G - 1) / G);
+    if constexpr (ONE) {  // (more tiles than this device's workgroups after all: the pipelined build)
+        if (tiles > grid * G) return launch_tok_t<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64, false>(a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
+    }
     const u64 cap = out.vals ? out.capacity : 0;
-    hipLaunchKernelGGL((k_tok_lds<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64>), dim3((unsigned)grid), dim3(TPB), lds, st, a, qc, qs, qe, nq,
+    hipLaunchKernelGGL((k_tok_lds<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64, ONE>), dim3((unsigned)grid), dim3(TPB), lds, st, a, qc, qs, qe, nq,
                        min_bp, out.offsets, out.vals, cap, ws, ep.epoch, ep.ticket_base, stage, spin_limit, d_base, d_total_out);
     GT_HIP(hipGetLastError());
     // tickets drawn by this launch: one per tile beyond the first `grid * G`, plus one failing draw per group
     if (tiles > grid * G) ep.ticket_base += (u32)tiles;
     return GTARS_OK;
+}
+
+// one round, one group and no more tiles than workgroups: the one-tile build (k_tok_lds<.., ONE>); everything else the pipelined one
+template <int TPB, int QPT, int R, int G, bool FILTER, bool IMPL, bool REV, int RUNS, bool U64 = false>
+static gtars_status launch_tok_pick(bool one, const AccelView &a, const u32 *qc, const u32 *qs, const u32 *qe, u64 nq, i32 min_bp,
+                                    const EnumOut &out, ScanWs *ws, ScanEpoch &ep, const u64 *d_base, u64 *d_total_out, hipStream_t st) {
+    if constexpr (R == 1 && G == 1) {
+        if (one) return launch_tok_t<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64, true>(a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
+    }
+    return launch_tok_t<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64, false>(a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
 }
 
 gtars_status launch_tokenize_lds(const AccelView &a, const u32 *qc, const u32 *qs, const u32 *qe, u64 nq,
@@ -2112,10 +2189,11 @@ gtars_status launch_tokenize_lds(const AccelView &a, const u32 *qc, const u32 *q
     const i32 min_bp = has_min ? min_overlap : 0;
     ScanWs *ws = (ScanWs *)scan_ws;
     if (!impl && !a.rec4) return fail(GTARS_ERR_INTERNAL, "index has no id records");
+    const bool one = rounds == 1 && groups == 1 && tiles <= (u64)cus;  // (launch_tok_t: grid = min(CUs, tiles))
     ProfScope p("k_tok_lds", st);
 #define GT_TOK_CASE(N, GG, F, I, V, W)                                                                                      \
     if (rounds == N && groups == GG && filter == F && impl == I && reverse == V && wide == (W != 0))                        \
-        return launch_tok_t<TPB, 4, N, GG, F, I, V, W>(a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
+        return launch_tok_pick<TPB, 4, N, GG, F, I, V, W>(one, a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
 #define GT_TOK_GEOM(N, GG, I)                                                                                               \
     GT_TOK_CASE(N, GG, false, I, false, 0)                                                                                  \
     GT_TOK_CASE(N, GG, true, I, false, 0)                                                                                   \
@@ -2124,7 +2202,7 @@ gtars_status launch_tokenize_lds(const AccelView &a, const u32 *qc, const u32 *q
 #define GT_TOK_WIDE(GG, I)                                                                                                  \
     GT_TOK_CASE(1, GG, false, I, false, GTARS_TOK_RUNS)                                                                     \
     GT_TOK_CASE(1, GG, false, I, true, GTARS_TOK_RUNS)
-    if (unit_rec && groups == 1) return launch_tok_t<TPB, 4, 1, 1, false, true, false, 0, true>(a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
+    if (unit_rec && groups == 1) return launch_tok_pick<TPB, 4, 1, 1, false, true, false, 0, true>(one, a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
     if (unit_rec && groups == 2) return launch_tok_t<TPB, 4, 1, 2, false, true, false, 0, true>(a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
     GT_TOK_GEOM(1, 1, true)
     GT_TOK_GEOM(2, 1, true)

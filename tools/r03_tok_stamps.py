@@ -34,9 +34,9 @@ for n in [int(x) for x in os.environ.get("SIZES", "1000000,64000000").split(",")
     print(f"== {n} queries: {e0.elapsed_time(e1) * 1e3:.1f} us (diagnostic build)")
     for w in (0, 1):
         x = v[12 * w: 12 * w + 12]
-        wg, tot = max(x[11], 1), sum(x[:8])
+        wg, tot = max(x[11], 1), sum(x[:8]) + x[10]
         if w == 1: print(f"  look-back rounds: {x[8]} without a wait, {x[9]} after spinning (all workgroups)")
         print(f"  wave {w}: {wg} workgroups, {tot / wg:.0f} cycles each")
-        for nme, y in zip(NAMES, x[:8]):
+        for nme, y in zip(NAMES + ["early stage (wave 0, one-tile launches)"], x[:8] + [x[10]]):
             print(f"     {nme:34s} {y / wg:10.0f}  {100 * y / tot:5.1f} %")
     del big, off, ids
