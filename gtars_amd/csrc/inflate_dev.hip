@@ -12,7 +12,7 @@
 // Everything the serial chain touches lives in LDS, whose round trip is ~100 cycles against ~1 us for the L2:
 //   window   32 KiB ring of the stream's last output bytes (a match reads it, literals and matches write it); flushed to the
 //            result in 4-KiB pieces, 16 bytes per lane and store
-//   input    2 KiB ring (+ 8 mirrored bytes), refilled a KiB at a time, the next KiB already in registers
+//   input    2 KiB ring (+ 16 mirrored bytes), refilled a KiB at a time, the next KiB already in registers
 //   tables   literal/length: 512 entries (9 bits), distance: 256 entries (8 bits), u32 each; a longer code -- rare -- is decoded
 //            bit by bit from the canonical code's per-length counts and its symbols in code order (what zlib's puff.c does)
 // = 39.5 KiB per wave: four streams per CU, 1024 at once on the chip.
@@ -20,6 +20,8 @@
 // The decoder REFUSES rather than diagnoses, like the host's inflate_fast.h: status != 0 (invalid code, distance in front of the
 // stream, input or output exhausted) sends the file back to the host path, whose checks and messages are the ones a user sees.
 // The caller verifies length and CRC-32 of what comes out (the pipeline computes the CRC on the device anyway).
+// One valid stream is refused by design: a block whose literal/length code is nothing but a 1-bit end-of-block code counts as an
+// incomplete code (status 2), as in inflate_fast.h; zlib decodes it, and no compressor writes it.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -151,7 +153,8 @@ __device__ u32 inf_slow(BitReader &r, const unsigned short *cnt, const unsigned 
 }
 
 // Decode tables of a canonical Huffman code given as code lengths in L.lens[base, base + n).  Lanes work on symbols side by side.
-// kind 0: literal/length, 1: distance.  -> false: over-subscribed or incomplete (a distance code of <= 1 symbol is accepted)
+// kind 0: literal/length, 1: distance.  -> false: over-subscribed or incomplete (a distance code of no symbol, or of a single
+// 1-bit one, is accepted)
 __device__ bool inf_build(InfLds &L, u32 base, u32 n, int kind, int lane) {
     u32 *table = kind ? L.dd : L.ll;
     unsigned short *cnt = kind ? L.d_cnt : L.ll_cnt, *syms = kind ? L.d_sym : L.ll_sym;
@@ -177,7 +180,8 @@ __device__ bool inf_build(InfLds &L, u32 base, u32 n, int kind, int lane) {
         over = over || left < 0;
     }
     if (over) return false;
-    if (left > 0 && !(kind == 1 && used <= 1u)) return false;  // incomplete (zlib accepts it only for the distance code of <= 1 symbol)
+    // incomplete: zlib accepts it only for a distance code of no symbol, or of one symbol whose code is one bit long
+    if (left > 0 && !(kind == 1 && (used == 0u || (used == 1u && count[1] == 1u)))) return false;
     // first code and first index (in code order) of every length
     u32 next_code[16], offs[16];
     {

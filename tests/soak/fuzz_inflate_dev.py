@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Soak fuzzer of the device-side DEFLATE decoder (csrc/inflate_dev.hip) against zlib: rounds of 64 random streams -- texts of
-five kinds, zlib levels 0-9 and strategies -- of which a third are damaged (byte flips, truncation, random bytes).  An intact
+"""Soak fuzzer of the device-side DEFLATE decoder (csrc/inflate_dev.hip) against zlib: rounds of 64 random streams -- two thirds
+texts of five kinds under zlib levels 0-9 and strategies, one third from tests/deflate_writer.py's random_stream (codes up to 15
+bits, distance codes of one or no symbol, random headers: what zlib's compressor never writes) -- of which a third are damaged
+(byte flips, truncation, random bytes).  An intact
 stream must come out bit-exact with the exact number of bytes consumed; a damaged one must be refused OR decode to something --
 whatever it does, not a byte may be written behind its capacity (guard bytes) and the call must return.
 usage: python tests/soak/fuzz_inflate_dev.py [rounds=200] [seed=1]"""
@@ -9,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
+from deflate_writer import random_stream
 from test_gpu_inflate import _run, _fragment_text
 
 def main():
@@ -32,8 +35,11 @@ def main():
                 d = bytes(np.repeat(rng.integers(0, 256, n // 50 + 1, dtype=np.uint8), rng.integers(1, 300, n // 50 + 1)))
             else:
                 d = bytes(rng.integers(0, 256, n, dtype=np.uint8))
-            co = zlib.compressobj(int(rng.integers(0, 10)), zlib.DEFLATED, -int(rng.integers(9, 16)), int(rng.integers(1, 10)), strategies[int(rng.integers(0, 5))])
-            s = co.compress(d) + co.flush()
+            if k % 3 == 2:  # the writer's own streams (seeds 0 .. 199 are the suite's: draw beyond them)
+                s, d = random_stream(int(rng.integers(200, 1 << 40)))
+            else:
+                co = zlib.compressobj(int(rng.integers(0, 10)), zlib.DEFLATED, -int(rng.integers(9, 16)), int(rng.integers(1, 10)), strategies[int(rng.integers(0, 5))])
+                s = co.compress(d) + co.flush()
             ok = True
             mode = int(rng.integers(0, 9))
             if mode == 0 and len(s) > 4:
