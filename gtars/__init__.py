@@ -5,8 +5,9 @@ code reads ``from gtars.tokenizers import Tokenizer``, ``from gtars.models impor
 ``from gtars.utils import read_tokens_from_gtok``, ``from gtars.lola import RegionDB, run_lola``.  This package makes
 those imports resolve to the MI355X implementation (gtars_amd.*) without edits to the calling code.
 ``gtars.genomic_distributions`` provides ``consensus`` and ``median_abs_distance``, the functions of that module that need
-nothing beyond region sets.  The one sub-module that is not provided is refget: importing it raises
-ModuleNotFoundError, not a silent stub.  ``gtars.igd``, ``gtars.scoring`` and ``gtars.fragsplit`` are additive (the
+nothing beyond region sets.  The one sub-module that is not provided under this name is refget: importing ``gtars.refget``
+raises ModuleNotFoundError, not a silent stub; the module lives in ``gtars_amd.refget`` (registering the alias is a follow-up).
+``gtars.igd``, ``gtars.scoring`` and ``gtars.fragsplit`` are additive (the
 reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats`` is additive too: it holds
 ``GenomeAssembly``, ``BinaryGenomeAssembly``, ``calc_gc_content`` and ``calc_dinucl_freq``, which the reference keeps in
 ``gtars.models`` and ``gtars.genomic_distributions``; ``gtars.signal`` likewise holds ``SignalMatrix`` and

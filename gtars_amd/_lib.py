@@ -119,6 +119,8 @@ _SIG = {
     "gtars_igd_count_per_query": (C.c_int, [vp, vp, vp, vp, u64, i32, vp]),
     "gtars_igd_find_pairs": (C.c_int, [vp, vp, vp, vp, u64, i32, pp, pp, pu64]),
     "gtars_lola_contingency_device": (C.c_int, [vp, vp, u64, i64, i64, vp, vp, vp, vp, vp]),
+    "gtars_refget_digests_device": (C.c_int, [vp, vp, vp, vp, vp]),
+    "gtars_refget_substrings_device": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp, u64, pu64, vp]),
     "gtars_prof_enable": (None, [C.c_int]),
     "gtars_prof_reset": (None, []),
     "gtars_prof_read": (C.c_int, [vp, vp, vp, C.c_int]),
@@ -367,6 +369,21 @@ _HOST_SIG = {
     "gtars_hgvs_resolve": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, u64, u32, vp]),
     "gtars_hgvs_to_vrs": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, u64, vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp]),
     "gtars_hgvs_ids_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gtars_md5": (C.c_int, [vp, u64, vp]),
+    "gtars_refget_alphabet": (C.c_int, [vp, u64]),
+    "gtars_refget_class_table": (None, [vp]),
+    "gtars_refget_host_len": (u32, []),
+    "gtars_seqcol_from_fasta": (C.c_int, [cstr, C.c_int, u32, pp]),
+    "gtars_seqcol_from_fasta_bytes": (C.c_int, [vp, u64, C.c_int, u32, pp]),
+    "gtars_seqcol_free": (None, [vp]),
+    "gtars_seqcol_len": (u64, [vp]),
+    "gtars_seqcol_is_gzip": (C.c_int, [vp]),
+    "gtars_seqcol_assembly": (vp, [vp]),
+    "gtars_seqcol_record": (C.c_int, [vp, u64, pp, pp, pu64, C.POINTER(C.c_int), pu64, C.POINTER(u32), C.POINTER(u32), vp, vp,
+                                      C.POINTER(C.c_int), pp]),
+    "gtars_seqcol_digests": (C.c_int, [vp, vp]),
+    "gtars_seqcol_substrings": (C.c_int, [vp, vp, vp, vp, u64, C.c_int, u32, vp, pp, pp]),
+    "gtars_seqcol_digest_records": (C.c_int, [vp, C.c_int, u32, vp, vp, vp]),
 }
 
 # include/gtars_amd_debug.h: test / A-B / diagnostics hooks, not part of the drop-in boundary

@@ -384,6 +384,34 @@ gtars_status gtars_lola_contingency_device(const uint64_t *d_user_hits,
                                            void *stream);
 
 /* ------------------------------------------------------------------------
+ * K21, refget on resident columns (csrc/refget.hip).  A gtars_seqcol_t is a
+ * sequence collection read with its sequence data (include/gtars_amd_host.h);
+ * its packed device image is built at the first call, on the device current
+ * then, and every later call must run on that device.  Both calls are queued
+ * on `stream`, which is drained before they return.
+ * digests: per record, in the collection's order, the 32 characters of
+ * sha512t24u (d_digests, 8-byte aligned), the 16 MD5 bytes (d_md5, 8-byte
+ * aligned) and the alphabet class 0 .. 4 (d_class) of the upper-cased
+ * sequence; any of the three may be NULL.
+ * substrings: row i asks for bytes [d_start[i], d_end[i]) of record d_seq[i]
+ * (2^32 - 1: a sequence the collection lacks).  d_status[i]: 0 ok, 1 no such
+ * sequence, 2 bad range (start == end is the empty string wherever it lies;
+ * otherwise start < end, start < length and end <= length), 3 wider than
+ * 2^32 - 1 bytes.  d_offsets[n + 1] and d_bytes (8-byte aligned, `cap` bytes):
+ * the upper-cased bytes of the rows as a CSR, no bytes for a row that failed.
+ * *total: the bytes needed; above `cap` the call is GTARS_ERR_CAPACITY
+ * ("need N") with the statuses and offsets written and no bytes.
+ * ---------------------------------------------------------------------- */
+typedef struct gtars_seqcol gtars_seqcol_t;
+gtars_status gtars_refget_digests_device(gtars_seqcol_t *c, char *d_digests, uint8_t *d_md5,
+                                         uint8_t *d_class, void *stream);
+gtars_status gtars_refget_substrings_device(gtars_seqcol_t *c, const uint32_t *d_seq,
+                                            const uint64_t *d_start, const uint64_t *d_end,
+                                            uint64_t n, uint8_t *d_status, uint64_t *d_offsets,
+                                            uint8_t *d_bytes, uint64_t cap, uint64_t *total,
+                                            void *stream);
+
+/* ------------------------------------------------------------------------
  * Instrumentation used by bench.py: when enabled every kernel launch made by
  * this library on the calling thread is bracketed by HIP events on its own
  * stream; gtars_prof_read() synchronises and returns accumulated times.

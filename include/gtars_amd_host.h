@@ -966,6 +966,49 @@ gtars_status gtars_hgvs_ids_device(gtars_txbind_t *b, const gtars_hgvs_columns *
                                    uint8_t *d_detail, uint8_t *d_warnings, uint32_t *d_chrom, uint64_t *d_start, uint64_t *d_end,
                                    char *d_digests, void *stream);
 
+/* ---- K21: refget (gtars-refget/src/digest, store/readonly.rs; csrc/refget.cpp, csrc/refget.hip) -------------------------
+ * Scalar calls, host code: md5 gives 32 lower-case hex characters and a NUL; alphabet the class of n bytes read upper-cased
+ * (0 dna2bit, 1 dna3bit, 2 dnaio, 3 protein, 4 ASCII; no bytes: dna2bit); class_table the class of every byte value;
+ * host_len the GTARS_REFGET_HOST_LEN in force (records longer than this are hashed on the host threads, default 65536).
+ *
+ * A gtars_seqcol_t holds the records of one FASTA text in file order -- plain or gzip by the magic bytes; text before the
+ * first '>' is ignored; the name is the first whitespace-delimited token of the trimmed header, the description the trimmed
+ * rest; a sequence line is a line that is not blank, without its trailing ASCII whitespace; a repeated name stays a record
+ * of its own.  flags: GTARS_SEQCOL_KEEP_BYTES keeps the sequence data (needed by every call below `digests`),
+ * GTARS_SEQCOL_ON_HOST hashes on `threads` host threads (0 = gtars_host_threads) instead of the device,
+ * GTARS_SEQCOL_NO_DIGESTS reads names, lengths and FAI data only (no device either).  Without ON_HOST and NO_DIGESTS the
+ * records up to host_len bytes are hashed on the current device from an image of those records alone, the longer ones on
+ * the host threads meanwhile (GTARS_ERR_NO_DEVICE without a device).
+ * record: the strings live as long as the handle; *description NULL without one; FAI data as samtools faidx has them
+ * (*has_fai 0 for a record without a sequence line and for gzip input); sha33 / md5_33 empty and *alphabet 5 without
+ * digests; *bytes the record's bytes as the file has them (not upper-cased), NULL when they were not kept.
+ * digests: seven times 32 characters and a NUL -- the collection digest, the level-1 digests names, sequences, lengths and
+ * the ancillary name_length_pairs, sorted_name_length_pairs, sorted_sequences (types.rs:204-347).
+ * assembly: an assembly over the kept bytes with one entry per record, owned by the collection (NULL without bytes).
+ * substrings: as gtars_refget_substrings_device for host columns; *offsets (n + 1) and *bytes: gtars_free.  on_host != 0:
+ * the library's host path, no device.  digest_records: the per-record digests again from the kept bytes, through the
+ * collection's full device image (or on the host): n * 32 characters, n * 16 MD5 bytes, n classes, any may be NULL. */
+#define GTARS_SEQCOL_KEEP_BYTES 1
+#define GTARS_SEQCOL_ON_HOST 2
+#define GTARS_SEQCOL_NO_DIGESTS 4
+gtars_status gtars_md5(const void *data, uint64_t n, char *out33);
+int gtars_refget_alphabet(const void *data, uint64_t n);
+void gtars_refget_class_table(uint8_t *out256);
+uint32_t gtars_refget_host_len(void);
+gtars_status gtars_seqcol_from_fasta(const char *path, int flags, uint32_t threads, gtars_seqcol_t **out);
+gtars_status gtars_seqcol_from_fasta_bytes(const void *text, uint64_t n, int flags, uint32_t threads, gtars_seqcol_t **out);
+void gtars_seqcol_free(gtars_seqcol_t *c);
+uint64_t gtars_seqcol_len(const gtars_seqcol_t *c);
+int gtars_seqcol_is_gzip(const gtars_seqcol_t *c);
+gtars_assembly_t *gtars_seqcol_assembly(gtars_seqcol_t *c);
+gtars_status gtars_seqcol_record(const gtars_seqcol_t *c, uint64_t i, const char **name, const char **description, uint64_t *length,
+                                 int *has_fai, uint64_t *fai_offset, uint32_t *line_bases, uint32_t *line_bytes, char *sha33, char *md5_33,
+                                 int *alphabet, const uint8_t **bytes);
+gtars_status gtars_seqcol_digests(const gtars_seqcol_t *c, char *out7x33);
+gtars_status gtars_seqcol_substrings(gtars_seqcol_t *c, const uint32_t *seq, const uint64_t *start, const uint64_t *end, uint64_t n, int on_host,
+                                     uint32_t threads, uint8_t *status, uint64_t **offsets, uint8_t **bytes);
+gtars_status gtars_seqcol_digest_records(gtars_seqcol_t *c, int on_host, uint32_t threads, char *digests, uint8_t *md5, uint8_t *alphabet);
+
 #ifdef __cplusplus
 }
 #endif
