@@ -31,6 +31,7 @@
 #include "common.h"
 #include "scan.h"
 
+#include <cstring>
 #include <mutex>
 
 namespace gtars {
@@ -100,6 +101,22 @@ __device__ __forceinline__ bool wave_full(u64 q0, u64 nq, int lane) { return q0 
 #ifndef GTARS_TOK_LB_W1
 #define GTARS_TOK_LB_W1 1  // look-back windows per round in one-tile-per-group launches (see resolve_prefix_helping)
 #endif
+// How the prefix travels between the workgroups of a one-tile-per-workgroup launch (k_tok_lds<.., ONE>, at most TOK_LB_ROW tiles,
+// all publishing and all looking back at about the same time; A/B and the dropped arm: profiles/tok_lookback/ab.txt):
+//   0 chain     the chained look-back on ScanWs::state[], as the pipelined launches run it: every workgroup polls and stores into
+//               the same sixteen 128-byte lines
+//   1 replicas  the same algorithm on TOK_LB_REPL copies of the state array, each on lines of its own: a granule is stored into every
+//               copy by ONE wave instruction (lane r: copy r), and tile i reads copy i % TOK_LB_REPL -- an eighth of the pollers per line
+// GTARS_TOK_LOOKBACK=chain|replicas selects at run time (tests, A/B).
+#ifndef GTARS_TOK_LOOKBACK
+#define GTARS_TOK_LOOKBACK 1
+#endif
+constexpr u32 LB_CHAIN = 0, LB_REPLICAS = 1;
+constexpr u32 TOK_LB_ROW = 256;      // granules per copy (2 KiB): the most tiles a launch on the copies may have
+constexpr u32 TOK_LB_REPL = 8;
+constexpr size_t TOK_LB_OFF = 2304;  // byte offset of copy 0 in the scan workspace (a multiple of 128): behind a one-tile launch's own state[]
+static_assert(TOK_LB_OFF % 128 == 0 && TOK_LB_OFF >= sizeof(ScanWs) + TOK_LB_ROW * sizeof(u64), "the copies start on a line of their own");
+constexpr size_t TOK_LB_BYTES = (size_t)TOK_LB_REPL * TOK_LB_ROW * sizeof(u64);  // 16 KiB
 #ifndef GTARS_TOK_KEYS_U16
 #define GTARS_TOK_KEYS_U16 1  // the in-bucket keys by eight 2-byte reads instead of one 16-byte read at a 2-byte-aligned address (1-2 % at the 100k universe)
 #endif
@@ -1042,11 +1059,15 @@ __device__ __forceinline__ u64 help_count_tile(const AccelView &a, const SearchL
 // W = 1 everywhere: wider rounds measured SLOWER both for launches whose groups take many tiles (558 / 600 / 615 / 672 us per
 // 64M queries for W = 1 / 2 / 4 / 8) and for one-tile-per-workgroup launches, where all <= 256 tiles publish at about the same
 // time (16.5 / 17.3 / 18.4 us per 1M queries for W = 1 / 2 / 4 when every round re-reads all W windows, 16.5 / 16.6 / 17.3 when only
-// the incomplete window is polled again): the look-back of a 1M-query launch is the wait for the slowest predecessor
-// workgroup, not a chain of round trips (profiles/r03/README.md).
-template <int W, class Help>
+// the incomplete window is polled again): the look-back of a 1M-query launch is no chain of round trips (profiles/r03/README.md).
+// Nor is it only the wait for the slowest predecessor workgroup, as these lines once said: a good half of it is the traffic of 245
+// polling waves and 490 stores on the sixteen lines of one state array (profiles/tok_lookback: 17.22 us chain, 16.03 us on eight
+// copies, 15.05 us with no look-back at all).
+// REPL > 1 (one-tile launches, GTARS_TOK_LOOKBACK=replicas): `state` is the copy this tile READS, `all` copy 0 of REPL copies, each
+// TOK_LB_ROW granules long; every granule is stored into all of them by one wave instruction (lane r: copy r).
+template <int W, int REPL = 1, class Help>
 __device__ __forceinline__ u64 resolve_prefix_helping(u64 *state, u32 tile, u64 agg, int lane, u32 epoch, u32 spin_limit,
-                                                      u64 base, Help &&help) {
+                                                      u64 base, Help &&help, u64 *all = nullptr) {
     const u64 ep = (u64)epoch << EP_SHIFT;
     u64 part = 0;  // this lane's share of the exclusive prefix
     i64 pred = (i64)tile - 1;
@@ -1088,7 +1109,11 @@ __device__ __forceinline__ u64 resolve_prefix_helping(u64 *state, u32 tile, u64 
                 if (++spins > spin_limit) {
                     const i64 missing = pred - 64 * w - (__ffsll((long long)(b_inv & need)) - 1);
                     const u64 h = help((u32)missing) + (missing == 0 ? base : 0ull);
-                    if (lane == 0) st_state(&state[missing], (missing == 0 ? ST_INC : ST_AGG) | ep | h);
+                    if constexpr (REPL == 1) {
+                        if (lane == 0) st_state(&state[missing], (missing == 0 ? ST_INC : ST_AGG) | ep | h);
+                    } else {
+                        if (lane < REPL) st_state(&all[(size_t)lane * TOK_LB_ROW + missing], (missing == 0 ? ST_INC : ST_AGG) | ep | h);
+                    }
                     spins = 0;
                 } else {
                     __builtin_amdgcn_s_sleep(1);
@@ -1101,7 +1126,11 @@ __device__ __forceinline__ u64 resolve_prefix_helping(u64 *state, u32 tile, u64 
     }
     // `base`: what precedes tile 0 (chained launches); later tiles get it through tile 0's inclusive prefix
     const u64 excl = wave_reduce_sum_u48(part) + (tile == 0 ? base : 0ull);
-    if (lane == 0) st_state(&state[tile], ST_INC | ep | (excl + agg));
+    if constexpr (REPL == 1) {
+        if (lane == 0) st_state(&state[tile], ST_INC | ep | (excl + agg));
+    } else {
+        if (lane < REPL) st_state(&all[(size_t)lane * TOK_LB_ROW + tile], ST_INC | ep | (excl + agg));
+    }
     return excl;
 }
 
@@ -1128,9 +1157,11 @@ __global__ void __launch_bounds__(TPB, TPB / 256)
 k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, const u32 *__restrict__ qe,
           u64 nq, i32 min_bp, u64 *__restrict__ offsets, u32 *__restrict__ ovals, u64 cap, ScanWs *ws,
           u32 epoch, u32 ticket_base, u32 stage_cap, u32 spin_limit, const u64 *__restrict__ d_base,
-          u64 *__restrict__ d_total_out) {
+          u64 *__restrict__ d_total_out, u32 lb) {
     extern __shared__ __attribute__((aligned(16))) u32 smem[];
     constexpr int NW = TPB / 64, GW = NW / G;  // waves per workgroup / per group
+    // (lb: the look-back form of a one-tile launch, LB_*; the copies of the state array lie in the workspace behind state[])
+    u64 *const lb_copies = reinterpret_cast<u64 *>(reinterpret_cast<char *>(ws) + TOK_LB_OFF);
     static_assert(GW * R <= 64, "one lane per wave part in the group's scan");
     __shared__ u32 s_tile[G];
     __shared__ u64 s_prefix[G];
@@ -1254,7 +1285,11 @@ k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, c
                 cur.q[r].excl = inc[r] - tsum[r];
             }
             cur.tile = tile;
-            if (gtid == 0) publish_aggregate(ws->state, tile, (u64)cur.total + (tile == 0 ? base : 0ull), epoch);
+            if (ONE && lb == LB_REPLICAS) {  // (published by the wave that polls, before its first poll)
+                if (gtid < TOK_LB_REPL)
+                    publish_aggregate(lb_copies + (size_t)gtid * TOK_LB_ROW, tile, (u64)cur.total + (tile == 0 ? base : 0ull), epoch);
+            } else if (gtid == 0)
+                publish_aggregate(ws->state, tile, (u64)cur.total + (tile == 0 ? base : 0ull), epoch);
         }
         // resolve + write the PREVIOUS tile.  Round 0's ids are staged in LDS before the base is known: by waves 1.. while
         // wave 0 looks back, by wave 0 right after.
@@ -1264,10 +1299,15 @@ k_tok_lds(AccelView a, const u32 *__restrict__ qc, const u32 *__restrict__ qs, c
         if (have_prev && gwave != 0)
             pre0 = stage_queries<QPT, FILTER, IMPL, REV, RUNS, U64>(a, L, qc, qs, qe, min_bp, prev.q[0], prev_q0, cap, stage, stage_cap, orel0);
         if (have_prev && gwave == 0) {
-            const u64 excl = (GTARS_TOK_ABLATE & 1) ? (u64)prev.tile * 2400u
-                                                    : (draw ? resolve_prefix_helping<1>(ws->state, prev.tile, (u64)prev.total, lane, epoch, spin_limit, base, help)
-                                                            : resolve_prefix_helping<GTARS_TOK_LB_W1>(ws->state, prev.tile, (u64)prev.total, lane, epoch,
-                                                                                                      spin_limit, base, help));
+            u64 excl;
+            if (GTARS_TOK_ABLATE & 1)
+                excl = (u64)prev.tile * 2400u;
+            else if (ONE && lb == LB_REPLICAS)
+                excl = resolve_prefix_helping<GTARS_TOK_LB_W1, (int)TOK_LB_REPL>(lb_copies + (size_t)(prev.tile % TOK_LB_REPL) * TOK_LB_ROW, prev.tile,
+                                                                                 (u64)prev.total, lane, epoch, spin_limit, base, help, lb_copies);
+            else
+                excl = draw ? resolve_prefix_helping<1>(ws->state, prev.tile, (u64)prev.total, lane, epoch, spin_limit, base, help)
+                            : resolve_prefix_helping<GTARS_TOK_LB_W1>(ws->state, prev.tile, (u64)prev.total, lane, epoch, spin_limit, base, help);
             if (lane == 0) {
                 s_prefix[grp] = excl;
                 if (prev.tile == num_tiles - 1) {
@@ -2058,9 +2098,19 @@ static int choose_groups(u64 nq, int cus) {
     return nq >= (u64)cus * 8192ull * 4ull ? 2 : 1;
 }
 
+// the look-back form of one-tile launches (LB_*)
+static u32 tok_lookback_mode() {
+    const char *v = cfg_get("GTARS_TOK_LOOKBACK");
+    if (v && !strcmp(v, "chain")) return LB_CHAIN;
+    if (v && !strcmp(v, "replicas")) return LB_REPLICAS;
+    return GTARS_TOK_LOOKBACK;
+}
+
 size_t tokenize_lds_ws_bytes(u64 nq) {
-    // sized for the smallest tile (k_tok_sweep: 256 threads x 4 queries)
-    return scan_ws_bytes_for_tiles((nq + 1023) / 1024);
+    // sized for the smallest tile (k_tok_sweep: 256 threads x 4 queries), and never less than a one-tile launch's copies of its state
+    // array.  (A caller that allocates a fresh workspace for every call pays for them in the memset that clears a new workspace:
+    // 18.25 KiB at the least instead of a few hundred bytes for a small batch.)
+    return std::max(scan_ws_bytes_for_tiles((nq + 1023) / 1024), TOK_LB_OFF + TOK_LB_BYTES);
 }
 
 // words of id staging per wave: what is left of the LDS budget, at most 512 (a wave-tile of 256 queries rarely has more hits)
@@ -2093,8 +2143,11 @@ static gtars_status launch_tok_t(const AccelView &a, const u32 *qc, const u32 *q
         if (tiles > grid * G) return launch_tok_t<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64, false>(a, qc, qs, qe, nq, min_bp, out, ws, ep, d_base, d_total_out, st);
     }
     const u64 cap = out.vals ? out.capacity : 0;
+    // (a device with more workgroups than a copy has granules: the chain)
+    const u32 lb = ONE && tiles <= TOK_LB_ROW ? tok_lookback_mode() : LB_CHAIN;
+    if (ONE) prof_note_fact(lb == LB_REPLICAS ? "tok_lookback_replicas" : "tok_lookback_chain");
     hipLaunchKernelGGL((k_tok_lds<TPB, QPT, R, G, FILTER, IMPL, REV, RUNS, U64, ONE>), dim3((unsigned)grid), dim3(TPB), lds, st, a, qc, qs, qe, nq,
-                       min_bp, out.offsets, out.vals, cap, ws, ep.epoch, ep.ticket_base, stage, spin_limit, d_base, d_total_out);
+                       min_bp, out.offsets, out.vals, cap, ws, ep.epoch, ep.ticket_base, stage, spin_limit, d_base, d_total_out, lb);
     GT_HIP(hipGetLastError());
     // tickets drawn by this launch: one per tile beyond the first `grid * G`, plus one failing draw per group
     if (tiles > grid * G) ep.ticket_base += (u32)tiles;
@@ -2175,7 +2228,10 @@ gtars_status launch_tokenize_lds(const AccelView &a, const u32 *qc, const u32 *q
     const u64 tile_q = tok_tile_queries(TPB / groups, 4 * rounds);
     const u64 tiles = (nq + tile_q - 1) / tile_q;
     if (tiles > 0xFFFFFFF0ull) return fail(GTARS_ERR_INVALID_ARG, "query batch too large for one launch");
-    const size_t need = scan_ws_bytes_for_tiles(tiles);
+    const bool one = rounds == 1 && groups == 1 && tiles <= (u64)cus;  // (launch_tok_t: grid = min(CUs, tiles))
+    // (a one-tile launch's copies of the state array lie behind its state[]; what an earlier pipelined launch's state[] left there is
+    // stale by its epoch, and so is what the copies leave in a later pipelined launch's state[])
+    const size_t need = std::max(scan_ws_bytes_for_tiles(tiles), one ? TOK_LB_OFF + TOK_LB_BYTES : (size_t)0);
     if (scan_ws_bytes < need) return fail(GTARS_ERR_INTERNAL, "fused scan workspace too small");
     // The workspace is cleared only when it is new (ep.epoch == 0), when it has to grow past what
     // was cleared, or when the 14-bit epoch wraps; otherwise stale granules are told apart by epoch.
@@ -2189,7 +2245,6 @@ gtars_status launch_tokenize_lds(const AccelView &a, const u32 *qc, const u32 *q
     const i32 min_bp = has_min ? min_overlap : 0;
     ScanWs *ws = (ScanWs *)scan_ws;
     if (!impl && !a.rec4) return fail(GTARS_ERR_INTERNAL, "index has no id records");
-    const bool one = rounds == 1 && groups == 1 && tiles <= (u64)cus;  // (launch_tok_t: grid = min(CUs, tiles))
     ProfScope p("k_tok_lds", st);
 #define GT_TOK_CASE(N, GG, F, I, V, W)                                                                                      \
     if (rounds == N && groups == GG && filter == F && impl == I && reverse == V && wide == (W != 0))                        \
