@@ -206,20 +206,19 @@ def test_every_switch_meets_the_definitions(ga, monkeypatch, switch):
 
 
 @pytest.mark.parametrize("kind", BOTH)
-def test_sweep_form_on_batches_in_order(ga, monkeypatch, kind):
-    """GTARS_TOK_SWEEP on batches sorted by (chromosome, start): k_tok_sweep, forward (Bits) and reversed (a flat AIList)"""
-    monkeypatch.setenv("GTARS_TOK_SWEEP", "1")
+def test_sweep_form_on_batches_in_order(ga, kind):
+    """batches sorted by (chromosome, start), once the sweep form's: k_tok_lds, forward (Bits) and reversed (a flat AIList)"""
     for explicit_ids in (False, True):
         m, h = disjoint_model(kind, explicit_ids, 6000, True, True)
-        facts = run_case(ga, disjoint(explicit_ids), m, h, kind, f"sweep: disjoint ids={explicit_ids}", **SHORT)
-        assert "tok_build_sweep" in facts and "k_tok_sweep" in facts, facts
+        facts = run_case(ga, disjoint(explicit_ids), m, h, kind, f"in order: disjoint ids={explicit_ids}", **SHORT)
+        assert "k_tok_lds" in facts and "tok_build_sweep" not in facts and "k_tok_sweep" not in facts, facts
     if kind == KIND_BITS:
         d = case("mid")
         o = np.lexsort((d["qs"], d["qc"]))
         m, _ = model_of("mid", kind)
         h = m.query(d["qc"][o], d["qs"][o], d["qe"][o])
-        facts = run_case(ga, d, m, h, kind, "sweep: mid in order", **SHORT)
-        assert "tok_build_sweep" in facts, facts
+        facts = run_case(ga, d, m, h, kind, "in order: mid", **SHORT)
+        assert "k_tok_lds" in facts and "tok_build_sweep" not in facts, facts
 
 
 # ------------------------------------------------------------- query counts at the tile's edges

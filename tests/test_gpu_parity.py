@@ -2334,8 +2334,8 @@ def _tok_device(ga, g, qc, qs, qe, hint, cap_factor=6):
 
 
 def sweep_cases(ga, rng, kind, explicit_ids):
-    """the universes and in-order batches of the sweep tokenizer's tests, one after the other (the caller may draw from rng
-    between two of them) -> (n, g, oracle index, (qc, qs, qe), id-buffer factor)"""
+    """the universes and in-order batches of the sorted hint's tests (once the sweep tokenizer's), one after the other (the caller
+    may draw from rng between two of them) -> (n, g, oracle index, (qc, qs, qe), id-buffer factor)"""
     for n, n_chrom, span, wmax, qwmax, nq in ((60_000, 5, 4_000_000, 400, 600, 70_000), (3_000, 40, 100_000, 90, 200, 30_000),
                                               (400_000, 3, 60_000_000, 300, 500, 50_000), (20_000, 2, 1_000_000, 3000, 40_000, 20_000)):
         c = np.sort(rng.integers(0, n_chrom, n)).astype(np.uint32)
@@ -2354,13 +2354,13 @@ def sweep_cases(ga, rng, kind, explicit_ids):
 
 @pytest.mark.parametrize("kind", BOTH)
 @pytest.mark.parametrize("explicit_ids", [False, True])
-def test_sweep_tokenizer_on_batches_in_order(ga, monkeypatch, kind, explicit_ids):
-    """Round 6: GTARS_TOK_SORTED -- the sweep form of the tokenizer (k_tok_sweep) for batches in (chromosome, start) order, what a
-    file-loaded RegionSet is (region_set.rs:182, 502-505).  Same offsets and ids as Bits::find / AIList::find (bits.rs:141-156,
-    433-446; ailist.rs:238-263) and as the default kernel, on: disjoint and overlapping universes with position-derived and
-    explicit ids, several tiles with chromosome boundaries inside tiles (two and more runs per tile), unknown chromosomes
-    inside the batch, zero-length and wide queries (hits beyond the 32-interval mask: the global walk), a universe far beyond
-    k_tok_lds' LDS key budget, min-overlap filters, an id buffer that is too short (offsets complete, GTARS_ERR_CAPACITY)."""
+def test_sweep_tokenizer_on_batches_in_order(ga, kind, explicit_ids):
+    """GTARS_TOK_SORTED on batches in (chromosome, start) order, what a file-loaded RegionSet is (region_set.rs:182, 502-505).  The
+    hint is accepted and ignored (the sweep form it once selected was removed): the default kernel serves the batch -- k_tok_lds,
+    or k_enum_fused where the index has no blocked structure.  Same offsets and ids as Bits::find / AIList::find (bits.rs:141-156,
+    433-446; ailist.rs:238-263), on: disjoint and overlapping universes with position-derived and explicit ids, several tiles with
+    chromosome boundaries inside tiles, unknown chromosomes inside the batch, zero-length and wide queries, a universe of 400k
+    regions, the same batch shuffled, an id buffer that is too short (offsets complete, GTARS_ERR_CAPACITY)."""
     rng = np.random.default_rng(17 + kind)
     for n, g, o_, (qc, qs, qe), cap_factor in sweep_cases(ga, rng, kind, explicit_ids):
         nq = len(qc)
@@ -2371,27 +2371,21 @@ def test_sweep_tokenizer_on_batches_in_order(ga, monkeypatch, kind, explicit_ids
         off, ids = _tok_device(ga, g, qc, qs, qe, g.TOK_SORTED, cap_factor=cap_factor)
         prof = _lib.prof_read()
         _lib.lib.gtars_prof_enable(0)
-        if kind == KIND_BITS or "tok_build_sweep" in prof:  # (a nested AIList universe has no blocked structure: generic kernel)
-            assert "tok_build_sweep" in prof, sorted(prof)
+        assert "tok_build_sweep" not in prof and "k_tok_sweep" not in prof, sorted(prof)
+        if kind == KIND_BITS:
+            assert "k_tok_lds" in prof, sorted(prof)
+        else:  # (a nested AIList universe has no blocked structure: generic kernel)
+            assert "k_tok_lds" in prof or "k_enum_fused<ailist>" in prof, sorted(prof)
         assert np.array_equal(off, want_off), (n, np.argwhere(off != want_off)[:3])
         assert np.array_equal(ids, want_ids), (n, np.argwhere(ids != want_ids)[:3])
         off2, ids2 = _tok_device(ga, g, qc, qs, qe, g.TOK_AUTO, cap_factor=cap_factor)
         assert np.array_equal(off2, want_off) and np.array_equal(ids2, want_ids)
-        # the same batch SHUFFLED under the hint: still right (many runs per tile -> the global path)
+        # the same batch SHUFFLED under the hint: still right
         p = rng.permutation(nq)[: 6000]
         w_off, w_ids = o_.tokenize(qc[p], qs[p], qe[p])
         off3, ids3 = _tok_device(ga, g, qc[p], qs[p], qe[p], g.TOK_SORTED, cap_factor=cap_factor)
         assert np.array_equal(off3, w_off) and np.array_equal(ids3, w_ids)
-    # forced small budgets: 8 staged blocks per wave (every run beyond -> global memory), one run per wave and round (the second
-    # run -> global memory), none; two rounds per tile on a batch this small
-    for env, val_ in (("GTARS_TOK_SWEEP_BLOCKS", "8"), ("GTARS_TOK_SWEEP_RUNS", "1"), ("GTARS_TOK_SWEEP_RUNS", "0"),
-                      ("GTARS_TOK_SWEEP_ROUNDS", "2")):
-        monkeypatch.setenv(env, val_)
-        off5, ids5 = _tok_device(ga, g, qc, qs, qe, g.TOK_SORTED, cap_factor=cap_factor)
-        monkeypatch.delenv(env)
-        assert np.array_equal(off5, want_off) and np.array_equal(ids5, want_ids), env
-    # min-overlap filter through count_overlaps is another kernel; the tokenizer's filter form through find_overlaps' values
-    # is covered by the fuzzer (GTARS_TOK_SWEEP=1); here: an id buffer that is too short
+    # an id buffer that is too short
     import torch
 
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -2407,8 +2401,8 @@ def test_sweep_tokenizer_on_batches_in_order(ga, monkeypatch, kind, explicit_ids
 
 
 def test_sweep_tokenizer_config2_in_order_and_large_universes(ga):
-    """BASELINE config 2's batch in (chromosome, start) order through the sweep form: ids AND order == oracle at 1M queries; then
-    universes of 200k and 1M regions (beyond the LDS key image of the default kernel), same batch law, in order."""
+    """BASELINE config 2's batch in (chromosome, start) order under the sorted hint (accepted, no effect: the default kernel): ids AND
+    order == oracle at 1M queries; then universes of 200k and 1M regions, same batch law, in order."""
     from gtars_amd import synth
 
     for nu in (100_000, 200_000, 1_000_000):

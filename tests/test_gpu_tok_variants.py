@@ -1,6 +1,6 @@
 """The fused tokenizer's switchable forms against the CPU oracle, bit-exact: the redo of a batch by the generic kernel after a
 look-back timeout (GTARS_TEST_FORCE_LOOKBACK_TIMEOUT), the id staging of a wave on both sides of its threshold
-(GTARS_TOK_STAGE), and the sweep form with 1024-thread workgroups (GTARS_TOK_SWEEP_TPB) or switched off (GTARS_TOK_NO_SWEEP).
+(GTARS_TOK_STAGE), and the sorted hint (GTARS_TOK_SORTED), which is accepted and changes nothing.
 Which kernel a call ran is read from the profiler's kernel names and facts, never assumed."""
 import numpy as np
 import pytest
@@ -236,60 +236,13 @@ def test_id_staging_on_both_sides_of_its_threshold(ga, monkeypatch, stage_inputs
                 _assert_capacity_rule(res, cap, off_o, ids_o, (variant, stage_env, name, STAGE_BLOCKS[block], stage, total, cap))
 
 
-# ------------------------------------------------------------------------------------------------------- the sweep forms
-
-def _ids_follow_from_position(g):
-    """the index's stored ids ascend by one inside every chromosome (api.hip: acc_ids_affine -- such an index has no id records)"""
-    c = seen = 0
-    while seen < len(g):
-        v = g.stored(c)[2].astype(np.int64)
-        if len(v) and not np.array_equal(v - v[0], np.arange(len(v))):
-            return False
-        seen += len(v)
-        c += 1
-    return True
-
+# ------------------------------------------------------------------------------------------------------- the sorted hint
 
 @pytest.mark.parametrize("explicit_ids", [False, True])
-def test_sweep_tokenizer_with_1024_thread_workgroups(ga, monkeypatch, explicit_ids):
-    """GTARS_TOK_SWEEP_TPB=1024: launch_sweep_t<1024, 1 | 2, ...> on the batches of test_sweep_tokenizer_on_batches_in_order.  The
-    launcher takes 1024 threads only for unfiltered, forward launches on an index whose ids follow from the position: the three
-    disjoint universes without explicit ids (the fourth universe overlaps, equal starts with unordered ends: Bits order is not
-    the input order and the index carries id records).  That it did is read from the fact the launcher notes -- and that it
-    did not for the others, where the 256-thread form must still be right under the switch.  Both rounds-per-tile forms."""
+def test_sorted_hint_without_the_sweep_form(ga, explicit_ids):
+    """A batch given with the sorted hint goes to k_tok_lds (or, for a universe beyond its LDS key budget, to the generic kernel)
+    and equals the oracle; no sweep kernel runs (the form the hint once selected was removed)."""
     rng = np.random.default_rng(17 + KIND_BITS)
-    monkeypatch.setenv("GTARS_TOK_SWEEP_TPB", "1024")
-    ran_1024 = 0
-    for n, g, o_, (qc, qs, qe), cap_factor in sweep_cases(ga, rng, KIND_BITS, explicit_ids):
-        implicit = _ids_follow_from_position(g)
-        assert implicit == (not explicit_ids and n != 20_000), (n, explicit_ids)
-        ran_1024 += implicit
-        want_off, want_ids = o_.tokenize(qc, qs, qe)
-        for rounds in (None, "2"):
-            if rounds:
-                monkeypatch.setenv("GTARS_TOK_SWEEP_ROUNDS", rounds)
-            (off, ids), prof = _profiled(ga, lambda: _tok_device(ga, g, qc, qs, qe, g.TOK_SORTED, cap_factor=cap_factor))
-            if rounds:
-                monkeypatch.delenv("GTARS_TOK_SWEEP_ROUNDS")
-            assert "tok_build_sweep" in prof and "k_tok_sweep" in prof, sorted(prof)
-            assert ("tok_sweep_tpb1024" in prof) == implicit, (n, rounds, sorted(prof))
-            assert np.array_equal(off, want_off), (n, rounds, np.argwhere(off != want_off)[:3])
-            assert np.array_equal(ids, want_ids), (n, rounds, np.argwhere(ids != want_ids)[:3])
-        # an id buffer that is too short, 1024 threads
-        d = _to_device(qc, qs, qe)
-        cap = max(len(want_ids) // 3, 1)
-        res, prof = _profiled(ga, lambda: _tokenize_with_capacity(ga, g, d, cap, len(want_ids), hint=g.TOK_SORTED))
-        assert ("tok_sweep_tpb1024" in prof) == implicit, sorted(prof)
-        _assert_capacity_rule(res, cap, want_off, want_ids, (n, "capacity"))
-    assert ran_1024 == (0 if explicit_ids else 3)
-
-
-@pytest.mark.parametrize("explicit_ids", [False, True])
-def test_sorted_hint_without_the_sweep_form(ga, monkeypatch, explicit_ids):
-    """GTARS_TOK_NO_SWEEP=1: a batch given with the sorted hint goes to k_tok_lds (or, for a universe beyond its LDS key budget,
-    to the generic kernel) and equals the oracle all the same; the sweep kernel does not run."""
-    rng = np.random.default_rng(17 + KIND_BITS)
-    monkeypatch.setenv("GTARS_TOK_NO_SWEEP", "1")
     ran = set()
     for n, g, o_, (qc, qs, qe), cap_factor in sweep_cases(ga, rng, KIND_BITS, explicit_ids):
         want_off, want_ids = o_.tokenize(qc, qs, qe)
@@ -300,6 +253,23 @@ def test_sorted_hint_without_the_sweep_form(ga, monkeypatch, explicit_ids):
         assert np.array_equal(off, want_off), (n, np.argwhere(off != want_off)[:3])
         assert np.array_equal(ids, want_ids), (n, np.argwhere(ids != want_ids)[:3])
     assert "k_tok_lds" in ran, sorted(ran)
+
+
+def test_sorted_hint_changes_nothing(ga, lookback_inputs):
+    """GTARS_TOK_SORTED is accepted and ignored: on every index of lookback_inputs, a call with the hint and one without record
+    the same kernel names and facts, and both return the oracle's offsets and ids."""
+    indexes, batches, _ = lookback_inputs
+    for name, (g, _) in indexes.items():
+        for nq in (3841, 50_001):
+            qc, qs, qe, want = batches[nq]
+            off_o, ids_o = want[name][0]
+            seen = {}
+            for hint in (g.TOK_SORTED, g.TOK_AUTO):
+                (off, ids), prof = _profiled(ga, lambda: _tok_device(ga, g, qc, qs, qe, hint))
+                assert np.array_equal(off, off_o) and np.array_equal(ids, ids_o), (name, nq, hint)
+                seen[hint] = set(prof)
+            assert seen[g.TOK_SORTED] == seen[g.TOK_AUTO], (name, nq, sorted(seen[g.TOK_SORTED] ^ seen[g.TOK_AUTO]))
+            assert "k_tok_lds" in seen[g.TOK_AUTO], (name, nq, sorted(seen[g.TOK_AUTO]))
 
 
 def test_generic_kernels_under_the_ab_switch(ga, monkeypatch, lookback_inputs):
@@ -314,5 +284,5 @@ def test_generic_kernels_under_the_ab_switch(ga, monkeypatch, lookback_inputs):
             off_o, ids_o = want[name][0]
             for hint in (g.TOK_AUTO, g.TOK_SORTED):
                 (off, ids), prof = _profiled(ga, lambda: _tok_device(ga, g, qc, qs, qe, hint))
-                assert enum in prof and "k_tok_lds" not in prof and "k_tok_sweep" not in prof, (name, nq, hint, sorted(prof))
+                assert enum in prof and "k_tok_lds" not in prof, (name, nq, hint, sorted(prof))
                 assert np.array_equal(off, off_o) and np.array_equal(ids, ids_o), (name, nq, hint)

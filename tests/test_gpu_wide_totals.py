@@ -101,7 +101,7 @@ def _forms_a(kind):
     return {
         "default": (0, False, {}, ("tok_build_wide", "k_tok_lds"), (enum, "k_tok_sweep")),
         "narrow": (1, False, {}, ("tok_build_narrow", "k_tok_lds"), (enum, "k_tok_sweep")),
-        "sorted": (4, True, {}, ("tok_build_sweep", "k_tok_sweep"), (enum, "k_tok_lds")),
+        "sorted": (4, True, {}, ("tok_build_wide", "k_tok_lds"), (enum, "k_tok_sweep")),
         "generic": (0, False, {"GTARS_NO_LDS_PATH": "1"}, (enum,), ("k_tok_lds", "k_tok_sweep")),
     }
 
@@ -150,8 +150,8 @@ def test_running_total_crosses_two_to_the_32(ga, monkeypatch, indexes_a, kind, f
     """140 000 queries on a stack of 70 000: full queries (70 000 hits) at the even positions, prefix queries and a few others at
     the odd ones; 7.3e9 hits, the running total passes 2^32 near query 82 000 of 140 000, no tile holds more than 2.3e8 (none of
     the launchers' tile guards is involved).  Count-only, synchronised (*total_hits) and not (offsets[nq]); the default (wide)
-    build, the narrow build, the sweep form on the batch in (chromosome, start) order -- there the 70 000 full queries lie in a
-    row -- and the generic kernel; a Bits index and an AIList index of one sub-list per chromosome (the stack's ends ascend with
+    build, the narrow build, the sorted hint (accepted, no effect: k_tok_lds) on the batch in (chromosome, start) order -- there the
+    70 000 full queries lie in a row -- and the generic kernel; a Bits index and an AIList index of one sub-list per chromosome (the stack's ends ascend with
     its starts: the REV forms)."""
     g = indexes_a(kind)
     if kind == KIND_AILIST:
@@ -185,9 +185,8 @@ def test_running_total_crosses_two_to_the_32_with_coordinates_in_the_upper_half_
 
 # ------------------------------------------------------------------------------ (b) one tile at exactly 2^32 and just past it
 
-# The fewest queries any tokenizer kernel takes as one tile: 256 lanes x 4 queries (k_enum_fused, and k_tok_sweep with 256-thread
-# workgroups).  k_tok_lds' smallest is 512 lanes x 4, the 1024-thread sweep's 1024 x 4 -- but an index one form cannot serve is
-# handed on, in the end to the generic kernel.  A batch may be REFUSED only where even 1024 queries that all hit the densest
+# The fewest queries any tokenizer kernel takes as one tile: 256 lanes x 4 queries (k_enum_fused).  k_tok_lds' smallest is
+# 512 lanes x 4 -- but an index it cannot serve is handed on, in the end to the generic kernel.  A batch may be REFUSED only where even 1024 queries that all hit the densest
 # chromosome could pass 2^32 - 1; every other call answers exactly.
 SMALLEST_TILE = 256 * 4
 
@@ -201,12 +200,9 @@ FORMS_B = {  # form -> (hint, switches)
     "wide g1": (WIDE, {"GTARS_TOK_GROUPS": "1"}),
     "wide g2": (WIDE, {"GTARS_TOK_GROUPS": "2"}),
     "sorted": (SORTED, {}),
-    "sorted r2": (SORTED, {"GTARS_TOK_SWEEP_ROUNDS": "2"}),
-    "sorted tpb1024": (SORTED, {"GTARS_TOK_SWEEP_TPB": "1024"}),
-    "sorted tpb1024 r2": (SORTED, {"GTARS_TOK_SWEEP_TPB": "1024", "GTARS_TOK_SWEEP_ROUNDS": "2"}),
     "generic": (0, {"GTARS_NO_LDS_PATH": "1"}),
 }
-TOKENIZER_KERNELS = ("k_tok_lds", "k_tok_sweep", "k_enum_fused<bits>")
+TOKENIZER_KERNELS = ("k_tok_lds", "k_enum_fused<bits>")
 
 
 def _exact_or_refused(ga, g, d, hint, want, dense, what, also_async=False):
@@ -260,18 +256,18 @@ def batches_b():
     return get
 
 
-# One run of the heavy tile costs a workgroup 1 to 4 s (4.3e9 hits walked by 1024 lanes; measured: k_tok_lds 2.2 s, the 1024-thread
-# sweep 4 s, the generic kernel 0.7 to 2.7 s), so not every form runs at every size.  Each size keeps the default, the narrow and
+# One run of the heavy tile costs a workgroup 1 to 3 s (4.3e9 hits walked by 1024 lanes; measured: k_tok_lds 2.2 s, the generic
+# kernel 0.7 to 2.7 s), so not every form runs at every size.  Each size keeps the default, the narrow and
 # the generic form, and the forms whose tile is the one that size overflows:
-#   524 288 (T = 8192): the 8192-query tiles -- two rounds in one group, the 1024-thread sweep with two rounds;
+#   524 288 (T = 8192): the 8192-query tiles -- two rounds in one group;
 #   1 048 576 (T = 4096, exactly 2^32): one round in one group (4096), which the default (wide) build takes as well;
 #   1 048 577 (T = 4096, 2^32 + 4096): two rounds in one group (two steps down), the wide build with one group, and the sorted hint
-#       (the sweep does not serve this index: k_tok_lds takes the batch in order);
+#       (k_tok_lds takes the batch in order);
 #   2 097 152 (T = 2048): k_tok_lds' smallest tile overflows, every form ends on the generic kernel.
 # Not run: 2 rounds x 2 groups and 1 round x 2 groups (tiles of 4096 and 2048 queries: the first is the tile of `narrow r1 g1`, the
-# second holds the product at every size k_tok_lds serves), the 256-thread sweep with two rounds, the 1024-thread sweep with one.
+# second holds the product at every size k_tok_lds serves).
 FORMS_AT = {
-    524_288: ("default", "narrow r2 g1", "sorted tpb1024 r2", "generic"),
+    524_288: ("default", "narrow r2 g1", "generic"),
     1_048_576: ("default", "narrow r1 g1", "generic"),
     1_048_577: ("default", "narrow r2 g1", "wide g1", "sorted", "generic"),
     2_097_152: ("default", "narrow r1 g1", "generic"),
@@ -285,7 +281,7 @@ def test_one_tile_of_two_to_the_32_hits_under_every_geometry(ga, monkeypatch, de
     them beyond 2^32.  (The stack's intervals are 4 194 304 long here, so that 2 097 152 of them still share a part.)  Count-only
     under the geometries the launchers can be pushed to (FORMS_B; which of them at which size: FORMS_AT): k_tok_lds with 1 or
     2 rounds x 1 or 2 wave groups (tiles of 4096, 8192, 2048, 4096 queries; the narrow build, which alone takes two rounds), the
-    wide build, the sweep form on the batch in order (there ALL its full queries lie in a row), and the generic kernel.  The
+    wide build, the sorted hint on the batch in order (there ALL its full queries lie in a row), and the generic kernel.  The
     launchers must step the geometry down or hand the index on: offsets exact in every case."""
     g = dense_index(dense)
     t = W.heavy_tile(dense)
@@ -300,9 +296,7 @@ def test_one_tile_of_two_to_the_32_hits_under_every_geometry(ga, monkeypatch, de
     if form == "generic":
         assert "k_enum_fused<bits>" in prof, sorted(prof)
     if dense * 8192 <= TWO32:  # every form can serve this index in some geometry: the forced form is the one that ran
-        assert ("k_tok_sweep" if hint & SORTED else "k_enum_fused<bits>" if form == "generic" else "k_tok_lds") in prof, (form, sorted(prof))
-        if "tpb1024" in form:
-            assert "tok_sweep_tpb1024" in prof, (form, sorted(prof))
+        assert ("k_enum_fused<bits>" if form == "generic" else "k_tok_lds") in prof, (form, sorted(prof))
 
 
 def test_default_geometry_steps_down_for_a_dense_tile_in_a_long_batch(ga, dense_index):
