@@ -399,6 +399,8 @@ _DEBUG_SIG = {
     "gtars_debug_signal_sort_elems": (u32, [u32]),
     "gtars_debug_signal_split_hits": (u32, []),
     "gtars_debug_tokbatch_tile": (u32, []),
+    "gtars_debug_grid_clips": (u64, []),
+    "gtars_debug_seq_stage_blocks": (u64, []),
 }
 
 # every symbol the headers declare must resolve -- fail loudly otherwise (GTARS_AMD_LIB_OLDER=1, A/B tooling only: an older

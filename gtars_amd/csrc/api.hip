@@ -60,6 +60,23 @@ long cfg_int(const char *name, long dflt) {
     const char *v = cfg_get(name);
     return v && *v ? atol(v) : dflt;
 }
+// GTARS_GRID_CAP is asked for at every grid-stride launch: parsed once per snapshot, not looked up per launch.  (A launch on
+// another thread that races gtars_debug_reload_env may store the value it parsed from the old snapshot after the reset
+// below; the cap then stays stale until the next reload.  Tests reload and launch from one thread.)
+namespace {
+constexpr u32 GRID_CAP_UNREAD = 0xFFFFFFFFu;
+std::atomic<u32> g_grid_cap{GRID_CAP_UNREAD};
+std::atomic<u64> g_grid_clips{0};
+}  // namespace
+u32 grid_cap_switch() {
+    u32 v = g_grid_cap.load(std::memory_order_relaxed);
+    if (v == GRID_CAP_UNREAD) {
+        v = (u32)std::min<long>(std::max<long>(cfg_int("GTARS_GRID_CAP", 0), 0), 1l << 30);
+        g_grid_cap.store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
+void note_grid_clip() { g_grid_clips.fetch_add(1, std::memory_order_relaxed); }
 
 gtars_status fail(gtars_status st, const std::string &msg) {
     g_last_error = msg;
@@ -690,7 +707,9 @@ void gtars_debug_reload_env(void) {
     std::lock_guard<std::mutex> lk(g_env_mu);
     if (g_env) g_env_old.push_back(g_env);  // (a value handed out by cfg_get stays valid)
     g_env = m;
+    g_grid_cap.store(GRID_CAP_UNREAD, std::memory_order_relaxed);
 }
+uint64_t gtars_debug_grid_clips(void) { return g_grid_clips.load(std::memory_order_relaxed); }
 void gtars_prof_reset(void) {
     prof_drain();
     g_prof_entries.clear();

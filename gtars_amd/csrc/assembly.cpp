@@ -343,6 +343,8 @@ int gtars_debug_set_assembly_device(void *assembly, int device) {
     return a->dev ? gtars::assembly_set_device(a->dev, device) : -1;
 }
 
+uint64_t gtars_debug_seq_stage_blocks(void) { return gtars::assembly_stage_blocks(); }
+
 uint32_t gtars_seqstats_piece_bytes(void) { return gtars::SEQ_PIECE; }
 
 gtars_status gtars_seqstats_counts_device(gtars_assembly_t *a, const uint32_t *d_chrom, const uint32_t *d_start,

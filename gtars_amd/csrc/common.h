@@ -179,6 +179,11 @@ struct StreamFrame {
 const char *cfg_get(const char *name);
 inline bool cfg_flag(const char *name) { return cfg_get(name) != nullptr; }
 long cfg_int(const char *name, long dflt);
+// GTARS_GRID_CAP (test switch; unset or 0: none): the most workgroups a grid-stride launch gets, so that a small input walks
+// the kernel's loop more than once.  Parsed once per snapshot.  note_grid_clip: a launch helper reports that this cap, and
+// not its own, cut a grid short (gtars_debug_grid_clips counts the reports).
+u32 grid_cap_switch();
+void note_grid_clip();
 
 // ---- device views ----------------------------------------------------------
 // One genome-wide overlap index: every chromosome's intervals concatenated in

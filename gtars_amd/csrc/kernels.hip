@@ -443,6 +443,10 @@ gtars_status launch_enumerate_fused(const IndexView &v, int kind, const u32 *qc,
 static unsigned stream_grid(u64 n, int tpb) {
     u64 g = (n + tpb - 1) / tpb;
     const u64 cap = 256ull * 16;
+    if (const u32 low = grid_cap_switch(); low && low < cap && g > low) {  // (GTARS_GRID_CAP, a test switch: common.h)
+        note_grid_clip();
+        return low;
+    }
     if (g > cap) g = cap;
     if (g == 0) g = 1;
     return (unsigned)g;

@@ -9,8 +9,14 @@
 namespace gtars {
 
 // workgroups of `per` elements that cover n, at least one and at most `cap` (grid-stride kernels)
+// (GTARS_GRID_CAP, a test switch, lowers `cap`: common.h)
 inline unsigned grid_for(u64 n, u32 per = 256, u32 cap = 1u << 16) {
-    return (unsigned)std::min<u64>(std::max<u64>(1, (n + per - 1) / per), cap);
+    const u64 want = std::max<u64>(1, (n + per - 1) / per);
+    if (const u32 low = grid_cap_switch(); low && low < cap && want > low) {
+        note_grid_clip();
+        return low;
+    }
+    return (unsigned)std::min<u64>(want, cap);
 }
 
 // first position p in [lo, hi) with x[p] >= key (first_gt: > key), hi if none; x ascends.  P: any indexable, global or LDS

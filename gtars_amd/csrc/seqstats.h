@@ -32,6 +32,7 @@ struct AssemblyParts {
 };
 AssemblyParts assembly_parts(const Assembly &a);
 int assembly_set_device(Assembly *a, int device);  // test hook (gtars_debug_set_assembly_device): -> the id recorded before
+uint64_t assembly_stage_blocks();  // test hook (gtars_debug_seq_stage_blocks): staging blocks sent by every build so far
 
 // d_chrom / d_start / d_end: n device rows, chromosome ids of the assembly, every row with start <= end <= len (a row
 // that is not fails the call with GTARS_ERR_INVALID_ARG and is never read from the image).

@@ -21,6 +21,7 @@
 //     k_seq_pieces zeroed: integer sums do not depend on order, the counts are exact either way.
 //   * LANES = 16 or 64 (a 256-byte or a 1-KiB step): GTARS_SEQ_LANES picks, see DESIGN.md K12 for the figures.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <memory>
 
@@ -46,7 +47,14 @@ namespace {
 constexpr int SEQ_TPB = 256;
 constexpr u64 SEQ_MAX_N = 0xFFFFF000u;
 constexpr u32 SEQ_MAX_BLOCKS = 256 * 8;
-constexpr size_t SEQ_STAGE_BYTES = 32u << 20;  // one pinned staging block of the upload
+constexpr size_t SEQ_STAGE_BYTES = 32u << 20;  // one pinned staging block of the upload (GTARS_SEQ_STAGE_BYTES, a test switch)
+
+// the staging block's size: the switch's value rounded down to a multiple of 16 (the image's alignment), at least 16
+size_t stage_bytes() {
+    const long v = cfg_int("GTARS_SEQ_STAGE_BYTES", (long)SEQ_STAGE_BYTES);
+    return (size_t)std::max<long>(v, 16) & ~(size_t)15;
+}
+std::atomic<u64> g_stage_blocks{0};  // staging blocks sent by every assembly_build so far (gtars_debug_seq_stage_blocks)
 
 // pieces per row; rows that are not one piece are zeroed here (no piece, or several that add).  A row that does not lie
 // inside its chromosome gets no piece and raises *bad.
@@ -289,7 +297,7 @@ gtars_status assembly_build(const uint8_t *const *seq, const uint64_t *len, uint
     GT_TRY(a->len.upload(ln));
     // the packed image leaves through two pinned blocks that take turns: one is filled while the other one's copy runs
     StreamFrame fr(nullptr);
-    const size_t block = (size_t)std::min<u64>(std::max<u64>(at, 16), SEQ_STAGE_BYTES);
+    const size_t block = (size_t)std::min<u64>(std::max<u64>(at, 16), stage_bytes());
     u8 *stage[2] = {(u8 *)fr.host(block), (u8 *)fr.host(block)};
     if (!stage[0] || !stage[1]) return fail(GTARS_ERR_INTERNAL, "out of host memory");
     hipEvent_t done[2] = {nullptr, nullptr};
@@ -321,6 +329,7 @@ gtars_status assembly_build(const uint8_t *const *seq, const uint64_t *len, uint
         }
         GT_TRY(fr.upload_to(a->seq.p + w0, dst, wl));
         GT_HIP(hipEventRecord(done[turn], fr.st));
+        g_stage_blocks.fetch_add(1, std::memory_order_relaxed);
     }
     GT_TRY(fr.drain());
     *out = a.release();
@@ -332,6 +341,8 @@ void assembly_free(Assembly *a) {
     DeviceScope on(a->device);  // (the buffers go back to the device they came from)
     delete a;
 }
+
+uint64_t assembly_stage_blocks() { return g_stage_blocks.load(std::memory_order_relaxed); }
 
 int assembly_device(const Assembly *a) { return a ? a->device : -1; }
 

@@ -361,29 +361,30 @@ __global__ void k_sweep_seq(const u32 *__restrict__ as, const u32 *__restrict__ 
                             const u32 *__restrict__ bs, const u32 *__restrict__ be, const u32 *__restrict__ boff, u32 n_rank,
                             const u32 *__restrict__ dirty, u32 *__restrict__ cnt, const u64 *__restrict__ off, u32 *__restrict__ oseg,
                             u32 *__restrict__ os, u32 *__restrict__ oe) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rank || !dirty[r]) return;
-    const u32 blo = boff[r], bhi = boff[r + 1];
-    u32 b_idx = blo;
-    for (u32 i = aoff[r]; i < aoff[r + 1]; ++i) {
-        const u32 s = as[i], e = ae[i];
-        while (b_idx < bhi && be[b_idx] <= s) ++b_idx;
-        const u64 o = WRITE ? off[i] : 0;
-        u32 c = 0;
-        if (MODE == SWEEP_SETDIFF) {
-            u32 pos = s;
-            for (u32 j = b_idx; j < bhi && bs[j] < e && pos < e; ++j) {
-                if (bs[j] > pos) emit<MODE, WRITE>(c, o, (u32)r, pos, bs[j], oseg, os, oe);
-                pos = max(pos, be[j]);
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_rank; r += (u64)gridDim.x * blockDim.x) {
+        if (!dirty[r]) continue;
+        const u32 blo = boff[r], bhi = boff[r + 1];
+        u32 b_idx = blo;
+        for (u32 i = aoff[r]; i < aoff[r + 1]; ++i) {
+            const u32 s = as[i], e = ae[i];
+            while (b_idx < bhi && be[b_idx] <= s) ++b_idx;
+            const u64 o = WRITE ? off[i] : 0;
+            u32 c = 0;
+            if (MODE == SWEEP_SETDIFF) {
+                u32 pos = s;
+                for (u32 j = b_idx; j < bhi && bs[j] < e && pos < e; ++j) {
+                    if (bs[j] > pos) emit<MODE, WRITE>(c, o, (u32)r, pos, bs[j], oseg, os, oe);
+                    pos = max(pos, be[j]);
+                }
+                if (pos < e) emit<MODE, WRITE>(c, o, (u32)r, pos, e, oseg, os, oe);
+            } else {
+                for (u32 j = b_idx; j < bhi && bs[j] < e; ++j) {
+                    const u32 ps = max(s, bs[j]), pe = min(e, be[j]);
+                    if (ps < pe) emit<MODE, WRITE>(c, o, (u32)r, ps, pe, oseg, os, oe);
+                }
             }
-            if (pos < e) emit<MODE, WRITE>(c, o, (u32)r, pos, e, oseg, os, oe);
-        } else {
-            for (u32 j = b_idx; j < bhi && bs[j] < e; ++j) {
-                const u32 ps = max(s, bs[j]), pe = min(e, be[j]);
-                if (ps < pe) emit<MODE, WRITE>(c, o, (u32)r, ps, pe, oseg, os, oe);
-            }
+            if (!WRITE) cnt[i] = c;
         }
-        if (!WRITE) cnt[i] = c;
     }
 }
 

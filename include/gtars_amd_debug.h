@@ -32,6 +32,10 @@ int gtars_debug_set_handle_device(void *handle, int is_igd, int device);
 /* The same for the device image of an assembly handle (gtars_assembly_t *, include/gtars_amd_host.h): -1 when the image
  * is not built yet.  tests/test_gpu_vrs.py. */
 int gtars_debug_set_assembly_device(void *assembly, int device);
+/* The pinned staging blocks that the builds of assembly images have sent to the device so far, over all assemblies (csrc/
+ * seqstats.hip: assembly_build; the block's size is GTARS_SEQ_STAGE_BYTES).  Never reset: tests/test_gpu_seq_stage.py reads it
+ * around a build to prove that the build went round the fill loop as often as its block size says. */
+uint64_t gtars_debug_seq_stage_blocks(void);
 
 /* Test / measurement entry of the device-side DEFLATE decoder (csrc/inflate_dev.hip; the fused fragment pipeline's input stage,
  * gtars-fragsplit/src/split.rs:84-131 reads its files through flate2's MultiGzDecoder): n_streams raw DEFLATE streams (RFC 1951, no
@@ -76,6 +80,13 @@ uint32_t gtars_debug_signal_split_hits(void);
 /* Test hook of the batched tokenizer (csrc/tokbatch.hip, K15; tests/test_gpu_tokbatch.py): the output ids a workgroup of
  * k_set_pack packs per step. */
 uint32_t gtars_debug_tokbatch_tile(void);
+
+/* Test hook of the grid-stride launches (csrc/pipeline.h grid_for, csrc/kernels.hip stream_grid; tests/test_gpu_grid_cap.py).
+ * GTARS_GRID_CAP = C > 0 lowers the most workgroups either helper hands out to min(its own cap, C), so that an input of a
+ * few hundred rows walks a kernel's grid-stride loop several times; unset or 0 changes nothing.  This counter rises by one
+ * for every helper call in which the lowered cap, and not the helper's own, cut the grid short: a test reads it around a
+ * call to prove that the call ran more than one trip.  Never reset. */
+uint64_t gtars_debug_grid_clips(void);
 
 /* (Stamp builds -- tools/build_variant.sh with -DGTARS_TOK_STAMPS=1 / -DIGD_STAMPS=1 -- additionally export
  * gtars_debug_tok_stamps / gtars_debug_route_stamps / gtars_debug_sweep_stamps: s_memtime at the phase boundaries of the tile
