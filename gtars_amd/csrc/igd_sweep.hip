@@ -1865,26 +1865,7 @@ constexpr int SG_ITEMS = 8;             // consecutive elements per lane
 constexpr int SG_WAVE = 64 * SG_ITEMS;  // elements per wave
 constexpr int SG_TPB = 256;
 
-struct SegAgg {
-    u32 f;  // a segment head lies in the range
-    i32 v;  // maximum since the last head (of the whole range if there is none)
-};
-__device__ __forceinline__ SegAgg seg_combine(SegAgg a, SegAgg b) {  // a then b
-    SegAgg r;
-    r.f = a.f | b.f;
-    r.v = b.f ? b.v : max(a.v, b.v);
-    return r;
-}
-__device__ __forceinline__ SegAgg seg_wave_inclusive(SegAgg x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        SegAgg y;
-        y.f = __shfl_up(x.f, d, 64);
-        y.v = __shfl_up(x.v, d, 64);
-        if (lane >= d) x = seg_combine(y, x);
-    }
-    return x;
-}
+using SegEnd = SegMax<i32>;  // head flag + largest end since the last head, clamped at 0
 
 // sorted (file, position) pairs -> per element: segment-head flag and value (the record's end)
 __device__ __forceinline__ u32 chrom_of(const u32 *__restrict__ chrom_off, u32 n_chrom, u32 r) {
@@ -1903,7 +1884,7 @@ __device__ __forceinline__ u32 chrom_of(const u32 *__restrict__ chrom_off, u32 n
 template <int PHASE>
 __global__ void __launch_bounds__(SG_TPB)
 k_pme_scan(const u32 *__restrict__ file_sorted, const u32 *__restrict__ pos, const i32 *__restrict__ ends,
-           const u32 *__restrict__ chrom_off, u32 n_chrom, u32 n, SegAgg *__restrict__ wave_agg, i32 *__restrict__ out) {
+           const u32 *__restrict__ chrom_off, u32 n_chrom, u32 n, SegEnd::T *__restrict__ wave_agg, i32 *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const u32 w = (blockIdx.x * SG_TPB + threadIdx.x) >> 6;
     const u32 base = w * SG_WAVE + (u32)lane * SG_ITEMS;
@@ -1932,7 +1913,7 @@ k_pme_scan(const u32 *__restrict__ file_sorted, const u32 *__restrict__ pos, con
             p[k] = 0xFFFFFFFFu;
         }
     }
-    SegAgg mine{0u, 0};
+    SegEnd::T mine = SegEnd::identity();
     i32 ex[SG_ITEMS];
     u32 headed[SG_ITEMS];  // a head at or before item k inside this lane
 #pragma unroll
@@ -1945,47 +1926,22 @@ k_pme_scan(const u32 *__restrict__ file_sorted, const u32 *__restrict__ pos, con
         ex[k] = mine.v;
         mine.v = max(mine.v, val[k]);
     }
-    const SegAgg inc = seg_wave_inclusive(mine, lane);
+    const SegEnd::T inc = wave_scan<SegEnd>(mine, lane);
     if (PHASE == 0) {
         if (lane == 63) wave_agg[w] = inc;
         return;
     }
-    SegAgg carry;  // everything before this lane: the waves before (wave_agg holds their EXCLUSIVE scan) and the lanes before
-    carry.f = __shfl_up(inc.f, 1, 64);
-    carry.v = __shfl_up(inc.v, 1, 64);
-    if (lane == 0) carry = SegAgg{0u, 0};
-    carry = seg_combine(wave_agg[w], carry);
+    // everything before this lane: the waves before (wave_agg holds their EXCLUSIVE scan) and the lanes before
+    const SegEnd::T carry = SegEnd::op(wave_agg[w], wave_exclusive<SegEnd>(inc, lane));
 #pragma unroll
     for (int k = 0; k < SG_ITEMS; ++k)
         if (p[k] != 0xFFFFFFFFu) out[p[k]] = headed[k] ? ex[k] : max(carry.v, ex[k]);
 }
 
 // exclusive scan of the wave aggregates, in place (one workgroup; a few thousand entries per round)
-__global__ void __launch_bounds__(1024)
-k_pme_scan_aggs(SegAgg *__restrict__ agg, u32 n_waves) {
-    __shared__ SegAgg s_w[16];
-    __shared__ SegAgg s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = SegAgg{0u, 0};
-    __syncthreads();
-    for (u32 base = 0; base < n_waves; base += 1024) {
-        const u32 i = base + threadIdx.x;
-        const SegAgg x = i < n_waves ? agg[i] : SegAgg{0u, 0};
-        const SegAgg inc = seg_wave_inclusive(x, lane);
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        SegAgg before = s_carry;
-        for (int k = 0; k < wave; ++k) before = seg_combine(before, s_w[k]);
-        SegAgg ex;
-        ex.f = __shfl_up(inc.f, 1, 64);
-        ex.v = __shfl_up(inc.v, 1, 64);
-        if (lane == 0) ex = SegAgg{0u, 0};
-        ex = seg_combine(before, ex);
-        if (i < n_waves) agg[i] = ex;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = seg_combine(ex, x);
-        __syncthreads();
-    }
+__global__ void __launch_bounds__(1024) k_pme_scan_aggs(SegEnd::T *__restrict__ agg, u32 n_waves) {
+    __shared__ SegEnd::T lds[1024 / 64];
+    (void)carry_walk<SegEnd>(agg, n_waves, lds);
 }
 
 __global__ void k_file_keys(const u32 *__restrict__ files, u32 *__restrict__ key, u32 n) {
@@ -2000,7 +1956,7 @@ __global__ void k_iota_u32(u32 *__restrict__ p, u32 n) {
 
 size_t igd_pme_ws_bytes(u32 n) {
     const u32 n_waves = (n + SG_WAVE - 1) / SG_WAVE;
-    return (size_t)n * 4 * 4 + (size_t)n_waves * sizeof(SegAgg) + radix_sort_ws_bytes(n) + 256;
+    return (size_t)n * 4 * 4 + (size_t)n_waves * sizeof(SegEnd::T) + radix_sort_ws_bytes(n) + 256;
 }
 
 gtars_status igd_build_pme_file(const IgdView &v, i32 *pme, void *ws, size_t ws_bytes, hipStream_t st) {
@@ -2009,7 +1965,7 @@ gtars_status igd_build_pme_file(const IgdView &v, i32 *pme, void *ws, size_t ws_
     if (ws_bytes < igd_pme_ws_bytes(n)) return fail(GTARS_ERR_INTERNAL, "pme_file workspace too small");
     u32 *k0 = (u32 *)ws, *v0 = k0 + n, *k1 = v0 + n, *v1 = k1 + n;
     const u32 n_waves = (n + SG_WAVE - 1) / SG_WAVE;
-    SegAgg *agg = (SegAgg *)(v1 + n);
+    SegEnd::T *agg = (SegEnd::T *)(v1 + n);
     void *sort_ws = (void *)(((uintptr_t)(agg + n_waves) + 63) & ~(uintptr_t)63);
     const size_t sort_bytes = ws_bytes - (size_t)((char *)sort_ws - (char *)ws);
     hipLaunchKernelGGL(k_file_keys, dim3((n + 255) / 256), dim3(256), 0, st, v.files, k0, n);  // (without a pieces view's flag bit)

@@ -143,33 +143,9 @@ k_scan_reduce(const u32 *__restrict__ counts, u64 n, u64 *__restrict__ partials)
 
 // single block: exclusive scan of the per-tile partials in place, total -> partials[np]
 __global__ void __launch_bounds__(1024) k_scan_partials(u64 *__restrict__ partials, u64 np) {
-    __shared__ u64 lds[16];
-    __shared__ u64 carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (u64 base = 0; base < np; base += 1024) {
-        const u64 i = base + threadIdx.x;
-        u64 x = i < np ? partials[i] : 0, inc = x;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            u64 y = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += y;
-        }
-        if (lane == 63) lds[wave] = inc;
-        __syncthreads();
-        u64 wbase = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wave) wbase += lds[w];
-            tot += lds[w];
-        }
-        const u64 carry = carry_s;
-        if (i < np) partials[i] = carry + wbase + inc - x;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[np] = carry_s;
+    __shared__ u64 lds[1024 / 64];
+    const u64 total = carry_walk<SumU64>(partials, np, lds);
+    if (threadIdx.x == 0) partials[np] = total;
 }
 
 // Exclusive scan across the workgroup of one value < 2^35 per thread (the sum of SCAN_IPT u32 counts), exact in u64: a tile of

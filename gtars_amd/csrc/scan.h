@@ -1,6 +1,12 @@
-// scan.h -- wave/workgroup scans and the chained ("decoupled look-back")
-// cross-workgroup prefix sum shared by the fused enumerate kernels.
+// scan.h -- wave/workgroup scans, in three families:
+//   * u32 sums on the DPP path (wave_inclusive_scan_u32, block_exclusive_scan) for the additive hot paths;
+//   * scans over any monoid (wave_scan, block_scan, carry_walk) with the monoids SegMax and SumU64: the one skeleton
+//     behind every "scan a tile, let one workgroup walk the tile aggregates into carries, re-scan each tile with its
+//     carry" pass but the 16-byte top-2 scan of setops.hip (k_sm_*, k_pme_scan*, k_scan_partials);
+//   * the chained ("decoupled look-back") cross-workgroup prefix sum shared by the fused enumerate kernels.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace gtars {
@@ -73,6 +79,95 @@ __device__ __forceinline__ u32 block_exclusive_scan(u32 x, u32 *lds, u32 &total)
     total = tot;
     __syncthreads();
     return base + inc - x;
+}
+
+// ---- scans over a monoid -------------------------------------------------------
+// A monoid M supplies T (a trivially copyable struct of 32-bit words), identity() and op(a, b) = "a then b":
+// associative, identity() neutral on both sides, not necessarily commutative.
+
+// head flag + maximum since the last head (of the whole span if there is none).  V = u32: region-set ends.  V = i32:
+// IGD ends; {0, 0} is an identity only for values >= 0 (op({1, -5}, {0, 0}) is {1, 0}).  Its users keep to that: ends
+// are positive and every accumulator starts at 0, which is also what clamps their maxima at 0.
+template <class V>
+struct SegMax {
+    struct alignas(8) T {
+        u32 f;  // a segment head lies in the span
+        V v;
+    };
+    static __device__ __forceinline__ T identity() { return T{0u, 0}; }
+    static __device__ __forceinline__ T op(T a, T b) { return T{a.f | b.f, b.f ? b.v : max(a.v, b.v)}; }
+};
+
+struct SumU64 {
+    using T = u64;  // two words to the shuffles
+    static __device__ __forceinline__ T identity() { return 0; }
+    static __device__ __forceinline__ T op(T a, T b) { return a + b; }
+};
+
+// word by word: x of lane n, which must be wave-uniform (v_readlane, the result is scalar); UP: x of the lane n below
+template <bool UP, class T>
+__device__ __forceinline__ T shfl_words(T x, int n) {
+    static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % 4 == 0, "T: a struct of 32-bit words");
+    u32 w[sizeof(T) / 4];
+    __builtin_memcpy(w, &x, sizeof(T));
+#pragma unroll
+    for (size_t k = 0; k < sizeof(T) / 4; ++k) w[k] = UP ? __shfl_up(w[k], n, 64) : (u32)__builtin_amdgcn_readlane((int)w[k], n);
+    __builtin_memcpy(&x, w, sizeof(T));
+    return x;
+}
+
+// Inclusive scan across the wave's first N lanes (all 64 by default).  All 64 lanes must be active: call it only after
+// wave-uniform exits.
+template <class M, int N = 64>
+__device__ __forceinline__ typename M::T wave_scan(typename M::T x, int lane) {
+#pragma unroll
+    for (int d = 1; d < N; d <<= 1) {
+        const typename M::T y = shfl_words<true>(x, d);
+        if (lane >= d) x = M::op(y, x);
+    }
+    return x;
+}
+
+// the exclusive value of a lane from the wave's inclusive values
+template <class M>
+__device__ __forceinline__ typename M::T wave_exclusive(typename M::T inc, int lane) {
+    const typename M::T y = shfl_words<true>(inc, 1);
+    return lane ? y : M::identity();
+}
+
+// Scan across a TPB-thread workgroup: returns the thread's inclusive value, its exclusive value in `excl` and the
+// workgroup's total in `total`.  lds: TPB/64 elements, free again on return.  The wave totals are scanned by every wave
+// in its first TPB/64 lanes: log2 steps instead of a chain of TPB/64 dependent LDS reads.
+template <class M, int TPB>
+__device__ __forceinline__ typename M::T block_scan(typename M::T x, typename M::T *lds, typename M::T &excl, typename M::T &total) {
+    using T = typename M::T;
+    constexpr int NW = TPB / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const T inc = wave_scan<M>(x, lane), prev = wave_exclusive<M>(inc, lane);
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    const T tots = wave_scan<M, NW>(lds[lane % NW], lane);  // lane w < NW: waves 0 .. w
+    __syncthreads();
+    const T before = wave ? shfl_words<false>(tots, wave - 1) : M::identity();
+    excl = M::op(before, prev);
+    total = shfl_words<false>(tots, NW - 1);
+    return M::op(before, inc);
+}
+
+// One workgroup of TPB threads turns the n aggregates agg[] into exclusive carries, in place, TPB per round, and
+// returns the grand total to every thread.  lds: TPB/64 elements.
+template <class M, int TPB = 1024>
+__device__ __forceinline__ typename M::T carry_walk(typename M::T *__restrict__ agg, u64 n, typename M::T *lds) {
+    using T = typename M::T;
+    T run = M::identity();
+    for (u64 b = 0; b < n; b += TPB) {
+        const u64 i = b + threadIdx.x;
+        T ex, tot;
+        (void)block_scan<M, TPB>(i < n ? agg[i] : M::identity(), lds, ex, tot);
+        if (i < n) agg[i] = M::op(run, ex);
+        run = M::op(run, tot);
+    }
+    return run;
 }
 
 // ---- chained scan state ------------------------------------------------------

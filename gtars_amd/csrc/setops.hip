@@ -55,57 +55,31 @@ constexpr u32 SO_MAX_N = 0xFFFFF000u;
 enum { SWEEP_SETDIFF = 0, SWEEP_INTERSECT = 1 };
 
 // ---------------------------------------------------------------------------------------------- segmented max-scan
-struct SM {
-    u32 f, v;  // f: a segment head lies in the span; v: max of the values since the last head
-};
-__device__ __forceinline__ SM sm_op(SM a, SM b) { return SM{a.f | b.f, b.f ? b.v : max(a.v, b.v)}; }
-__device__ __forceinline__ u64 sm_pack(SM a) { return ((u64)a.f << 32) | a.v; }
-__device__ __forceinline__ SM sm_unpack(u64 x) { return SM{(u32)(x >> 32), (u32)x}; }
+using SMax = SegMax<u32>;  // f: a segment head lies in the span; v: max of the values since the last head
 __device__ __forceinline__ u32 is_head(const u32 *__restrict__ seg, u64 i) { return i == 0 || seg[i] != seg[i - 1]; }
 
-// inclusive scan across the workgroup; lds[t] holds thread t's inclusive value afterwards
-template <int TPB>
-__device__ __forceinline__ SM block_incl(SM x, u64 *lds) {
-    const int t = threadIdx.x;
-    lds[t] = sm_pack(x);
-    __syncthreads();
-    for (int d = 1; d < TPB; d <<= 1) {
-        SM y = x;
-        if (t >= d) y = sm_op(sm_unpack(lds[t - d]), x);
-        __syncthreads();
-        lds[t] = sm_pack(y);
-        x = y;
-        __syncthreads();
-    }
-    return x;
+// a thread's SO_IPT elements folded in order; elements past n are the identity
+__device__ __forceinline__ SMax::T sm_thread(const u32 *__restrict__ seg, const u32 *__restrict__ val, u32 n, u64 base) {
+    SMax::T acc = SMax::identity();
+#pragma unroll
+    for (int k = 0; k < SO_IPT; ++k)
+        if (base + k < n) acc = SMax::op(acc, SMax::T{is_head(seg, base + k), val[base + k]});
+    return acc;
 }
 
 __global__ void __launch_bounds__(SO_TPB)
-k_sm_tiles(const u32 *__restrict__ seg, const u32 *__restrict__ val, u32 n, u64 *__restrict__ agg) {
-    __shared__ u64 lds[SO_TPB];
+k_sm_tiles(const u32 *__restrict__ seg, const u32 *__restrict__ val, u32 n, SMax::T *__restrict__ agg) {
+    __shared__ SMax::T lds[SO_TPB / 64];
     const u64 base = (u64)blockIdx.x * SO_TILE + (u64)threadIdx.x * SO_IPT;
-    SM acc{0, 0};
-#pragma unroll
-    for (int k = 0; k < SO_IPT; ++k)
-        if (base + k < n) acc = sm_op(acc, SM{is_head(seg, base + k), val[base + k]});
-    acc = block_incl<SO_TPB>(acc, lds);
-    if (threadIdx.x == SO_TPB - 1) agg[blockIdx.x] = sm_pack(acc);
+    SMax::T excl, total;
+    (void)block_scan<SMax, SO_TPB>(sm_thread(seg, val, n, base), lds, excl, total);
+    if (threadIdx.x == 0) agg[blockIdx.x] = total;
 }
 
 // tile aggregates -> exclusive carries, in place (one workgroup)
-__global__ void __launch_bounds__(1024) k_sm_carry(u64 *__restrict__ agg, u32 n_tiles) {
-    __shared__ u64 lds[1024];
-    SM run{0, 0};
-    for (u32 b = 0; b < n_tiles; b += 1024) {
-        const u32 t = b + threadIdx.x;
-        const SM x = t < n_tiles ? sm_unpack(agg[t]) : SM{0, 0};
-        (void)block_incl<1024>(x, lds);
-        const SM ex = threadIdx.x ? sm_op(run, sm_unpack(lds[threadIdx.x - 1])) : run;
-        const SM last = sm_unpack(lds[1023]);
-        __syncthreads();
-        if (t < n_tiles) agg[t] = sm_pack(ex);
-        run = sm_op(run, last);
-    }
+__global__ void __launch_bounds__(1024) k_sm_carry(SMax::T *__restrict__ agg, u32 n_tiles) {
+    __shared__ SMax::T lds[1024 / 64];
+    (void)carry_walk<SMax>(agg, n_tiles, lds);
 }
 
 // INCL: out[i] = max of val over [segment head, i].  Else: out[i] = 1 where i opens a run: a head, or
@@ -113,28 +87,24 @@ __global__ void __launch_bounds__(1024) k_sm_carry(u64 *__restrict__ agg, u32 n_
 template <bool INCL>
 __global__ void __launch_bounds__(SO_TPB)
 k_sm_apply(const u32 *__restrict__ seg, const u32 *__restrict__ val, const u32 *__restrict__ start, u32 n,
-           const u64 *__restrict__ carry, u32 gap, u32 *__restrict__ out) {
-    __shared__ u64 lds[SO_TPB];
+           const SMax::T *__restrict__ carry, u32 gap, u32 *__restrict__ out) {
+    __shared__ SMax::T lds[SO_TPB / 64];
     const u64 base = (u64)blockIdx.x * SO_TILE + (u64)threadIdx.x * SO_IPT;
-    SM acc{0, 0};
-#pragma unroll
-    for (int k = 0; k < SO_IPT; ++k)
-        if (base + k < n) acc = sm_op(acc, SM{is_head(seg, base + k), val[base + k]});
-    (void)block_incl<SO_TPB>(acc, lds);
-    SM run = sm_unpack(carry[blockIdx.x]);
-    if (threadIdx.x) run = sm_op(run, sm_unpack(lds[threadIdx.x - 1]));
+    SMax::T excl, total;
+    (void)block_scan<SMax, SO_TPB>(sm_thread(seg, val, n, base), lds, excl, total);
+    SMax::T run = SMax::op(carry[blockIdx.x], excl);
 #pragma unroll
     for (int k = 0; k < SO_IPT; ++k) {
         const u64 i = base + k;
         if (i >= n) break;
-        const SM x{is_head(seg, i), val[i]};
+        const SMax::T x{is_head(seg, i), val[i]};
         if (INCL) {
-            run = sm_op(run, x);
+            run = SMax::op(run, x);
             out[i] = run.v;
         } else {
             const u32 lim = run.v > 0xFFFFFFFFu - gap ? 0xFFFFFFFFu : run.v + gap;  // saturating_add
             out[i] = (x.f || start[i] > lim) ? 1u : 0u;
-            run = sm_op(run, x);
+            run = SMax::op(run, x);
         }
     }
 }
@@ -143,7 +113,7 @@ gtars_status seg_max_pass(StreamFrame &fr, bool incl, const u32 *seg, const u32 
     if (!n) return GTARS_OK;
     hipStream_t st = fr.st;
     const u32 tiles = (n + SO_TILE - 1) / SO_TILE;
-    u64 *agg = nullptr;
+    SMax::T *agg = nullptr;
     GT_TRY(fr.alloc(&agg, tiles));
     hipLaunchKernelGGL(k_sm_tiles, dim3(tiles), dim3(SO_TPB), 0, st, seg, val, n, agg);
     hipLaunchKernelGGL(k_sm_carry, dim3(1), dim3(1024), 0, st, agg, tiles);
@@ -1321,7 +1291,8 @@ __device__ __forceinline__ T2 t2_row(const u32 *__restrict__ seg, const u32 *__r
     return T2{T2_V1 | (is_head(seg, i) ? T2_HEAD : 0u), end[i], set[i], 0u};
 }
 
-// the 16-byte form of block_incl: lds[t] holds thread t's inclusive value afterwards
+// Inclusive scan across the workgroup through LDS (Hillis-Steele); lds[t] holds thread t's inclusive value afterwards.
+// Kept beside scan.h's block_scan: on the shuffle form k_t2_apply measured 3 % slower (profiles/scan_skeleton).
 template <int TPB>
 __device__ __forceinline__ T2 t2_block_incl(T2 x, uint4 *lds) {
     const int t = threadIdx.x;

@@ -120,3 +120,28 @@ def wide_set(seed, n_names):
     s = rng.integers(0, 5000, len(c))
     e = s + rng.integers(0, 400, len(c))
     return [(f"k{int(c[i])}", int(s[i]), int(e[i])) for i in rng.permutation(len(c))]
+
+
+def long_covers(m, n_far=300, seed=0):
+    """Three sets for the folds over a list whose top-2 summary must travel a long way: set 0 is chr1:[0, B), set 1 is
+    chr1:[1, B - 1) plus the m regions chr1:[10 k, 10 k + 5), set 2 the m regions chr1:[10 k + 5, 10 k + 9) plus n_far
+    disjoint regions on chr2 (k = 1 .. m; B lies above every other end).  In sorted order the first two rows set m1 / s1
+    (set 0's end) and m2 (set 1's long end) for the 2 m rows behind them with no head between, and the first chr2 row
+    resets them.  cols: per set (chromosome index, start, end), shuffled; full / ex: the closed forms of union_all and of
+    the union without each set."""
+    rng = np.random.default_rng(seed)
+    k = np.arange(1, m + 1, dtype=np.int64)
+    top = 10 * m + 1000
+    far_s = 20 * np.arange(n_far, dtype=np.int64)
+    z = lambda n: np.zeros(n, dtype=np.int64)  # noqa: E731
+    cols = [(z(1), z(1), np.array([top], dtype=np.int64)),
+            (z(m + 1), np.concatenate([[1], 10 * k]), np.concatenate([[top - 1], 10 * k + 5])),
+            (np.concatenate([z(m), z(n_far) + 1]), np.concatenate([10 * k + 5, far_s]), np.concatenate([10 * k + 9, far_s + 10]))]
+    shuffled = []
+    for c, s, e in cols:
+        o = rng.permutation(len(c))
+        shuffled.append((c[o], s[o], e[o]))
+    far = [("chr2", int(s), int(s) + 10) for s in far_s]
+    full = [("chr1", 0, top)] + far
+    return SimpleNamespace(names=["chr1", "chr2"], cols=shuffled, full=full,
+                           ex=[[("chr1", 1, top - 1)] + far, full, [("chr1", 0, top)]])

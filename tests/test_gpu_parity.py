@@ -830,6 +830,41 @@ def test_igd_sweep_matches_oracle(ga, monkeypatch, seed, n, nq, F, span, wmax):
     assert g.count_region_hits(qc, qs, qe, 1).tolist() == exp_b
 
 
+def test_igd_pme_file_carries_a_maximum_across_the_second_round_of_wave_aggregates(ga, monkeypatch):
+    """pme_file (the binary count's first-hit rule for min_overlap == 1) is a segmented maximum over the records in (file,
+    stored) order: k_pme_scan leaves one aggregate per wave of 512 records and one workgroup (k_pme_scan_aggs) turns them
+    into carries, 1024 per round.  Two files on one chromosome: record 0 (file 0) covers the whole range, behind it short
+    disjoint records alternate between the files -- file 0 has more than 1024 * 512 + 512 of them, so its run crosses
+    the seam between the rounds with its maximum in front, and file 1's head behind it must reset that maximum.  Every
+    query lies inside one short record and overlaps record 0: file 0 scores nq exactly (a carry lost at the seam counts
+    file 0 again for every query on a file-0 record behind it), file 1 the queries on its records (a head not honoured
+    loses them).  The flat layout is asked for, so that record 0 is one record and not a chain of pieces that each renew
+    the maximum; that the sweep served the call is a profiling fact."""
+    monkeypatch.setenv("GTARS_IGD_SWEEP_MIN", "1")
+    monkeypatch.setenv("GTARS_IGD_NO_PIECES", "1")
+    n = 2 * (1024 * 512 + 512) + 75
+    k = np.arange(1, n, dtype=np.int64)
+    s = np.concatenate([[0], 16 * k])
+    e = np.concatenate([[16 * n + 100], 16 * k + 8])
+    f = np.concatenate([[0], k % 2])
+    assert int((f == 0).sum()) > 1024 * 512 + 512
+    g, o = _igd_pair(ga, np.zeros(n, dtype=np.int64), s, e, f, n_chrom=1, n_files=2)
+    nq = 65_536 + 3
+    on = np.linspace(1, n - 1, nq).astype(np.int64)  # the record each query lies in: first, last, both files, both rounds
+    qc, qs, qe = np.zeros(nq, dtype=np.int64), 16 * on + 2, 16 * on + 6
+    want = [nq, int((on % 2 == 1).sum())]
+    assert 0 < want[1] < nq and int(((on % 2 == 0) & (on > 2 * 1024 * 512)).sum()) > 0
+    _lib = ga._lib
+    _lib.lib.gtars_prof_reset()
+    _lib.lib.gtars_prof_enable(1)
+    got = g.count_region_hits(qc, qs, qe, 1).tolist()
+    names = set(_lib.prof_read())
+    _lib.lib.gtars_prof_enable(0)
+    assert "k_igd_sweep<binary>" in names, names
+    assert got == want
+    assert o.count_region_hits(qc, qs, qe, 1, n_files=2).tolist() == want
+
+
 def test_igd_routing_chunks_of_whole_steps_on_a_long_shuffled_batch(ga, monkeypatch):
     """Round 6: for long batches the routing kernel's chunks are whole 4096-query steps (fewer workgroups than CUs, no partial
     last step) and the first step's columns are requested in front of the table copy.  8.4M shuffled queries -- 256 chunks of

@@ -117,6 +117,24 @@ def test_tile_edges_disjoint_layout_with_chromosome_heads_on_the_seam(n, shift):
     assert _tuples(rsl.intersect_all()) == []
 
 
+def test_top2_carries_cross_the_second_round_of_the_tile_aggregates():
+    """edge_layouts.long_covers at m = 2^20 + 1100: more than 1024 tiles, so the one workgroup that turns the tile
+    aggregates into carries (k_t2_carry) takes a second round.  m1 / s1 (set 0's end) and m2 (set 1's long end) come from the
+    first two sorted rows and must reach every tile, across the seam between the rounds, with no head between; the chr2
+    head behind them must reset both.  Against the closed forms (tests/test_setlist_cpu.py holds them to the restatement)."""
+    from gtars.models import RegionSet, RegionSetList
+
+    lay = E.long_covers((1 << 20) + 1100)
+    assert sum(len(c) for c, _, _ in lay.cols) // TILE + 1 > 1024
+    rsl = RegionSetList([RegionSet.from_vectors([lay.names[i] for i in c.tolist()], s, e) for c, s, e in lay.cols])
+    full, ex = rsl.bulk_union_except()
+    assert _plain(full) == lay.full
+    assert [_tuples(x) for x in ex] == lay.ex
+    assert _tuples(rsl.union_all()) == lay.full
+    for i in range(3):
+        assert _tuples(rsl.union_except(i)) == lay.ex[i], i
+
+
 # ---- owner logic of the scan -------------------------------------------------------------------------------------------
 def test_one_set_covers_the_chromosome():
     """s1 is the covering set everywhere: only m2 decides the runs without it"""

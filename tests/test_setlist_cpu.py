@@ -268,6 +268,21 @@ def test_top2_scan_model_against_the_folds():
             assert pick(left) == want and pick(split) == want
 
 
+def test_long_covers_layout_closed_forms_against_the_restatement():
+    """edge_layouts.long_covers, which tests/test_gpu_setlist.py runs at 2^20 + 1100 regions per set against its closed
+    forms alone: at m = 1100 the closed forms are the fold's and the top-2 model's answers"""
+    import edge_layouts as E
+
+    lay = E.long_covers(1100)
+    sets = [[(lay.names[c], s, e) for c, s, e in zip(*(x.tolist() for x in col))] for col in lay.cols]
+    assert [len(s) for s in sets] == [1, 1101, 1400]
+    assert L.bulk_union_except(sets) == (lay.full, lay.ex)
+    assert L.bulk_union_except_top2(sets) == (lay.full, lay.ex)
+    assert L.union_all(sets) == lay.full
+    top = lay.full[0][2]
+    assert top > max(e for s in sets[1:] for _, _, e in s if e != top - 1) and len(lay.full) == 301
+
+
 def test_c_abi_answers_short_lists_on_the_host():
     """the four entry points themselves: NULL handle for "None", unreduced copies for one set (the other of two), and
     GTARS_ERR_INVALID_ARG for NULL arguments -- none of it needs a device"""
