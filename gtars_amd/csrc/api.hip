@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "countmat.h"
+#include "host_threads.h"
 #include "pipeline.h"
 #include "../../include/gtars_amd_debug.h"
 
@@ -350,9 +351,8 @@ struct gtars_index {
     // 0.43 vs 1.52, 2.30 vs 3.07, 3.34 vs 2.71 ms per 16M queries); GTARS_AILIST_REORDER_MAX_DEPTH moves the line (default 6)
     double ail_depth = 0;
     // per-chromosome sorted copy of the ends, built on the first Bits::count call (bits.rs:118-121)
-    mutable std::mutex ends_mu;
+    mutable Once ends_built;
     mutable DevBuf<u32> ends_sorted;
-    mutable bool ends_ready = false;
     AccelView accel() const {
         AccelView a;
         a.rec2 = reinterpret_cast<const uint4 *>(acc_rec2.p);
@@ -418,22 +418,19 @@ struct gtars_igd {
     // Databases with records longer than the piece length keep a second index of PIECES for the min_overlap == 1 counts (see
     // build_pieces_view below); null otherwise.
     std::unique_ptr<gtars_igd> pieces;
-    // host copy of the stored starts / ends: filled at build by the host-sort path, on first use
-    // (total_records / export) after a device build
+    // What is built on first use below is guarded by a Once each (host_threads.h): built under its mutex, read by any thread
+    // that has seen done().
+    // host copy of the stored starts / ends: filled at build by the host-sort arm, on first use
+    // (total_records / export / ensure_ntiles) after a device sort
     mutable std::vector<i32> h_starts, h_ends;
-    mutable std::mutex mirror_mu;
-    mutable bool mirror_ready = false;
+    mutable Once mirror;
     gtars_status ensure_mirror() const {
-        std::lock_guard<std::mutex> lk(mirror_mu);
-        if (mirror_ready) return GTARS_OK;
-        h_starts.resize(n);
-        h_ends.resize(n);
-        if (n) {
-            GT_HIP(hipMemcpy(h_starts.data(), starts.p, n * sizeof(i32), hipMemcpyDeviceToHost));
-            GT_HIP(hipMemcpy(h_ends.data(), ends.p, n * sizeof(i32), hipMemcpyDeviceToHost));
-        }
-        mirror_ready = true;
-        return GTARS_OK;
+        return mirror.run([&]() -> gtars_status {
+            StreamFrame fr(nullptr);
+            GT_TRY(fr.download(h_starts, starts.p, n));
+            GT_TRY(fr.download(h_ends, ends.p, n));
+            return fr.drain();
+        });
     }
     DevBuf<i32> starts, ends, values, chrom_maxlen;
     DevBuf<u32> files, chrom_off;
@@ -453,80 +450,78 @@ struct gtars_igd {
     DevBuf<unsigned short> tile_erank;
     DevBuf<u32> tile_tab_r;
     // per chromosome, the reference contig's tile count at nbp = 16384 (min_overlap <= 0 counts), built on first use
-    mutable std::mutex ntiles_mu;
     mutable DevBuf<i32> chrom_ntiles;
-    mutable bool ntiles_ready = false;
+    mutable Once ntiles;
     gtars_status ensure_ntiles() const {
-        std::lock_guard<std::mutex> lk(ntiles_mu);
-        if (ntiles_ready) return GTARS_OK;
-        gtars_status st = ensure_mirror();
-        if (st) return st;
-        std::vector<u32> off(n_chrom + 1, 0);
-        if (n_chrom) GT_HIP(hipMemcpy(off.data(), chrom_off.p, ((size_t)n_chrom + 1) * 4, hipMemcpyDeviceToHost));
-        std::vector<i32> nt(std::max<u32>(n_chrom, 1), 0);
-        for (u32 c = 0; c < n_chrom; ++c) {
-            i32 mx = 0;
-            for (u32 p = off[c]; p < off[c + 1]; ++p) mx = std::max(mx, h_ends[p]);
-            nt[c] = off[c + 1] > off[c] ? (mx - 1) / 16384 + 1 : 0;
-        }
-        DevBuf<i32> d;
-        GT_TRY(d.upload(nt));
-        chrom_ntiles = std::move(d);
-        ntiles_ready = true;
-        return GTARS_OK;
+        return ntiles.run([&]() -> gtars_status {
+            GT_TRY(ensure_mirror());
+            std::vector<u32> off;
+            StreamFrame fr(nullptr);
+            GT_TRY(fr.download(off, chrom_off.p, (size_t)n_chrom + 1));
+            GT_TRY(fr.drain());
+            std::vector<i32> nt(std::max<u32>(n_chrom, 1), 0);
+            for (u32 c = 0; c < n_chrom; ++c) {
+                i32 mx = 0;
+                for (u32 p = off[c]; p < off[c + 1]; ++p) mx = std::max(mx, h_ends[p]);
+                nt[c] = off[c + 1] > off[c] ? (mx - 1) / 16384 + 1 : 0;
+            }
+            return chrom_ntiles.upload(nt);
+        });
     }
     // static routing table (IgdTiles::route_*)
     DevBuf<u32> route_lut, route_base, route_len;
     u32 route_n = 0, route_shift = 0;
     DevBuf<u32> route_flut, route_kq, route_fbase;  // IgdTiles::route_f*
     u32 route_fn = 0, route_fshift = 0;
-    // IgdTiles::pme_file, built on the first binary count with min_overlap == 1
-    mutable std::mutex pme_mu;
+    // IgdTiles::pme_file, built on the first binary count with min_overlap == 1 -- the form such a count takes unless
+    // GTARS_IGD_NO_PME is set (tests / A-B runs: the list of credited files instead)
     mutable DevBuf<i32> pme_file;
-    mutable bool pme_ready = false;
-    gtars_status ensure_pme() const {
-        std::lock_guard<std::mutex> lk(pme_mu);
-        if (pme_ready || n == 0) return GTARS_OK;
-        const size_t wsb = igd_pme_ws_bytes((u32)n);
-        DevBuf<u8> ws;
-        GT_TRY(ws.alloc(wsb));
-        DevBuf<i32> pme;
-        GT_TRY(pme.alloc(n));
-        gtars_status st = igd_build_pme_file(view(), pme.p, ws.p, wsb, nullptr);
-        hipError_t e = hipDeviceSynchronize();
-        if (st || e != hipSuccess) return st ? st : fail(GTARS_ERR_HIP, "pme_file build failed");
-        pme_file = std::move(pme);
-        pme_ready = true;
-        return GTARS_OK;
+    mutable Once pme;
+    static bool pme_allowed() { return !cfg_get("GTARS_IGD_NO_PME"); }
+    static bool pme_serves(int binary, i32 min_overlap) { return binary && min_overlap == 1 && pme_allowed(); }
+    gtars_status ensure_pme_for(int binary, i32 min_overlap) const {
+        if (!pme_serves(binary, min_overlap) || n == 0) return GTARS_OK;
+        return pme.run([&]() -> gtars_status {
+            DevBuf<i32> built;  // (in front of the frame: freed after the frame has drained, whichever way this returns)
+            StreamFrame fr(nullptr);
+            const size_t wsb = igd_pme_ws_bytes((u32)n);
+            u8 *ws;
+            GT_TRY(fr.alloc(&ws, wsb));
+            GT_TRY(built.alloc(n));
+            GT_TRY(igd_build_pme_file(view(), built.p, ws, wsb, fr.st));
+            if (fr.drain()) return fail(GTARS_ERR_HIP, "pme_file build failed");
+            pme_file = std::move(built);
+            return GTARS_OK;
+        });
     }
     // are the records' values all distinct?  (then the per-query "first occurrence of a value" rule keeps every hit);
     // decided on the first per-query call by sorting a copy of the values
-    mutable std::mutex uniq_mu;
-    mutable int values_unique = -1;
+    mutable Once uniq;
+    mutable bool values_unique = true;
     gtars_status ensure_values_unique(bool *out) const {
-        std::lock_guard<std::mutex> lk(uniq_mu);
-        if (values_unique < 0) {
-            if (n < 2) {
-                values_unique = 1;
-            } else {
-                const u32 n32 = (u32)n;
-                DevBuf<u8> buf;
-                const size_t wsb = radix_sort_ws_bytes(n32);
-                GT_TRY(buf.alloc((size_t)n32 * 16 + wsb + 64));
-                u32 *k0 = (u32 *)buf.p, *v0 = k0 + n32, *k1 = v0 + n32, *v1 = k1 + n32;
-                void *ws = (void *)(v1 + n32);
-                u32 *d_dup = (u32 *)((char *)ws + wsb);
-                GT_HIP(hipMemcpy(k0, values.p, (size_t)n32 * 4, hipMemcpyDeviceToDevice));
-                GT_HIP(hipMemset(d_dup, 0, 4));
-                int res = 0;
-                GT_TRY(radix_sort_pairs(k0, v0, k1, v1, n32, 0, 32, ws, wsb, &res, nullptr));
-                GT_TRY(launch_has_adjacent_equal(res ? k1 : k0, n32, d_dup, nullptr));
-                u32 h = 1;
-                GT_HIP(hipMemcpy(&h, d_dup, 4, hipMemcpyDeviceToHost));
-                values_unique = h ? 0 : 1;
-            }
-        }
-        *out = values_unique == 1;
+        GT_TRY(uniq.run([&]() -> gtars_status {
+            if (n < 2) return GTARS_OK;
+            const u32 n32 = (u32)n, zero = 0;
+            u32 h = 1;
+            StreamFrame fr(nullptr);
+            const size_t wsb = radix_sort_ws_bytes(n32);
+            u32 *k0, *d_dup;
+            u8 *ws;
+            GT_TRY(fr.alloc(&k0, (size_t)n32 * 4));
+            GT_TRY(fr.alloc(&ws, wsb));
+            GT_TRY(fr.alloc(&d_dup, 1));
+            u32 *v0 = k0 + n32, *k1 = v0 + n32, *v1 = k1 + n32;
+            GT_HIP(hipMemcpyAsync(k0, values.p, (size_t)n32 * 4, hipMemcpyDeviceToDevice, fr.st));
+            GT_TRY(fr.upload_to(d_dup, &zero, 1));
+            int res = 0;
+            GT_TRY(radix_sort_pairs(k0, v0, k1, v1, n32, 0, 32, ws, wsb, &res, fr.st));
+            GT_TRY(launch_has_adjacent_equal(res ? k1 : k0, n32, d_dup, fr.st));
+            GT_TRY(fr.download(&h, d_dup, 1));
+            GT_TRY(fr.drain());
+            values_unique = !h;
+            return GTARS_OK;
+        }));
+        *out = values_unique;
         return GTARS_OK;
     }
     u32 n_tiles = 0;
@@ -538,7 +533,7 @@ struct gtars_igd {
         t.carry = tile_carry.p;
         t.bnd = tile_bnd.p;
         t.chrom_tile_off = chrom_tile_off.p;
-        t.pme_file = pme_ready && !cfg_get("GTARS_IGD_NO_PME") ? pme_file.p : nullptr;
+        t.pme_file = pme.done() && pme_allowed() ? pme_file.p : nullptr;
         t.pm = tile_pm.p;
         t.files16 = tile_files16.p;
         t.tab = tile_tab.p;
@@ -558,8 +553,8 @@ struct gtars_igd {
         t.n_tiles = n_tiles;
         return t;
     }
-    // after tile_first / tile_cnt / tile_chrom, starts and chrom_maxlen are on the device
-    gtars_status finish_tiles(const std::vector<u32> &tch) {
+    // after tile_first / tile_cnt / tile_chrom / tile_carry and the records are on the device or queued on the build's frame
+    gtars_status finish_tiles(StreamFrame &fr, const std::vector<u32> &tch) {
         std::vector<u32> cto(n_chrom + 1, 0);
         for (u32 c : tch) cto[c + 1]++;
         for (u32 c = 0; c < n_chrom; ++c) cto[c + 1] += cto[c];
@@ -567,14 +562,14 @@ struct gtars_igd {
         if (st) return st;
         std::vector<u32> zero(std::max<u32>(n_tiles, 1), 0);
         if ((st = tile_bnd.upload(zero))) return st;
-        if ((st = launch_igd_tile_bounds(view(), tile_first.p, tile_cnt.p, tile_chrom.p, n_tiles, tile_bnd.p, nullptr))) return st;
+        if ((st = launch_igd_tile_bounds(view(), tile_first.p, tile_cnt.p, tile_chrom.p, n_tiles, tile_bnd.p, fr.st))) return st;
         if (n_tiles && n_files <= 65535) {
             // one pass over the database: prefix maxima, u16 file ids, search tables (what the sweep streams with the records)
             GT_TRY(tile_pm.alloc(n));
             GT_TRY(tile_files16.alloc(((size_t)n + 1) & ~(size_t)1));  // (u16 pairs: whole words)
             GT_TRY(tile_tab.alloc((size_t)n_tiles * IGD_TILE_TAB_WORDS));
             GT_TRY(launch_igd_tile_tables(view(), tile_first.p, tile_cnt.p, tile_chrom.p, tile_carry.p, n_tiles, tile_pm.p, tile_files16.p,
-                                          tile_tab.p, nullptr));
+                                          tile_tab.p, fr.st));
             // the rank-histogram form's blocks (sorted ends + eranks: 6 bytes per staged record, ~7 per record).  Not for a pieces
             // view (its continuation rule is not a rank difference) and not under GTARS_IGD_NO_RANK_TABLES (tests / A-B runs)
             if (!piece_flags && n_files <= 16384 && !cfg_flag("GTARS_IGD_NO_RANK_TABLES")) {
@@ -582,7 +577,7 @@ struct gtars_igd {
                 if (tile_ends_sorted.try_alloc(slots) == hipSuccess && tile_erank.try_alloc(slots) == hipSuccess &&
                     tile_tab_r.try_alloc((size_t)n_tiles * IGD_TILE_TABR_WORDS) == hipSuccess) {
                     GT_TRY(launch_igd_tile_tables_rank(view(), tile_first.p, tile_cnt.p, tile_chrom.p, n_tiles, tile_ends_sorted.p,
-                                                       tile_erank.p, tile_tab_r.p, nullptr));
+                                                       tile_erank.p, tile_tab_r.p, fr.st));
                 } else {
                     (void)hipGetLastError();  // out of device memory: the database keeps the walked form
                     tile_ends_sorted.reset();
@@ -591,11 +586,13 @@ struct gtars_igd {
                 }
             }
         }
-        GT_HIP(hipDeviceSynchronize());
-        if (n_tiles && n_tiles < 65535) {
+        // (the wait: everything the build has queued is done before the handle is handed out)
+        const bool routed = n_tiles && n_tiles < 65535;
+        std::vector<u32> hb;
+        if (routed) GT_TRY(fr.download(hb, tile_bnd.p, n_tiles));
+        GT_TRY(fr.drain());
+        if (routed) {
             // routing table over (chromosome, start >> shift), from the tile bounds the device has just computed
-            std::vector<u32> hb(n_tiles);
-            GT_HIP(hipMemcpy(hb.data(), tile_bnd.p, (size_t)n_tiles * 4, hipMemcpyDeviceToHost));
             std::vector<u32> len(n_chrom, 0), base(n_chrom + 1, 0);
             for (u32 c = 0; c < n_chrom; ++c)
                 if (cto[c + 1] > cto[c]) len[c] = hb[cto[c + 1] - 1];
@@ -673,7 +670,7 @@ struct gtars_igd {
         v.values = values.p;
         v.chrom_off = chrom_off.p;
         v.chrom_maxlen = chrom_maxlen.p;
-        v.chrom_ntiles = ntiles_ready ? chrom_ntiles.p : nullptr;
+        v.chrom_ntiles = ntiles.done() ? chrom_ntiles.p : nullptr;
         v.pm = cfg_get("GTARS_IGD_NO_PM_START") ? nullptr : tile_pm.p;
         v.n_chrom = n_chrom;
         v.n = (u32)n;
@@ -1859,15 +1856,11 @@ gtars_status gtars_count_overlaps(const gtars_index_t *ix, const uint32_t *qc, c
 
 static gtars_status bits_count_prepare(const gtars_index_t *ix) {
     if (ix->kind != GTARS_KIND_BITS) return fail(GTARS_ERR_INVALID_ARG, "Bits::count needs a Bits-kind index");
-    std::lock_guard<std::mutex> lk(ix->ends_mu);
-    if (ix->ends_ready) return GTARS_OK;
-    std::vector<u32> e(ix->h_ends);
-    for (u32 c = 0; c < ix->n_chrom; ++c) std::sort(e.begin() + ix->h_chrom_off[c], e.begin() + ix->h_chrom_off[c + 1]);
-    DevBuf<u32> d;
-    GT_TRY(d.upload(e));
-    ix->ends_sorted = std::move(d);
-    ix->ends_ready = true;
-    return GTARS_OK;
+    return ix->ends_built.run([&]() -> gtars_status {
+        std::vector<u32> e(ix->h_ends);
+        for (u32 c = 0; c < ix->n_chrom; ++c) std::sort(e.begin() + ix->h_chrom_off[c], e.begin() + ix->h_chrom_off[c + 1]);
+        return ix->ends_sorted.upload(e);
+    });
 }
 
 gtars_status gtars_bits_count_device(const gtars_index_t *ix, const uint32_t *d_qc, const uint32_t *d_qs,
@@ -2151,132 +2144,74 @@ static gtars_status gtars_igd_build_core(const uint32_t *chrom, const int32_t *s
     gtars_status st = require_device();
     if (st) return st;
     if (n >= 0xFFFFFFF0ull) return fail(GTARS_ERR_INVALID_ARG, "too many records");
-    if (use_device_sort(n)) {
-        // ---- large builds: one sequential host pass (drop rule, bounds, per-chromosome counts and max
-        // length), then upload, radix sort and gather on the device.  Dropped records get the key
-        // n_chrom, so they sort behind every chromosome and are cut off.
-        std::vector<u32> kc(n), hoff(n_chrom + 1, 0);
-        std::vector<i32> hml(n_chrom, 0);
-        u64 kept = 0;
-        for (u64 i = 0; i < n; ++i) {
-            // Igd::add drop rule (igd.rs:114-116)
-            if (start[i] < 0 || end[i] < 0 || start[i] >= end[i]) {
-                kc[i] = n_chrom;
-                continue;
-            }
-            if (chrom[i] >= n_chrom) return fail(GTARS_ERR_INVALID_ARG, "record chromosome id >= n_chrom");
-            if ((file_idx[i] & fmask) >= n_files) return fail(GTARS_ERR_INVALID_ARG, "record file_idx >= n_files");
-            kc[i] = chrom[i];
-            hoff[chrom[i] + 1]++;
-            hml[chrom[i]] = std::max(hml[chrom[i]], end[i] - start[i]);
-            ++kept;
-        }
-        for (u32 c = 0; c < n_chrom; ++c) hoff[c + 1] += hoff[c];
-        std::unique_ptr<gtars_igd> g(new gtars_igd());
-        (void)hipGetDevice(&g->device);
-        g->piece_flags = piece_flags;
-        g->n_chrom = n_chrom;
-        g->n_files = n_files;
-        g->n = kept;
-        const u32 n32 = (u32)n;
-        // (a pieces view serves counts only: no values column, here or on the host path below)
-        const bool with_values = !piece_flags;
-        DevBuf<u32> in;
-        GT_TRY(in.alloc((size_t)n * (with_values ? 6 : 5)));
-        u32 *d_kc = in.p, *d_s = d_kc + n, *d_e = d_s + n, *d_f = d_e + n, *d_v = d_f + n, *d_perm = with_values ? d_v + n : d_v;
-        if (hipMemcpy(d_kc, kc.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_s, start, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_e, end, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_f, file_idx, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            (!with_values ? hipSuccess
-                          : value ? hipMemcpy(d_v, value, n * 4, hipMemcpyHostToDevice) : hipMemset(d_v, 0, n * 4)) != hipSuccess)
-            return fail(GTARS_ERR_HIP, "IGD build: upload failed");
-        // chromosome-major, then start, ties in insertion order (finalize: stable sort by start, igd.rs:157-167);
-        // kept starts are >= 0, so u32 order == i32 order
-        const size_t ws_bytes = device_sort_perm_ws_bytes(n32);
-        DevBuf<u8> ws;
-        GT_TRY(ws.alloc(ws_bytes));
-        GT_TRY(device_sort_perm_ws(d_kc, d_s, nullptr, n32, n_chrom + 1, d_perm, ws.p, ws_bytes, nullptr));
-        GT_TRY(g->starts.alloc(kept));
-        GT_TRY(g->ends.alloc(kept));
-        GT_TRY(g->files.alloc(kept));
-        if (with_values) GT_TRY(g->values.alloc(kept));
-        const u32 k32 = (u32)kept;
-        if ((st = device_gather_u32(d_s, d_perm, k32, (u32 *)g->starts.p, nullptr))) return st;
-        if ((st = device_gather_u32(d_e, d_perm, k32, (u32 *)g->ends.p, nullptr))) return st;
-        if ((st = device_gather_u32(d_f, d_perm, k32, g->files.p, nullptr))) return st;
-        if (with_values && (st = device_gather_u32(d_v, d_perm, k32, (u32 *)g->values.p, nullptr))) return st;
-        if (hipDeviceSynchronize() != hipSuccess) return fail(GTARS_ERR_HIP, "IGD build: device sort failed");
-        std::vector<u32> tf, tc, tch;
-        for (u32 c = 0; c < n_chrom; ++c)
-            for (u32 p = hoff[c]; p < hoff[c + 1]; p += IGD_TILE_RECORDS) {
-                tf.push_back(p);
-                tc.push_back(std::min<u32>(IGD_TILE_RECORDS, hoff[c + 1] - p));
-                tch.push_back(c);
-            }
-        g->n_tiles = (u32)tf.size();
-        st = g->tile_first.upload(tf);
-        if (!st) st = g->tile_cnt.upload(tc);
-        if (!st) st = g->tile_chrom.upload(tch);
-        if (!st) st = g->chrom_off.upload(hoff);
-        if (!st) st = g->chrom_maxlen.upload(hml);
-        if (st) return st;
-        {
-            // tile_carry: per-tile maximum end on the device, exclusive running maximum per chromosome on the host
-            std::vector<i32> tmax(g->n_tiles, 0), carry(g->n_tiles, 0);
-            DevBuf<i32> d_tmax;
-            GT_TRY(d_tmax.alloc(g->n_tiles));
-            GT_TRY(launch_igd_tile_max_end(g->ends.p, g->tile_first.p, g->tile_cnt.p, g->n_tiles, d_tmax.p, nullptr));
-            if (g->n_tiles && hipMemcpy(tmax.data(), d_tmax.p, (size_t)g->n_tiles * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(GTARS_ERR_HIP, "IGD build: tile maxima readback failed");
-            i32 run = 0;
-            for (u32 t = 0; t < g->n_tiles; ++t) {
-                if (t == 0 || tch[t] != tch[t - 1]) run = 0;
-                carry[t] = run;
-                run = std::max(run, tmax[t]);
-            }
-                GT_TRY(g->tile_carry.upload(carry));
-        }
-        GT_TRY(g->finish_tiles(tch));
-        *out = g.release();
-        return GTARS_OK;
-    }
-    // ---- small builds: host stable sort
-    // Igd::add drop rule (igd.rs:114-116)
-    std::vector<u32> keep;
-    keep.reserve(n);
+    // One sequential host pass: the drop rule, the two range checks, per-chromosome counts and longest record.  A dropped
+    // record gets the key n_chrom: behind every chromosome in the stored order, where it is cut off.
+    std::vector<u32> kc(n), hoff(n_chrom + 1, 0), perm;
+    std::vector<i32> hml(n_chrom, 0), tmax;
+    u64 kept = 0;
     for (u64 i = 0; i < n; ++i) {
-        if (start[i] < 0 || end[i] < 0 || start[i] >= end[i]) continue;
+        // Igd::add drop rule (igd.rs:114-116)
+        if (start[i] < 0 || end[i] < 0 || start[i] >= end[i]) {
+            kc[i] = n_chrom;
+            continue;
+        }
         if (chrom[i] >= n_chrom) return fail(GTARS_ERR_INVALID_ARG, "record chromosome id >= n_chrom");
         if ((file_idx[i] & fmask) >= n_files) return fail(GTARS_ERR_INVALID_ARG, "record file_idx >= n_files");
-        keep.push_back((u32)i);
+        kc[i] = chrom[i];
+        hoff[chrom[i] + 1]++;
+        hml[chrom[i]] = std::max(hml[chrom[i]], end[i] - start[i]);
+        ++kept;
     }
-    // chromosome-major, then start, ties in insertion order (finalize: stable sort by start, igd.rs:157-167)
-    std::stable_sort(keep.begin(), keep.end(), [&](u32 a, u32 b) {
-        if (chrom[a] != chrom[b]) return chrom[a] < chrom[b];
-        return start[a] < start[b];
-    });
+    for (u32 c = 0; c < n_chrom; ++c) hoff[c + 1] += hoff[c];
+    // (the handle and every host block a queued copy uses are declared in front of the frame: they outlive its last wait)
     std::unique_ptr<gtars_igd> g(new gtars_igd());
     (void)hipGetDevice(&g->device);
     g->piece_flags = piece_flags;
     g->n_chrom = n_chrom;
     g->n_files = n_files;
-    g->n = keep.size();
-    std::vector<i32> hv(g->n), hml(n_chrom, 0);
-    std::vector<u32> hf(g->n), hoff(n_chrom + 1, 0);
-    g->h_starts.resize(g->n);
-    g->h_ends.resize(g->n);
-    g->mirror_ready = true;
-    for (u64 p = 0; p < g->n; ++p) {
-        const u32 i = keep[p];
-        g->h_starts[p] = start[i];
-        g->h_ends[p] = end[i];
-        hv[p] = value ? value[i] : 0;
-        hf[p] = file_idx[i];
-        hoff[chrom[i] + 1]++;
-        hml[chrom[i]] = std::max(hml[chrom[i]], end[i] - start[i]);
+    g->n = kept;
+    const u32 n32 = (u32)n, k32 = (u32)kept;
+    const bool with_values = !piece_flags;  // (a pieces view serves counts only: no values column)
+    StreamFrame fr(nullptr);
+    u32 *d_kc;
+    GT_TRY(fr.alloc(&d_kc, (size_t)n * (with_values ? 6 : 5)));
+    u32 *d_s = d_kc + n, *d_e = d_s + n, *d_f = d_e + n, *d_v = d_f + n, *d_perm = with_values ? d_v + n : d_v;
+    if (fr.upload_to(d_s, (const u32 *)start, n) || fr.upload_to(d_e, (const u32 *)end, n) || fr.upload_to(d_f, file_idx, n) ||
+        (with_values && value && fr.upload_to(d_v, (const u32 *)value, n)))
+        return fail(GTARS_ERR_HIP, "IGD build: upload failed");
+    // The stored order -- chromosome-major, then start, ties in insertion order (finalize: stable sort by start,
+    // igd.rs:157-167) -- as d_perm[p] = input row of stored position p < kept: by the device radix sort (K1) or std::stable_sort
+    if (use_device_sort(n)) {
+        // (kept starts are >= 0, so u32 order == i32 order)
+        const size_t ws_bytes = device_sort_perm_ws_bytes(n32);
+        u8 *ws;
+        GT_TRY(fr.alloc(&ws, ws_bytes));
+        if (fr.upload_to(d_kc, kc.data(), n)) return fail(GTARS_ERR_HIP, "IGD build: upload failed");
+        GT_TRY(device_sort_perm_ws(d_kc, d_s, nullptr, n32, n_chrom + 1, d_perm, ws, ws_bytes, fr.st));
+    } else {
+        perm.reserve(kept);
+        for (u64 i = 0; i < n; ++i)
+            if (kc[i] != n_chrom) perm.push_back((u32)i);
+        std::stable_sort(perm.begin(), perm.end(), [&](u32 a, u32 b) {
+            if (kc[a] != kc[b]) return kc[a] < kc[b];
+            return start[a] < start[b];
+        });
+        if (fr.upload_to(d_perm, perm.data(), kept)) return fail(GTARS_ERR_HIP, "IGD build: upload failed");
+        // (the order is on the host here: the mirror of the stored starts / ends comes for free)
+        g->h_starts.resize(kept);
+        g->h_ends.resize(kept);
+        for (u64 p = 0; p < kept; ++p) g->h_starts[p] = start[perm[p]], g->h_ends[p] = end[perm[p]];
+        (void)g->mirror.run([] { return GTARS_OK; });
     }
-    for (u32 c = 0; c < n_chrom; ++c) hoff[c + 1] += hoff[c];
+    GT_TRY(g->starts.alloc(kept));
+    GT_TRY(g->ends.alloc(kept));
+    GT_TRY(g->files.alloc(kept));
+    if (with_values) GT_TRY(g->values.alloc(kept));
+    GT_TRY(device_gather_u32(d_s, d_perm, k32, (u32 *)g->starts.p, fr.st));
+    GT_TRY(device_gather_u32(d_e, d_perm, k32, (u32 *)g->ends.p, fr.st));
+    GT_TRY(device_gather_u32(d_f, d_perm, k32, g->files.p, fr.st));
+    if (with_values && value) GT_TRY(device_gather_u32(d_v, d_perm, k32, (u32 *)g->values.p, fr.st));
+    if (with_values && !value && kept) GT_HIP(hipMemsetAsync(g->values.p, 0, kept * 4, fr.st));  // (no values given: all 0)
     std::vector<u32> tf, tc, tch;
     for (u32 c = 0; c < n_chrom; ++c)
         for (u32 p = hoff[c]; p < hoff[c + 1]; p += IGD_TILE_RECORDS) {
@@ -2285,27 +2220,26 @@ static gtars_status gtars_igd_build_core(const uint32_t *chrom, const int32_t *s
             tch.push_back(c);
         }
     g->n_tiles = (u32)tf.size();
+    GT_TRY(g->tile_first.upload(tf));
+    GT_TRY(g->tile_cnt.upload(tc));
+    GT_TRY(g->tile_chrom.upload(tch));
+    GT_TRY(g->chrom_off.upload(hoff));
+    GT_TRY(g->chrom_maxlen.upload(hml));
+    // tile_carry: per-tile maximum end on the device, exclusive running maximum per chromosome on the host.  (The wait for
+    // the maxima is also the wait for the sort and the gathers in front of them.)
     std::vector<i32> carry(g->n_tiles, 0);
-    {
-        i32 run = 0;
-        for (u32 t = 0; t < g->n_tiles; ++t) {
-            if (t == 0 || tch[t] != tch[t - 1]) run = 0;
-            carry[t] = run;
-            for (u32 p = tf[t]; p < tf[t] + tc[t]; ++p) run = std::max(run, g->h_ends[p]);
-        }
+    i32 *d_tmax;
+    GT_TRY(fr.alloc(&d_tmax, g->n_tiles));
+    GT_TRY(launch_igd_tile_max_end(g->ends.p, g->tile_first.p, g->tile_cnt.p, g->n_tiles, d_tmax, fr.st));
+    if (fr.download(tmax, d_tmax, g->n_tiles) || fr.drain()) return fail(GTARS_ERR_HIP, "IGD build: tile maxima readback failed");
+    i32 run = 0;
+    for (u32 t = 0; t < g->n_tiles; ++t) {
+        if (t == 0 || tch[t] != tch[t - 1]) run = 0;
+        carry[t] = run;
+        run = std::max(run, tmax[t]);
     }
-    st = g->tile_carry.upload(carry);
-    if (!st) st = g->starts.upload(g->h_starts);
-    if (!st) st = g->tile_first.upload(tf);
-    if (!st) st = g->tile_cnt.upload(tc);
-    if (!st) st = g->tile_chrom.upload(tch);
-    if (!st) st = g->ends.upload(g->h_ends);
-    if (!st && !piece_flags) st = g->values.upload(hv);  // (a pieces view serves counts only)
-    if (!st) st = g->files.upload(hf);
-    if (!st) st = g->chrom_off.upload(hoff);
-    if (!st) st = g->chrom_maxlen.upload(hml);
-    if (!st) st = g->finish_tiles(tch);
-    if (st) return st;
+    GT_TRY(g->tile_carry.upload(carry));
+    GT_TRY(g->finish_tiles(fr, tch));
     *out = g.release();
     return GTARS_OK;
 }
@@ -2427,7 +2361,7 @@ gtars_status gtars_igd_build(const uint32_t *chrom, const int32_t *start, const 
 // pme_file form)
 static const gtars_igd *igd_count_target(const gtars_igd *g, int32_t min_overlap, int binary) {
     if (!g->pieces || min_overlap != 1) return g;
-    if (binary && cfg_get("GTARS_IGD_NO_PME")) return g;
+    if (binary && !gtars_igd::pme_serves(binary, min_overlap)) return g;  // (the credited-file form: flat layout only)
     return g->pieces.get();
 }
 
@@ -2506,10 +2440,9 @@ gtars_status gtars_igd_count_device(const gtars_igd_t *g, const uint32_t *d_qc, 
         if (t != g && g_prof_on) g_prof_entries[prof_entry("igd_pieces_view")].launches += 1;  // (a fact for the tests)
         g = t;
     }
+    if ((st = g->ensure_pme_for(binary, min_overlap))) return st;
     if (igd_sweep_supported(g->view(), nq)) {
         // large batch: group the queries by owner tile once, stream the database once (igd_sweep.hip)
-        const bool no_pme = cfg_get("GTARS_IGD_NO_PME") != nullptr;  // tests / A-B runs: the credited-file list instead
-        if (binary && min_overlap == 1 && !no_pme && (st = g->ensure_pme())) return st;
         Workspace &ws = tls_workspace(2, (hipStream_t)stream);
         st = ws.reserve(igd_sweep_ws_bytes(nq, g->n_tiles, g->n_chrom));
         if (st) return st;
@@ -2517,7 +2450,6 @@ gtars_status gtars_igd_count_device(const gtars_igd_t *g, const uint32_t *d_qc, 
                                 (hipStream_t)stream, ws.igd_calls++);
     }
     // small batch: one thread per query (kernels.hip); binary counts with min_overlap == 1 through pme_file as well
-    if (binary && min_overlap == 1 && !cfg_get("GTARS_IGD_NO_PME") && (st = g->ensure_pme())) return st;
     return launch_igd_count(g->view(), g->tiles().pme_file, d_qc, d_qs, d_qe, nq, min_overlap, binary, d_hits, (hipStream_t)stream,
                             g->tiles().pm);
 }
@@ -2556,8 +2488,7 @@ gtars_status gtars_igd_count_sets_device(const gtars_igd_t *g, const uint32_t *d
             st = gtars_igd_count_device(g, d_qc + lo, d_qs + lo, d_qe + lo, n, min_overlap, binary, d_hits + (size_t)k0 * F, stream);
             if (st) return st;
         } else {
-            const bool no_pme = cfg_get("GTARS_IGD_NO_PME") != nullptr;
-            if (binary && min_overlap == 1 && !no_pme && (st = gs->ensure_pme())) return st;
+            if ((st = gs->ensure_pme_for(binary, min_overlap))) return st;
             Workspace &ws = tls_workspace(2, (hipStream_t)stream);
             st = ws.reserve(igd_sweep_ws_bytes(n, gs->n_tiles, gs->n_chrom));
             if (st) return st;

@@ -81,6 +81,27 @@ void parallel_for(size_t n, unsigned threads, size_t chunk, F &&body) {
     if (first) std::rethrow_exception(first);
 }
 
+// Something built on first use and read by any thread afterwards.  run(build): under the mutex, returns 0 at once when the
+// build has succeeded before; otherwise calls build(), whose status it returns -- 0 publishes what build() wrote (release),
+// anything else leaves the guard clear, so a later call tries again.  done() is the matching acquire load: a thread that
+// sees true also sees everything the successful build() wrote, without taking the mutex.
+class Once {
+  public:
+    template <class F>
+    auto run(F &&build) -> decltype(build()) {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (done_.load(std::memory_order_relaxed)) return {};
+        const auto st = build();
+        if (!st) done_.store(true, std::memory_order_release);
+        return st;
+    }
+    bool done() const { return done_.load(std::memory_order_acquire); }
+
+  private:
+    std::mutex mu_;
+    std::atomic<bool> done_{false};
+};
+
 // `parts` + 1 ascending offsets into text[0, n): the first is 0, the last n, every other one lies just behind a '\n' (or is n) --
 // the text cut at line starts into `parts` chunks of about n / parts bytes.  A cut never lies in front of the one before it:
 // behind a line longer than a chunk the next cut is the next line start.

@@ -1,6 +1,7 @@
 // host_threads_check.cpp -- csrc/host_threads.h on its own, meant to be built with -fsanitize=thread (tests/test_host_cpu.py):
 // parallel_for visits every index once and brings a body's exception to the caller with every thread joined, cut_at_lines cuts
-// at line starts, JoinedThreads stops and joins on the way out of an exception.
+// at line starts, JoinedThreads stops and joins on the way out of an exception, Once builds until a build succeeds and
+// publishes what it built to readers that only look at done().
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread -o host_threads_check host_threads_check.cpp && ./host_threads_check
 #include "../../gtars_amd/csrc/host_threads.h"
 
@@ -209,8 +210,48 @@ static void joined_threads() {
     CHECK(stops == 1);
 }
 
+// Eight threads call run() on one Once at the same moment; the builder fails on its first call and succeeds on its second.
+// Two readers never take the mutex: they spin on done() and then read what the builder stored (plain int: a done() that
+// did not order the read behind the builder's write is a race ThreadSanitizer reports).
+static void once_guard() {
+    gtars::Once once;
+    int value = 0;
+    std::atomic<int> builds{0}, failed{0}, succeeded{0};
+    std::atomic<bool> go{false};
+    auto builder = [&]() -> int {
+        if (++builds == 1) return 7;  // (the guard stays clear: the next caller builds again)
+        value = 42;
+        return 0;
+    };
+    {
+        JoinedThreads th([] {});
+        th.start(8, [&] {
+            while (!go.load()) std::this_thread::yield();
+            const int st = once.run(builder);
+            if (st) {
+                CHECK(st == 7);
+                ++failed;
+            } else {
+                CHECK(once.done() && value == 42);
+                ++succeeded;
+            }
+        });
+        th.start(2, [&] {
+            while (!once.done()) std::this_thread::yield();
+            CHECK(value == 42);
+        });
+        CHECK(!once.done());
+        go.store(true);
+    }
+    CHECK(builds == 2);  // one failure, one success, six calls that found it done
+    CHECK(failed == 1 && succeeded == 7);
+    CHECK(once.run([&]() -> int { return ++builds; }) == 0);  // done: returns 0 and does not call the builder
+    CHECK(builds == 2 && once.done() && value == 42);
+}
+
 int main() {
     coverage();
+    for (int rep = 0; rep < 20; ++rep) once_guard();
     for (int rep = 0; rep < 20; ++rep) {
         one_side_throws(false);
         one_side_throws(true);

@@ -750,6 +750,101 @@ def test_device_sort_builds_the_same_index(ga, monkeypatch, n, n_chrom, span):
     assert gq.tolist() == oq.tolist() and gs.tolist() == os_.tolist()
 
 
+def test_igd_build_is_the_same_under_either_sort(ga, monkeypatch):
+    """gtars_igd_build orders the kept records by the device radix sort or by std::stable_sort on the host (GTARS_DEVICE_SORT=1 /
+    0 force one) and does everything else once: both handles must hold exactly the restatement below -- the kept rows (Igd::add
+    drop rule, igd.rs:114-116) in np.lexsort((start, chrom)) order, which is stable (finalize, igd.rs:157-167) -- and count like
+    the oracle through every lazily built table.  Six chromosomes with 0 / 1 / 2047 / 2048 / 2049 / 4097 kept records (the tile
+    holds 2048), starts in 0..300 so that nearly every start is tied, values = input row so that insertion order shows, ~5 % of
+    the rows invalid in each of the rule's three ways on every chromosome.  Then the same database with 16-bp pieces (the shared
+    body with piece flags), and the two range checks, which fail the build with the same text on both arms."""
+    _lib = ga._lib
+    lib, ptr = _lib.lib, _lib.ptr
+    rng = np.random.default_rng(2048)
+    kept_per_chrom, F = [0, 1, 2047, 2048, 2049, 4097], 7
+    n_chrom, n_kept = len(kept_per_chrom), sum(kept_per_chrom)
+    n_bad = 3 * 600
+    c = np.concatenate([np.repeat(np.arange(n_chrom), kept_per_chrom), rng.integers(0, n_chrom, n_bad)]).astype(np.uint32)
+    n = len(c)
+    s = rng.integers(0, 301, n).astype(np.int32)
+    e = (s + rng.integers(1, 201, n)).astype(np.int32)
+    bad = n_kept + rng.permutation(n_bad)
+    s[bad[:600]] = -1 - rng.integers(0, 50, 600)                    # start < 0
+    e[bad[600:1200]] = -1 - rng.integers(0, 50, 600)                # end < 0
+    e[bad[1200:]] = np.maximum(s[bad[1200:]] - rng.integers(0, 3, 600), 0)  # start >= end, both >= 0
+    mix = rng.permutation(n)
+    c, s, e = c[mix], s[mix], e[mix]
+    f = rng.integers(0, F, n).astype(np.uint32)
+    v = np.arange(n, dtype=np.int32)
+    ok = np.flatnonzero((s >= 0) & (e >= 0) & (s < e))
+    assert len(ok) == n_kept and np.bincount(c[ok], minlength=n_chrom).tolist() == kept_per_chrom
+    for dropped in (s < 0, e < 0, (s >= 0) & (e >= 0) & (s >= e)):
+        assert dropped.sum() == 600 and len(np.unique(c[dropped])) == n_chrom  # each way, on every chromosome
+    stored = ok[np.lexsort((s[ok], c[ok]))]
+    want_cols = [c[stored], s[stored], e[stored], v[stored], f[stored]]
+    o = oracle.Igd()
+    o.add_arrays(c, s, e, v, f)
+    o.n_files = F
+    o.finalize()
+    qc, qs, qe = _random_query_set(rng, 3000, n_chrom, 520, 60)
+    i31 = (qs < 2**31) & (qe < 2**31)  # (the per-query call takes i32 coordinates)
+    pq = (qc[i31], qs[i31], qe[i31])
+    want = {"pairwise": o.count_set_overlaps(qc, qs, qe, 1, n_files=F), "binary 1": o.count_region_hits(qc, qs, qe, 1, n_files=F),
+            "binary 0": o.count_region_hits(qc, qs, qe, 0, n_files=F), "per query": o.count_overlaps_per_query(*pq, 1)}
+
+    def build(sort):
+        monkeypatch.setenv("GTARS_DEVICE_SORT", sort)
+        return ga.IgdIndex(c, s, e, f, v, n_chrom=n_chrom, n_files=F)
+
+    def counts(g):
+        return {"pairwise": g.count_set_overlaps(qc, qs, qe, 1), "binary 1": g.count_region_hits(qc, qs, qe, 1),
+                "binary 0": g.count_region_hits(qc, qs, qe, 0), "per query": g.count_overlaps_per_query(*pq, 1)}
+
+    handles = {sort: build(sort) for sort in ("0", "1")}
+    for sort, g in handles.items():
+        got_cols = [np.zeros(n_kept, dtype=np.uint32)] + [np.zeros(n_kept, dtype=np.int32) for _ in range(3)] + [np.zeros(n_kept, dtype=np.uint32)]
+        _lib.check(lib.gtars_igd_export(g._h, *[ptr(a) for a in got_cols]))
+        for name, got, exp in zip(("chrom", "start", "end", "value", "file_idx"), got_cols, want_cols):
+            assert np.array_equal(got, exp), (sort, name, np.flatnonzero(got != exp)[:5].tolist())
+        assert len(g) == n_kept and int(lib.gtars_igd_n_files(g._h)) == F
+        assert g.total_records(16384) == o.total_records() == int(((e[ok] - 1) // 16384 - s[ok] // 16384 + 1).sum())
+    for sweep_min in ("1", None):
+        if sweep_min:
+            monkeypatch.setenv("GTARS_IGD_SWEEP_MIN", sweep_min)
+        else:
+            monkeypatch.delenv("GTARS_IGD_SWEEP_MIN")
+        for sort, g in handles.items():
+            for name, got in counts(g).items():
+                assert np.array_equal(got, want[name]), (sort, sweep_min, name)
+    # the same body with piece flags: almost every record is cut into 16-bp pieces; pme_file of the pieces view is built by the
+    # sweep on one arm and by the per-query kernel on the other
+    monkeypatch.setenv("GTARS_IGD_PIECE_BP", "16")
+    pieces = {sort: build(sort) for sort in ("0", "1")}
+    for sort, g in pieces.items():
+        for sweep_first in (sort == "0", sort != "0"):
+            if sweep_first:
+                monkeypatch.setenv("GTARS_IGD_SWEEP_MIN", "1")
+            else:
+                monkeypatch.delenv("GTARS_IGD_SWEEP_MIN", raising=False)
+            lib.gtars_prof_reset()
+            lib.gtars_prof_enable(1)
+            got_p, got_b = g.count_set_overlaps(qc, qs, qe, 1), g.count_region_hits(qc, qs, qe, 1)
+            prof = _lib.prof_read()
+            lib.gtars_prof_enable(0)
+            assert prof.get("igd_pieces_view", {"launches": 0})["launches"] == 2, (sort, sorted(prof))
+            assert np.array_equal(got_p, want["pairwise"]) and np.array_equal(got_b, want["binary 1"]), (sort, sweep_first)
+    # a kept row out of range fails the build, whichever arm sorts
+    row = int(ok[0])
+    for sort in ("0", "1"):
+        monkeypatch.setenv("GTARS_DEVICE_SORT", sort)
+        c2, f2 = c.copy(), f.copy()
+        c2[row], f2[row] = n_chrom, F
+        with pytest.raises(ValueError, match="^record chromosome id >= n_chrom$"):
+            ga.IgdIndex(c2, s, e, f, v, n_chrom=n_chrom, n_files=F)
+        with pytest.raises(ValueError, match="^record file_idx >= n_files$"):
+            ga.IgdIndex(c, s, e, f2, v, n_chrom=n_chrom, n_files=F)
+
+
 @pytest.mark.parametrize("top_max", ["64", "300", "4096"])
 def test_lds_path_with_sampled_top_level(ga, monkeypatch, top_max):
     """Universes too large for the LDS top level use a sampled top (top_shift > 0) plus a short search of
@@ -2283,8 +2378,10 @@ def test_handles_carry_their_device_and_every_entry_point_checks_it(ga):
 
 def test_igd_counts_from_four_host_threads_on_one_handle(ga, monkeypatch):
     """One Igd handle, four host threads, all of them starting at once on a handle nobody has queried yet: the handle's lazily
-    built, mutex-guarded members (pme_file for the binary sweep, the contig tile counts for min_overlap <= 0, the host mirror,
-    the values-unique flag) are built under contention, every thread has its own stream workspace.  Every result against the
+    built members (pme_file for the binary sweep, the contig tile counts for min_overlap <= 0, the host mirror, the
+    values-unique flag -- each behind a Once of csrc/host_threads.h: built under its mutex, published by a release store that
+    tiles() / view() read with acquire) are built under contention, every thread has its own stream workspace.  That the
+    guard itself is free of data races is tests/soak/host_threads_check.cpp's matter, under ThreadSanitizer.  Every result against the
     oracle (igd.rs:504-590: counts are pure functions of the database and the batch)."""
     import threading
 

@@ -578,7 +578,9 @@ def test_host_threads_under_the_thread_sanitizer(tmp_path):
     exactly once (n around the thread count and 10,007, chunks of 1 and 8, 1 / 2 / 7 threads), a body's exception arrives on the
     caller with every thread joined whether a worker's body or the caller's own threw it, of two exceptions one arrives, a throw
     ends the hand-out of indices; cut_at_lines cuts at line starts; JoinedThreads stops and joins when an exception leaves its
-    scope."""
+    scope; Once (the guard of the handles' lazily built tables): eight threads in run() at once, the builder fails once and then
+    succeeds -- it runs exactly twice, a run() after the success returns 0 without calling it, and readers that only spin on
+    done() see what it stored."""
     import shutil
     import subprocess
 
