@@ -121,6 +121,7 @@ _SIG = {
     "gtars_lola_contingency_device": (C.c_int, [vp, vp, u64, i64, i64, vp, vp, vp, vp, vp]),
     "gtars_refget_digests_device": (C.c_int, [vp, vp, vp, vp, vp]),
     "gtars_refget_substrings_device": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp, u64, pu64, vp]),
+    "gtars_refget_packed_substrings_device": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp, u64, pu64, vp]),
     "gtars_prof_enable": (None, [C.c_int]),
     "gtars_prof_reset": (None, []),
     "gtars_prof_read": (C.c_int, [vp, vp, vp, C.c_int]),
@@ -384,6 +385,24 @@ _HOST_SIG = {
     "gtars_seqcol_digests": (C.c_int, [vp, vp]),
     "gtars_seqcol_substrings": (C.c_int, [vp, vp, vp, vp, u64, C.c_int, u32, vp, pp, pp]),
     "gtars_seqcol_digest_records": (C.c_int, [vp, C.c_int, u32, vp, vp, vp]),
+    "gtars_refget_bits": (u32, [C.c_int]),
+    "gtars_refget_encode": (C.c_int, [vp, u64, C.c_int, vp, u64, pu64]),
+    "gtars_refget_decode": (C.c_int, [vp, u64, u64, u64, u64, C.c_int, vp]),
+    "gtars_refget_byte_range": (None, [u64, u64, u32, pu64, pu64]),
+    "gtars_seqpack_from_seqcol": (C.c_int, [vp, vp, C.c_int, u32, pp]),
+    "gtars_seqpack_from_files": (C.c_int, [vp, vp, vp, u64, u32, pp]),
+    "gtars_seqpack_from_buffers": (C.c_int, [vp, vp, vp, vp, u64, pp]),
+    "gtars_seqpack_free": (None, [vp]),
+    "gtars_seqpack_len": (u64, [vp]),
+    "gtars_seqpack_device": (C.c_int, [vp]),
+    "gtars_seqpack_image_bytes": (u64, [vp]),
+    "gtars_seqpack_record": (C.c_int, [vp, u64, pp, pu64, pu64, C.POINTER(C.c_int)]),
+    "gtars_seqpack_write_files": (C.c_int, [vp, vp, u32]),
+    "gtars_seqpack_substrings": (C.c_int, [vp, vp, vp, vp, u64, C.c_int, u32, vp, pp, pp]),
+    "gtars_seqpack_decode_records": (C.c_int, [vp, C.c_int, u32, pp, pp]),
+    "gtars_seqcol_from_seq_files": (C.c_int, [vp, vp, u64, u32, pp]),
+    "gtars_seqcol_from_buffers": (C.c_int, [vp, vp, u64, pp]),
+    "gtars_seqcol_write_files": (C.c_int, [vp, vp, u32]),
 }
 
 # include/gtars_amd_debug.h: test / A-B / diagnostics hooks, not part of the drop-in boundary

@@ -15,6 +15,7 @@
 #include "host_threads.h"
 #include "refget.h"
 #include "refget_core.h"
+#include "refget_seqcol.h"
 
 namespace gtars {
 unsigned host_threads_for(unsigned cap);
@@ -22,17 +23,6 @@ bool read_file_by_magic(const std::string &path, std::string &out, std::string &
 }  // namespace gtars
 using gtars::fail;
 using gtars::guarded;
-
-// The records of one FASTA text in file order (a repeated name stays a record of its own).  With the bytes kept, `a` is an
-// assembly over them with ONE entry per record -- its name map knows the last record of a name -- whose lazy device image
-// serves the substring calls.
-struct gtars_seqcol {
-    std::vector<gtars::RefgetRecord> recs;
-    std::vector<gtars::RefgetDigest> digests;  // per record, once computed
-    bool has_digests = false, has_bytes = false, gzip = false;
-    gtars::RefgetColDigests col;
-    gtars_assembly a;
-};
 
 namespace {
 

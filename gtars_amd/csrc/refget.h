@@ -50,6 +50,13 @@ struct RefgetSubCall {
 };
 gtars_status refget_sub_run(const Assembly &a, const RefgetSubCall &call);
 
+// The same call over any image whose rows have the device column len[n_seq] on `device` (K22's packed image, refget_pack.hip):
+// statuses, counts and offsets as above; `fill` queues the launch that writes out[0, total) from the device columns seq /
+// start (the call's rows) and the scanned offsets off[0 .. n].
+using RefgetFill = std::function<gtars_status(const uint32_t *seq, const uint64_t *start, const uint64_t *off, uint32_t n, uint64_t total,
+                                              uint8_t *out, void *stream)>;
+gtars_status refget_sub_run_over(const uint64_t *d_len, uint32_t n_seq, int device, const RefgetSubCall &call, const RefgetFill &fill);
+
 // the configured GTARS_REFGET_HOST_LEN: rows longer than this are hashed on the host threads
 uint32_t refget_host_len();
 

@@ -177,6 +177,15 @@ gtars_status refget_digest_run(const Assembly &a, const RefgetDigestCall &call) 
 
 gtars_status refget_sub_run(const Assembly &a, const RefgetSubCall &call) {
     const AssemblyParts ap = assembly_parts(a);
+    return refget_sub_run_over(ap.len, ap.n_chrom, ap.device, call,
+                               [&](const u32 *seq, const u64 *start, const u64 *off, u32 n, u64 total, u8 *out, void *st) {
+                                   const RefgetRowSrc rows{ap.seq, ap.off, seq, start, nullptr};
+                                   return csr_fill("k_refget_fill", rows, off, n, total, out, (hipStream_t)st);
+                               });
+}
+
+gtars_status refget_sub_run_over(const uint64_t *d_len, uint32_t n_seq, int device, const RefgetSubCall &call, const RefgetFill &fill) {
+    const AssemblyParts ap{nullptr, nullptr, d_len, n_seq, device};  // (the frame and the row kernel need no more of an image)
     GT_TRY(check_device(ap, call.on_device));
     if (call.n > RG_MAX_N) return fail(GTARS_ERR_INVALID_ARG, "refget: too many rows (" + std::to_string(call.n) + ")");
     if (call.off) call.off->assign(1, 0), call.bytes->clear();
@@ -212,21 +221,20 @@ gtars_status refget_sub_run(const Assembly &a, const RefgetSubCall &call) {
     u64 *off, total = 0;
     GT_TRY(scan_total(fr, cnt, n, &off, &total));
     if (call.total) *call.total = total;
-    const RefgetRowSrc rows{ap.seq, ap.off, seq, start, nullptr};
     if (call.on_device) {
         if (call.d_off) GT_HIP(hipMemcpyAsync(call.d_off, off, (n + 1) * sizeof(u64), hipMemcpyDeviceToDevice, st));
         if (total > call.cap || (total && !call.d_bytes)) {
             GT_TRY(fr.drain());
             return fail(GTARS_ERR_CAPACITY, "refget: the byte column is too small: need " + std::to_string(total));
         }
-        GT_TRY(csr_fill("k_refget_fill", rows, off, (u32)n, total, call.d_bytes, st));
+        GT_TRY(fill(seq, start, off, (u32)n, total, call.d_bytes, st));
     } else if (call.off) {
         GT_TRY(fr.download(*call.off, off, n + 1));
         call.bytes->resize((size_t)total);
         if (total) {
             u8 *d_bytes;
             GT_TRY(fr.alloc(&d_bytes, (size_t)total));
-            GT_TRY(csr_fill("k_refget_fill", rows, off, (u32)n, total, d_bytes, st));
+            GT_TRY(fill(seq, start, off, (u32)n, total, d_bytes, st));
             GT_TRY(fr.download(call.bytes->data(), d_bytes, (size_t)total));
         }
     }

@@ -409,6 +409,16 @@ gtars_status gtars_refget_substrings_device(gtars_seqcol_t *c, const uint32_t *d
                                             uint8_t *d_bytes, uint64_t cap, uint64_t *total,
                                             void *stream);
 
+/* K22, the same substrings from a collection's bit-packed image (csrc/refget_pack.hip;
+ * a gtars_seqpack_t: include/gtars_amd_host.h), decoded by the alphabet class of
+ * each record: same columns, statuses and capacity rule. */
+typedef struct gtars_seqpack gtars_seqpack_t;
+gtars_status gtars_refget_packed_substrings_device(gtars_seqpack_t *p, const uint32_t *d_seq,
+                                                   const uint64_t *d_start, const uint64_t *d_end,
+                                                   uint64_t n, uint8_t *d_status, uint64_t *d_offsets,
+                                                   uint8_t *d_bytes, uint64_t cap, uint64_t *total,
+                                                   void *stream);
+
 /* ------------------------------------------------------------------------
  * Instrumentation used by bench.py: when enabled every kernel launch made by
  * this library on the calling thread is bracketed by HIP events on its own

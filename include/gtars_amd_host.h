@@ -1009,6 +1009,58 @@ gtars_status gtars_seqcol_substrings(gtars_seqcol_t *c, const uint32_t *seq, con
                                      uint32_t threads, uint8_t *status, uint64_t **offsets, uint8_t **bytes);
 gtars_status gtars_seqcol_digest_records(gtars_seqcol_t *c, int on_host, uint32_t threads, char *digests, uint8_t *md5, uint8_t *alphabet);
 
+/* ---- K22: the encoded storage mode and the `.seq` files of a refget store (gtars-refget/src/digest/encoder.rs, alphabet.rs,
+ * store/readonly.rs; csrc/refget_pack_core.h, csrc/refget_pack.cpp, csrc/refget_pack.hip) ------------------------------------
+ * Scalar calls, host code, no device.  bits: 2 / 3 / 4 / 5 / 8 bits per symbol of alphabet class 0 .. 4, 8 for 5 (Unknown).
+ * encode: n bytes -> ceil(n * bits / 8) packed bytes, MSB first, the unused low bits of the last byte zero; *n_bytes is set
+ * and more than `cap` is GTARS_ERR_CAPACITY ("need N").  2-bit: T C A G = 0 .. 3, others 0; 3-bit: A C G T N R Y = 0 .. 6,
+ * others 7; IUPAC: A 1, C 2, G 4, T and U 8, R 5, Y 10, S 6, W 9, K 7, M 3, B 12, D 13, H 14, V 15, N and others 0; protein:
+ * the position in ACDEFGHIKLMNPQRSTVWY*X-., others 0; 8-bit: the byte upper-cased.  Both letter cases encode alike.
+ * decode: symbols [start, end) of an encoding of which `packed` holds bytes [byte_offset, byte_offset + n_packed); bits
+ * outside that window read as zero; end <= start writes nothing; out: end - start characters.  The tables: TCAG, ACGTNRYX,
+ * NACMGRSKTWYDBHVV (no inverse of the encoding: D comes back as H, H as V, U as T), ACDEFGHIKLMNPQRSTVWY*X-. with X for
+ * codes 24 .. 31, and the code itself.  byte_range: the bytes [*b0, *b1) of an encoding that hold symbols [start, end).
+ *
+ * A gtars_seqpack_t is the packed image of a collection: record r at a 16-byte-aligned offset, ceil(length * bits / 8) bytes
+ * at the width of its own class, at least 16 zero bytes behind it; kept on the host and, from the first device call on, on
+ * the device current then (every later device call must run there).
+ * from_seqcol: from a collection read with its sequence data; alphabet: one class per record, NULL = the classes of the
+ * collection's digests.  on_host == 0: k_refget_pack packs the collection's raw device image (built on the current device
+ * if it is not yet) in one launch; on_host != 0: the same text on `threads` host threads, no device.
+ * from_files: record i is the whole file paths[i], read on the host threads and uploaded as it is -- nothing is decoded on
+ * the host; a file whose size is not ceil(length[i] * bits / 8) is GTARS_ERR_PARSE naming it.  from_buffers: the same from
+ * host memory.  write_files: each record's exact packed bytes into paths[i] (NULL: skipped).  record: the host copy of one
+ * record's packed bytes (valid while the handle lives), its length and class.
+ * substrings / decode_records: as gtars_seqcol_substrings, the rows decoded from the packed image (k_refget_fill_packed);
+ * decode_records is every record from 0 to its length.  *offsets and *bytes: gtars_free.  on_host != 0: the host threads.
+ *
+ * A Raw store's `.seq` files are upper-case text: gtars_seqcol_from_seq_files reads them (a file whose size is not length[i]
+ * is GTARS_ERR_PARSE) and gtars_seqcol_from_buffers takes host memory into a collection with its bytes kept and no digests,
+ * the records named by their numbers; gtars_seqcol_write_files writes every record's upper-cased bytes (NULL: skipped). */
+typedef struct gtars_seqpack gtars_seqpack_t;
+uint32_t gtars_refget_bits(int alphabet);
+gtars_status gtars_refget_encode(const void *seq, uint64_t n, int alphabet, uint8_t *out, uint64_t cap, uint64_t *n_bytes);
+gtars_status gtars_refget_decode(const uint8_t *packed, uint64_t n_packed, uint64_t byte_offset, uint64_t start, uint64_t end, int alphabet,
+                                 uint8_t *out);
+void gtars_refget_byte_range(uint64_t start, uint64_t end, uint32_t bits, uint64_t *b0, uint64_t *b1);
+gtars_status gtars_seqpack_from_seqcol(gtars_seqcol_t *c, const uint8_t *alphabet, int on_host, uint32_t threads, gtars_seqpack_t **out);
+gtars_status gtars_seqpack_from_files(const char *const *paths, const uint64_t *length, const uint8_t *alphabet, uint64_t n, uint32_t threads,
+                                      gtars_seqpack_t **out);
+gtars_status gtars_seqpack_from_buffers(const uint8_t *const *packed, const uint64_t *n_packed, const uint64_t *length, const uint8_t *alphabet,
+                                        uint64_t n, gtars_seqpack_t **out);
+void gtars_seqpack_free(gtars_seqpack_t *p);
+uint64_t gtars_seqpack_len(const gtars_seqpack_t *p);
+int gtars_seqpack_device(const gtars_seqpack_t *p);
+uint64_t gtars_seqpack_image_bytes(const gtars_seqpack_t *p);
+gtars_status gtars_seqpack_record(const gtars_seqpack_t *p, uint64_t i, const uint8_t **bytes, uint64_t *n_bytes, uint64_t *length, int *alphabet);
+gtars_status gtars_seqpack_write_files(const gtars_seqpack_t *p, const char *const *paths, uint32_t threads);
+gtars_status gtars_seqpack_substrings(gtars_seqpack_t *p, const uint32_t *seq, const uint64_t *start, const uint64_t *end, uint64_t n,
+                                      int on_host, uint32_t threads, uint8_t *status, uint64_t **offsets, uint8_t **bytes);
+gtars_status gtars_seqpack_decode_records(gtars_seqpack_t *p, int on_host, uint32_t threads, uint64_t **offsets, uint8_t **bytes);
+gtars_status gtars_seqcol_from_seq_files(const char *const *paths, const uint64_t *length, uint64_t n, uint32_t threads, gtars_seqcol_t **out);
+gtars_status gtars_seqcol_from_buffers(const uint8_t *const *seq, const uint64_t *length, uint64_t n, gtars_seqcol_t **out);
+gtars_status gtars_seqcol_write_files(const gtars_seqcol_t *c, const char *const *paths, uint32_t threads);
+
 #ifdef __cplusplus
 }
 #endif
