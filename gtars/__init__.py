@@ -17,7 +17,8 @@ reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats``
 ``location_digest``) and the batch calls on top of the device kernels (``normalize_alleles``, ``vrs_ids``, ``compute_vrs_ids``);
 its ``hgvs`` sub-module (``gtars.vrs.hgvs``, also ``gtars.hgvs``) holds the reference's HGVS parser classes, ``parse_hgvs``,
 ``HgvsError`` and ``hgvs_to_vrs_id`` over an assembly and a transcript store, and, additive, the batch bridge on the device
-(``hgvs_to_vrs_ids``); the transcript-anchored bridge is not provided.  ``gtars.reftx`` holds the reference's transcript classes (``TxStoreBuilder``,
+(``hgvs_to_vrs_ids``), and the transcript-anchored bridge (``hgvs_to_transcript_vrs_id``, ``hgvs_to_transcript_allele``, the batch
+``hgvs_to_transcript_vrs_ids``; ``gtars.vrs.transcript_vrs_ids`` for alleles given on transcripts).  ``gtars.reftx`` holds the reference's transcript classes (``TxStoreBuilder``,
 ``ReadonlyTxStore``, ``CoordinateMapper``, ``Transcript``, ``Exon``, ``ManeStatus``, ``Strand``, ``MappingError``, ``TxStoreError``) and, additive,
 the batch mapping calls and the spliced mRNA of every transcript on the device (``mature_mrna``, ``mature_mrnas``,
 ``transcript_accessions``); ``ReftxProvider`` is not provided.

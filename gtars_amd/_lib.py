@@ -370,6 +370,9 @@ _HOST_SIG = {
     "gtars_hgvs_resolve": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, u64, u32, vp]),
     "gtars_hgvs_to_vrs": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, u64, vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp]),
     "gtars_hgvs_ids_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gtars_hgvs_to_transcript_vrs": (C.c_int, [vp, vp, vp, u64, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gtars_hgvs_transcript_ids_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gtars_vrs_transcript_ids": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, C.c_int, u32, vp, vp, vp, vp, vp]),
     "gtars_md5": (C.c_int, [vp, u64, vp]),
     "gtars_refget_alphabet": (C.c_int, [vp, u64]),
     "gtars_refget_class_table": (None, [vp]),

@@ -1,6 +1,8 @@
 // hgvs.cpp -- the host layer of K20 (gtars.vrs.hgvs; gtars-vrs/src/hgvs/{parser,bridge}.rs, gtars-python/src/vrs/hgvs.rs): the
 // scalar parse, the batch parse and accession lookup on the host threads, the library's host path of the bridge and the
-// batch calls on top of hgvs.hip.  Declared in include/gtars_amd_host.h.  The rules themselves are hgvs_core.h.
+// batch calls on top of hgvs.hip; and the same for K23, the transcript-anchored bridge (hgvs_tx.hip, bridge.rs:226-534).
+// Declared in include/gtars_amd_host.h.  The rules themselves are hgvs_core.h and hgvs_tx_core.h.
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -12,6 +14,7 @@
 #include "guard.h"
 #include "hgvs.h"
 #include "hgvs_core.h"
+#include "hgvs_tx_core.h"
 #include "host_threads.h"
 #include "vrs.h"
 #include "vrs_core.h"
@@ -174,6 +177,129 @@ gtars_status run_on_device(gtars_txbind_t *b, const gtars::TxBindParts &p, const
     return gtars::hgvs_run(*image, *dev, call);
 }
 
+// ---- K23: the transcript-anchored bridge ------------------------------------------------------------------------------
+struct TxOutputs {
+    uint8_t *status, *detail, *warnings;
+    uint32_t *tx;
+    uint64_t *start, *end;
+    char *digest, *anchor;
+};
+
+constexpr size_t TX_HOST_BLOCK = 256;           // rows a host thread takes at a time
+constexpr uint64_t TX_MAX_POOL = 0xFFFFFFF0ull;  // as on the device
+
+// a thread's open transcript: its mature mRNA and "SQ." + its digest, derived once per run of equal transcript ids
+struct OpenTranscript {
+    uint32_t tx = gtars::TX_NONE;
+    std::string mrna;
+    char acc[35] = {'S', 'Q', '.'};
+    void open(const gtars::TxTables &t, const uint8_t *const *h_seq, uint32_t want) {
+        if (want == tx) return;
+        gtars::tx_sequence(t, want, t.len[want] ? h_seq[t.chrom[want]] : nullptr, mrna);
+        gtars::sha512t24u((const uint8_t *)mrna.data(), mrna.size(), acc + 3);
+        tx = want;
+    }
+    const uint8_t *bytes() const { return (const uint8_t *)mrna.data(); }
+};
+
+// normalize_ref over the open mRNA and the two digests (finalize_transcript_vrs_id); the status of vrs_core.h
+uint8_t finish_on_host(const OpenTranscript &m, uint64_t start, const uint8_t *ref, uint64_t ref_len, const uint8_t *alt, uint64_t alt_len,
+                       uint64_t *ns, uint64_t *ne, char *digest) {
+    const gtars::VrsNorm r = gtars::vrs_normalize(m.bytes(), m.mrna.size(), start, ref, ref_len, alt, alt_len);
+    if (r.status != gtars::VRS_OK) return r.status;
+    *ns = r.start, *ne = r.end;
+    if (digest) {
+        char loc[32];
+        gtars::vrs_location_digest(m.acc, 35, r.start, r.end, loc);
+        gtars::vrs_allele_digest(loc, m.bytes() + r.start, r.lroll, alt + r.alt_skip, r.alt_len, m.bytes() + (r.end - r.rroll), r.rroll, digest);
+    }
+    return gtars::VRS_OK;
+}
+
+// the library's host path of hgvs_tx_run: hgvs_tx_span_one row by row, then vrs_normalize and the digest writers over the
+// transcript's mRNA
+gtars_status run_tx_on_host(const gtars::TxBindParts &p, const gtars::HgvsCols &c, unsigned threads, const TxOutputs &o) {
+    const size_t n = (size_t)c.n;
+    const gtars::TxTables t = p.tables->view();
+    gtars::HgvsGenome g;
+    g.chroms = p.h_seq, g.len = p.assembly->len.data(), g.n_chrom = (uint32_t)p.assembly->names.size();
+    std::atomic<bool> too_long{false};
+    gtars::parallel_for((n + TX_HOST_BLOCK - 1) / TX_HOST_BLOCK, threads, 1, [&](size_t blk) {
+        OpenTranscript m;
+        std::vector<uint8_t> pool;
+        for (size_t i = blk * TX_HOST_BLOCK; i < std::min(n, (blk + 1) * TX_HOST_BLOCK); ++i) {
+            const gtars::HgvsTxSpan s = gtars::hgvs_tx_span_one(t, g, c, i);
+            uint8_t st = s.status, detail = s.detail;
+            uint64_t ns = 0, ne = 0;
+            char digest[32] = {}, anchor[32] = {};
+            if (st == gtars::HGVS_OK && s.ref_len + s.alt_len > TX_MAX_POOL) too_long.store(true), st = gtars::HGVS_OUT_OF_BOUNDS;
+            const uint32_t tx = st == gtars::HGVS_OK ? s.tx : gtars::TX_NONE;
+            if (st == gtars::HGVS_OK) {
+                m.open(t, p.h_seq, s.tx);
+                pool.resize((size_t)(s.ref_len + s.alt_len));
+                const uint8_t *alt = c.text + c.text_off[i] + c.alt_off[i];
+                for (uint64_t k = 0; k < s.ref_len + s.alt_len; ++k)
+                    pool[k] = (uint8_t)gtars::hgvs_tx_pool_byte(m.bytes(), s.start, s.ref_len, s.mode, alt, k);
+                const uint8_t vs = finish_on_host(m, s.start, pool.data(), s.ref_len, pool.data() + s.ref_len, s.alt_len, &ns, &ne, digest);
+                if (vs != gtars::VRS_OK) st = gtars::HGVS_NORMALIZE_ERROR, detail = vs;
+                else memcpy(anchor, m.acc + 3, 32);
+            }
+            if (o.status) o.status[i] = st;
+            if (o.detail) o.detail[i] = detail;
+            if (o.warnings) o.warnings[i] = (c.flags[i] & gtars::HGVS_UNCERTAIN) ? (uint8_t)gtars::HGVS_WARN_UNCERTAIN : (uint8_t)0;
+            if (o.tx) o.tx[i] = tx;
+            if (o.start) o.start[i] = ns;
+            if (o.end) o.end[i] = ne;
+            if (o.digest) memcpy(o.digest + i * 32, digest, 32);  // (zero bytes unless the row passed)
+            if (o.anchor) memcpy(o.anchor + i * 32, anchor, 32);
+        }
+    });
+    if (too_long.load()) return fail(GTARS_ERR_CAPACITY, "hgvs: the alleles of one call must fit 4 GiB; split the batch");
+    return GTARS_OK;
+}
+
+gtars_status run_tx_on_device(gtars_txbind_t *b, const gtars::TxBindParts &p, const gtars::HgvsCols &c, unsigned threads, bool on_device,
+                              void *stream, const TxOutputs &o) {
+    gtars::Assembly *image;
+    gtars::TxDevice *dev;
+    if (const gtars_status e = gtars::tx_bind_device(b, &image, &dev)) return e;
+    const gtars::TxTables t = p.tables->view();
+    gtars::HgvsTxCall call;
+    call.cols = c, call.on_device = on_device, call.stream = stream;
+    call.host.h_tables = &t, call.host.h_seq = p.h_seq, call.host.threads = threads;
+    call.status = o.status, call.detail = o.detail, call.warnings = o.warnings, call.tx = o.tx;
+    call.start = o.start, call.end = o.end, call.digest = o.digest, call.anchor = o.anchor;
+    return gtars::hgvs_tx_run(*image, *dev, call);
+}
+
+// the host path of vrs_tx_run: K18's checks in K18's order, over the transcript's mRNA
+void tx_alleles_on_host(const gtars::TxBindParts &p, const gtars::VrsTxCall &k, unsigned threads) {
+    const size_t n = (size_t)k.n;
+    const gtars::TxTables t = p.tables->view();
+    gtars::parallel_for((n + TX_HOST_BLOCK - 1) / TX_HOST_BLOCK, threads, 1, [&](size_t blk) {
+        OpenTranscript m;
+        for (size_t i = blk * TX_HOST_BLOCK; i < std::min(n, (blk + 1) * TX_HOST_BLOCK); ++i) {
+            const uint32_t tx = k.tx[i];
+            uint8_t st = gtars::VRS_OK;
+            uint64_t ns = 0, ne = 0;
+            char digest[32] = {}, anchor[32] = {};
+            if (tx >= t.n_tx || t.seq_status[tx] != gtars::TXSEQ_OK) st = gtars::VRS_NO_CHROM;
+            else if ((uint64_t)k.ref_off[i] + k.ref_len[i] > k.pool_bytes || (uint64_t)k.alt_off[i] + k.alt_len[i] > k.pool_bytes)
+                st = gtars::VRS_BAD_ALLELE;
+            else {
+                m.open(t, p.h_seq, tx);
+                st = finish_on_host(m, k.start[i], k.pool + k.ref_off[i], k.ref_len[i], k.pool + k.alt_off[i], k.alt_len[i], &ns, &ne, digest);
+                if (st == gtars::VRS_OK) memcpy(anchor, m.acc + 3, 32);
+            }
+            if (k.status) k.status[i] = st;
+            if (k.new_start) k.new_start[i] = ns;
+            if (k.new_end) k.new_end[i] = ne;
+            if (k.digest) memcpy(k.digest + i * 32, digest, 32);  // (zero bytes unless the row passed)
+            if (k.anchor) memcpy(k.anchor + i * 32, anchor, 32);
+        }
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -253,6 +379,67 @@ gtars_status gtars_hgvs_ids_device(gtars_txbind_t *b, const gtars_hgvs_columns *
         std::vector<char> tab;
         if (const gtars_status e = gtars::vrs_accession_table(p.assembly, accessions, nt, tab)) return e;
         return run_on_device(b, p, view_of(*d_cols), tab.data(), nt, true, stream, Outputs{d_status, d_detail, d_warnings, d_chrom, d_start, d_end, d_digests});
+    });
+}
+
+gtars_status gtars_hgvs_to_transcript_vrs(gtars_txbind_t *b, const uint8_t *text, const uint64_t *offsets, uint64_t n, int on_host,
+                                          uint32_t threads, uint8_t *status, uint8_t *detail, uint8_t *warnings, uint32_t *tx, uint64_t *start,
+                                          uint64_t *end, char *digests, char *anchors) {
+    return guarded([&]() -> gtars_status {
+        if (!b || (n && (!offsets || (!text && offsets[n])))) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (!n) return GTARS_OK;
+        const gtars::TxBindParts p = gtars::tx_bind_parts(b);
+        const unsigned nt = threads_of(threads);
+        const size_t k = (size_t)n;
+        std::vector<uint8_t> bytes(5 * k);
+        std::vector<uint32_t> words(5 * k);
+        std::vector<int64_t> longs(4 * k);
+        std::vector<uint64_t> text_off(k);
+        gtars_hgvs_columns c{};
+        c.pre = bytes.data(), c.kind = c.pre + k, c.loc = c.kind + k, c.edit = c.loc + k, c.flags = c.edit + k;
+        c.tx = words.data(), c.ref_off = c.tx + k, c.ref_len = c.ref_off + k, c.alt_off = c.ref_len + k, c.alt_len = c.alt_off + k;
+        c.base1 = longs.data(), c.off1 = c.base1 + k, c.base2 = c.off1 + k, c.off2 = c.base2 + k;
+        c.text_off = text_off.data();
+        if (const gtars_status e = resolve(b, text, offsets, n, Aliases(), nt, c)) return e;
+        const TxOutputs o{status, detail, warnings, tx, start, end, digests, anchors};
+        if (on_host) return run_tx_on_host(p, view_of(c), nt, o);
+        return run_tx_on_device(b, p, view_of(c), nt, false, nullptr, o);
+    });
+}
+
+gtars_status gtars_hgvs_transcript_ids_device(gtars_txbind_t *b, const gtars_hgvs_columns *d_cols, uint8_t *d_status, uint8_t *d_detail,
+                                              uint8_t *d_warnings, uint32_t *d_tx, uint64_t *d_start, uint64_t *d_end, char *d_digests,
+                                              char *d_anchors, void *stream) {
+    return guarded([&]() -> gtars_status {
+        if (!b || !d_cols) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (!d_cols->n) return GTARS_OK;
+        if (!columns_complete(*d_cols)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        return run_tx_on_device(b, gtars::tx_bind_parts(b), view_of(*d_cols), threads_of(0), true, stream,
+                                TxOutputs{d_status, d_detail, d_warnings, d_tx, d_start, d_end, d_digests, d_anchors});
+    });
+}
+
+gtars_status gtars_vrs_transcript_ids(gtars_txbind_t *b, const uint32_t *tx, const uint64_t *start, const uint8_t *pool, uint64_t pool_bytes,
+                                      const uint32_t *ref_off, const uint32_t *ref_len, const uint32_t *alt_off, const uint32_t *alt_len,
+                                      uint64_t n, int on_host, uint32_t threads, uint8_t *status, uint64_t *new_start, uint64_t *new_end,
+                                      char *digests, char *anchors) {
+    return guarded([&]() -> gtars_status {
+        if (!b) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (n && (!tx || !start || !ref_off || !ref_len || !alt_off || !alt_len || (!pool && pool_bytes)))
+            return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (!n) return GTARS_OK;
+        const gtars::TxBindParts p = gtars::tx_bind_parts(b);
+        const gtars::TxTables t = p.tables->view();
+        gtars::VrsTxCall call;
+        call.tx = tx, call.start = start, call.pool = pool, call.pool_bytes = pool_bytes;
+        call.ref_off = ref_off, call.ref_len = ref_len, call.alt_off = alt_off, call.alt_len = alt_len, call.n = n;
+        call.host.h_tables = &t, call.host.h_seq = p.h_seq, call.host.threads = threads_of(threads);
+        call.status = status, call.new_start = new_start, call.new_end = new_end, call.digest = digests, call.anchor = anchors;
+        if (on_host) return tx_alleles_on_host(p, call, call.host.threads), GTARS_OK;
+        gtars::Assembly *image;
+        gtars::TxDevice *dev;
+        if (const gtars_status e = gtars::tx_bind_device(b, &image, &dev)) return e;
+        return gtars::vrs_tx_run(*image, *dev, call);
     });
 }
 

@@ -22,6 +22,7 @@
 #include "image_call.h"
 #include "pipeline.h"
 #include "reftx.h"
+#include "reftx_image.h"
 #include "sha512.h"
 
 namespace gtars {
@@ -128,6 +129,52 @@ gtars_status check_device(const AssemblyParts &ap, bool on_device) {
 
 }  // namespace
 
+// sha512t24u of rows' mature sequences into d_digest (four u64 per row; zero for a row whose status is not TXSEQ_OK), cnt:
+// the rows' lengths as k_tx_rows leaves them.  The stream is drained when it returns.
+gtars_status tx_digest_rows(StreamFrame &fr, const AssemblyParts &ap, const TxTables &t, const u32 *idx, const u32 *cnt, const u8 *status, u32 n,
+                            u64 *d_digest, const TxTables *h_tables, const uint8_t *const *h_seq, unsigned threads) {
+    hipStream_t st = fr.st;
+    // (a negative or unreadable value is the default; 2^30 bounds the u32 the kernel compares with)
+    const long host_len_cfg = cfg_int("GTARS_TX_HOST_LEN", 65536);
+    const u32 host_len = (u32)std::min(host_len_cfg < 0 ? 65536l : host_len_cfg, 0x40000000l);
+    u32 *perm, *host_list, *n_host;
+    GT_TRY(sort_perm(fr, nullptr, cnt, nullptr, n, 1, &perm));
+    GT_TRY(fr.alloc(&host_list, n));
+    GT_TRY(fr.alloc(&n_host, 1));
+    GT_HIP(hipMemsetAsync(n_host, 0, sizeof(u32), st));
+    {
+        ProfScope ps("k_tx_digest", st);
+        hipLaunchKernelGGL(k_tx_digest, dim3(grid_for(n, TX_TPB, TX_MAX_BLOCKS)), dim3(TX_TPB), 0, st, t, ap.seq, ap.off, idx, perm, status, n,
+                           host_len, d_digest, host_list, n_host);
+        GT_HIP(hipGetLastError());
+    }
+    u32 *h_n = (u32 *)fr.host(sizeof(u32));
+    if (!h_n) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+    GT_TRY(fr.download(h_n, n_host, 1));
+    GT_TRY(fr.drain());
+    if (const u32 n_list = *h_n) {
+        // the host tail: the rows and their transcript indexes come back, the digests go up
+        if (!h_tables || !h_seq) return fail(GTARS_ERR_INTERNAL, "reftx: the host tail needs the host tables");
+        std::vector<u32> rows, txs(n_list);
+        GT_TRY(fr.download(rows, host_list, n_list));
+        GT_TRY(fr.drain());
+        for (u32 k = 0; k < n_list; ++k) GT_TRY(fr.download(&txs[k], idx + rows[k], 1));
+        GT_TRY(fr.drain());
+        std::vector<char> text((size_t)n_list * 32);
+        const TxTables &h = *h_tables;
+        parallel_for(n_list, threads, 1, [&](size_t k) { tx_digest(h, txs[k], h_seq[h.chrom[txs[k]]], &text[k * 32]); });
+        for (u32 k = 0; k < n_list; ++k) GT_TRY(fr.upload_to((char *)(d_digest + 4 * (size_t)rows[k]), &text[(size_t)k * 32], 32));
+        GT_TRY(fr.drain());
+    }
+    return GTARS_OK;
+}
+
+// the rows' mature sequences back to back: row r at d_bytes[off[r], off[r + 1]); `name` is the launch's ProfScope entry
+gtars_status tx_fill_rows(const char *name, StreamFrame &fr, const AssemblyParts &ap, const TxTables &t, const u32 *idx, const u64 *off, u32 n,
+                          u64 total, u8 *d_bytes) {
+    return csr_fill(name, TxRowSrc{t, ap.seq, ap.off, idx}, off, n, total, d_bytes, fr.st);
+}
+
 gtars_status tx_device_build(const Assembly &a, const TxHostTables &h, TxDevice **out) {
     *out = nullptr;
     const AssemblyParts ap = assembly_parts(a);
@@ -200,9 +247,6 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
     StreamFrame &fr = ic.fr;
     hipStream_t st = fr.st;
     const size_t n = (size_t)call.n;
-    // (a negative or unreadable value is the default; 2^30 bounds the u32 the kernel compares with)
-    const long host_len_cfg = cfg_int("GTARS_TX_HOST_LEN", 65536);
-    const u32 host_len = (u32)std::min(host_len_cfg < 0 ? 65536l : host_len_cfg, 0x40000000l);
     const TxTables t = d.view();
     const u32 *idx;
     GT_TRY(ic.in(call.idx, n, &idx));
@@ -219,35 +263,7 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
     if (call.digest) {
         u64 *d_digest;
         GT_TRY(ic.digests_out(call.digest, n, &d_digest));
-        u32 *perm, *host_list, *n_host;
-        GT_TRY(sort_perm(fr, nullptr, cnt, nullptr, (u32)n, 1, &perm));
-        GT_TRY(fr.alloc(&host_list, n));
-        GT_TRY(fr.alloc(&n_host, 1));
-        GT_HIP(hipMemsetAsync(n_host, 0, sizeof(u32), st));
-        {
-            ProfScope ps("k_tx_digest", st);
-            hipLaunchKernelGGL(k_tx_digest, dim3(grid), dim3(TX_TPB), 0, st, t, ap.seq, ap.off, idx, perm, status, (u32)n, host_len, d_digest,
-                               host_list, n_host);
-            GT_HIP(hipGetLastError());
-        }
-        u32 *h_n;
-        GT_TRY(ic.host_word(&h_n));
-        GT_TRY(fr.download(h_n, n_host, 1));
-        GT_TRY(fr.drain());
-        if (const u32 n_list = *h_n) {
-            // the host tail: the rows and their transcript indexes come back, the digests go up
-            if (!call.h_tables || !call.h_seq) return fail(GTARS_ERR_INTERNAL, "reftx: the host tail needs the host tables");
-            std::vector<u32> rows, txs(n_list);
-            GT_TRY(fr.download(rows, host_list, n_list));
-            GT_TRY(fr.drain());
-            for (u32 k = 0; k < n_list; ++k) GT_TRY(fr.download(&txs[k], idx + rows[k], 1));
-            GT_TRY(fr.drain());
-            std::vector<char> text((size_t)n_list * 32);
-            const TxTables &h = *call.h_tables;
-            parallel_for(n_list, call.threads, 1, [&](size_t k) { tx_digest(h, txs[k], call.h_seq[h.chrom[txs[k]]], &text[k * 32]); });
-            for (u32 k = 0; k < n_list; ++k) GT_TRY(fr.upload_to((char *)(d_digest + 4 * (size_t)rows[k]), &text[(size_t)k * 32], 32));
-            GT_TRY(fr.drain());
-        }
+        GT_TRY(tx_digest_rows(fr, ap, t, idx, cnt, status, (u32)n, d_digest, call.h_tables, call.h_seq, call.threads));
         GT_TRY(ic.digests_back(call.digest, d_digest, n));
     }
     if (call.seq_off) {
@@ -258,7 +274,7 @@ gtars_status tx_seq_run(const Assembly &a, const TxDevice &d, const TxSeqCall &c
         if (total) {
             u8 *d_bytes;
             GT_TRY(fr.alloc(&d_bytes, (size_t)total));
-            GT_TRY(csr_fill("k_tx_fill", TxRowSrc{t, ap.seq, ap.off, idx}, off, (u32)n, total, d_bytes, st));
+            GT_TRY(tx_fill_rows("k_tx_fill", fr, ap, t, idx, off, (u32)n, total, d_bytes));
             GT_TRY(fr.download(call.seq_bytes->data(), d_bytes, (size_t)total));
         }
     }

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 #include "seqstats.h"
@@ -40,6 +41,25 @@ struct VrsCall {
 // runs the batch on the image's device: the device-affinity rule of the other handle-taking entries for on_device calls
 // (the current device must be the image's), the image's device is selected for host columns
 gtars_status vrs_run(const Assembly &a, const VrsCall &call);
+
+// The sequences a batch is normalized over, without an Assembly: `n_seq` sequences packed in device memory, sequence c at
+// seq[off[c], off[c] + len[c]) (each shorter than 2^32 - 16 bytes).  A roll is bounded by 0 and len[c], never by the
+// neighbours in the image.  The accession table, 32 characters per sequence, is device memory (d_acc) or host memory
+// (h_acc, uploaded by the call); both null: no digests, every sequence counts.  host_tail serves the digest's host tail:
+// for the listed sequence ids it hands back the sequences' first bytes and their 32 accession characters on the host; the
+// pointers must stay valid until vrs_run_view returns.
+struct VrsSeqView {
+    int device = -1;
+    const uint8_t *seq = nullptr;
+    const uint64_t *off = nullptr, *len = nullptr;
+    uint32_t n_seq = 0;
+    const uint8_t *d_acc = nullptr;
+    const char *h_acc = nullptr;
+    std::function<gtars_status(const std::vector<uint32_t> &ids, std::vector<const uint8_t *> &seq, std::vector<const char *> &acc)> host_tail;
+};
+// vrs_run over such a view (call.accessions and call.h_seq are not read: the view has them); vrs_run(const Assembly &, ...)
+// is a caller of it, hgvs_tx.hip (K23) the other
+gtars_status vrs_run_view(const VrsSeqView &s, const VrsCall &call);
 
 // vrs.cpp, for the host layers on top of K18 (hgvs.cpp): the library's own host path of a batch -- host columns; the call's
 // accessions, threads, status, new_start, new_end and digest are used --, the accession table of a call (the caller's 32

@@ -17,6 +17,8 @@
 //     must not hash a megabase serially): vrs_run finishes them with the same header on the host threads.
 //   * k_vrs_lens + the scan of kernels.hip + the fill of byte_csr.h over VrsRowSrc (profiled as k_vrs_fill): the normalized
 //     sequences as a byte CSR, eight output bytes per lane.
+// The kernels see sequences only as (bytes, offsets, lengths, accessions): vrs_run_view runs them over any such view --
+// the assembly's image (vrs_run), or the mature mRNAs a call of K23 derived (hgvs_tx.hip), where "chromosome" is a slot.
 #include <cstring>
 
 #include "byte_csr.h"
@@ -361,12 +363,12 @@ struct VrsRowSrc {
 
 }  // namespace
 
-gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
-    const AssemblyParts ap = assembly_parts(a);
+gtars_status vrs_run_view(const VrsSeqView &sv, const VrsCall &call) {
+    const AssemblyParts ap{sv.seq, sv.off, sv.len, sv.n_seq, sv.device};
     if (ap.device < 0) return fail(GTARS_ERR_INTERNAL, "vrs: the assembly has no device image");
     if (call.n > VRS_MAX_N) return fail(GTARS_ERR_INVALID_ARG, "vrs: too many alleles (" + std::to_string(call.n) + ")");
     if ((call.seq_off == nullptr) != (call.seq_bytes == nullptr)) return fail(GTARS_ERR_INVALID_ARG, "vrs: sequences need both vectors");
-    if (call.digest && !call.accessions) return fail(GTARS_ERR_INVALID_ARG, "vrs: digests need the accession table");
+    if (call.digest && !sv.d_acc && !sv.h_acc) return fail(GTARS_ERR_INVALID_ARG, "vrs: digests need the accession table");
     if (call.seq_off) call.seq_off->assign(1, 0), call.seq_bytes->clear();
     if (!call.n) return GTARS_OK;
     if (!call.chrom || !call.start || !call.ref_off || !call.ref_len || !call.alt_off || !call.alt_len || (!call.pool && call.pool_bytes))
@@ -390,9 +392,11 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
     GT_TRY(ic.in(call.alt_off, n, &v.alt_off));
     GT_TRY(ic.in(call.alt_len, n, &v.alt_len));
     GT_TRY(ic.in(call.pool, (size_t)call.pool_bytes, &v.pool));
-    if (call.accessions) {
+    if (sv.d_acc) {
+        v.acc = sv.d_acc;
+    } else if (sv.h_acc) {
         u8 *d_acc;
-        GT_TRY(fr.upload(&d_acc, (const u8 *)call.accessions, (size_t)ap.n_chrom * 32));
+        GT_TRY(fr.upload(&d_acc, (const u8 *)sv.h_acc, (size_t)ap.n_chrom * 32));
         v.acc = d_acc;
     }
     // per-allele results: the caller's device columns where it gave them, the frame's otherwise
@@ -435,22 +439,28 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
         GT_TRY(fr.drain());
         if (const u32 n_host = *h_n) {
             // the host tail: the records and their ALT bytes come back, the digests go up
-            if (!call.h_seq) return fail(GTARS_ERR_INTERNAL, "vrs: the host tail needs the host sequences");
+            if (!sv.host_tail) return fail(GTARS_ERR_INTERNAL, "vrs: the host tail needs the host sequences");
             std::vector<VrsHostRec> recs;
             GT_TRY(fr.download(recs, host_list, n_host));
             GT_TRY(fr.drain());
             std::vector<std::vector<u8>> alts(n_host);
+            std::vector<u32> ids(n_host);
             for (u32 k = 0; k < n_host; ++k) {
+                ids[k] = recs[k].chrom;
                 alts[k].resize(recs[k].t_len);
                 GT_TRY(fr.download(alts[k].data(), v.pool + recs[k].t_off, recs[k].t_len));
             }
             GT_TRY(fr.drain());
+            std::vector<const uint8_t *> h_seq;
+            std::vector<const char *> h_acc;
+            GT_TRY(sv.host_tail(ids, h_seq, h_acc));
+            if (h_seq.size() != n_host || h_acc.size() != n_host) return fail(GTARS_ERR_INTERNAL, "vrs: the host tail got no sequences");
             std::vector<char> text((size_t)n_host * 32);
             parallel_for(n_host, call.threads, 1, [&](size_t k) {
                 const VrsHostRec &r = recs[k];
-                const uint8_t *seq = call.h_seq[r.chrom];
+                const uint8_t *seq = h_seq[k];
                 char acc[35] = {'S', 'Q', '.'};
-                memcpy(acc + 3, call.accessions + (size_t)r.chrom * 32, 32);
+                memcpy(acc + 3, h_acc[k], 32);
                 char loc[32];
                 vrs_location_digest(acc, 35, r.ns, r.ne, loc);
                 vrs_allele_digest(loc, seq + r.ns, r.lroll, alts[k].data(), r.t_len, seq + (r.ne - r.rroll), r.rroll, &text[k * 32]);
@@ -486,6 +496,18 @@ gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
     GT_TRY(ic.back(call.new_start, v.ns, n));
     GT_TRY(ic.back(call.new_end, v.ne, n));
     return fr.drain();
+}
+
+gtars_status vrs_run(const Assembly &a, const VrsCall &call) {
+    const AssemblyParts ap = assembly_parts(a);
+    VrsSeqView sv;
+    sv.device = ap.device, sv.seq = ap.seq, sv.off = ap.off, sv.len = ap.len, sv.n_seq = ap.n_chrom, sv.h_acc = call.accessions;
+    if (call.h_seq)
+        sv.host_tail = [&call](const std::vector<uint32_t> &ids, std::vector<const uint8_t *> &seq, std::vector<const char *> &acc) {
+            for (const uint32_t c : ids) seq.push_back(call.h_seq[c]), acc.push_back(call.accessions + (size_t)c * 32);
+            return GTARS_OK;
+        };
+    return vrs_run_view(sv, call);
 }
 
 }  // namespace gtars

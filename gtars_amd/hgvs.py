@@ -15,8 +15,13 @@ assembly, REF and ALT are written eight bytes per lane, and the columns go strai
 ``on_host=True`` runs the library's own host path instead: the same results, no device.  Without a device the default calls
 raise NoDeviceError; there is no silent fallback.
 
-Only the genome-anchored bridge with literal sequence states is computed.  The transcript-anchored bridge
-(``hgvs_to_transcript_*``: an allele on the derived mRNA) and ``ReferenceLengthExpression`` states are not part of this module.
+``hgvs_to_transcript_vrs_id`` / ``hgvs_to_transcript_vrs_ids`` / ``hgvs_to_transcript_allele`` are the second bridge of the
+reference (bridge.rs:226-534): the allele of a ``c.`` / ``n.`` expression anchored on the transcript's own refget accession,
+"SQ." + sha512t24u of the mature mRNA derived from the assembly.  Coordinates, REF, ALT and the normalization are in mRNA
+space and in transcript orientation; a roll crosses exon junctions and stops at the transcript's ends (csrc/hgvs_tx.hip,
+DESIGN.md section 3, K23).  These take the assembly and the store in place of the reference's ``genome`` / ``tx_store``.
+
+Only literal sequence states are computed; ``ReferenceLengthExpression`` states are not part of this module.
 """
 from __future__ import annotations
 
@@ -27,9 +32,9 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from ._lib import check, lib, ptr
-from .reftx import BoundTxStore, ReadonlyTxStore, TxStoreBuilder, _mapping_text
+from .reftx import BoundTxStore, ReadonlyTxStore, TxStoreBuilder, _mapping_text, mature_mrna
 from .seqstats import _genome_handle
-from .vrs import VA_PREFIX, _accession_table
+from .vrs import VA_PREFIX, _accession_table, sha512t24u
 from .vrs import STATUS_NAMES as _VRS_STATUS_NAMES
 
 
@@ -430,4 +435,140 @@ def hgvs_to_vrs_id(hgvs_str: str, genome, store=None, accessions: Optional[Dict[
     r = hgvs_to_vrs_ids(genome, b, [hgvs_str], accessions, aliases, on_host, 1)
     if r["statuses"][0] != OK:
         raise ValueError(_failure_text(b, hgvs_str, int(r["statuses"][0]), int(r["details"][0]), aliases))
+    return r["ids"][0]
+
+
+# ---- the transcript-anchored bridge (K23) -----------------------------------------------------------------------------------
+TX_NOT_EXONIC = 8  # the detail of MAPPING_ERROR for a position that is intronic or outside the mature mRNA
+
+
+def transcript_ids_device(genome, store, d_cols: Dict[str, int], text_bytes: int, n: int, d_status: int = 0, d_detail: int = 0,
+                          d_warnings: int = 0, d_tx: int = 0, d_start: int = 0, d_end: int = 0, d_digests: int = 0, d_anchors: int = 0,
+                          stream: int = 0) -> None:
+    """the transcript-anchored bridge for resolved columns that are on the device already (``d_cols`` as for ``ids_device``);
+    outputs u8 statuses, details and warnings, u32 transcript numbers, u64 starts / ends on the mRNA, n * 32 digest bytes and
+    n * 32 bytes of the anchors' digests, any may be 0.  Queued on ``stream``, which is drained before the call returns.  The
+    current device must be the assembly's."""
+    b = _bound(genome, store)
+    c = _CColumns(**{name: int(d_cols[name]) for name, _ in COLUMN_DTYPES}, text=int(d_cols["text"]), text_bytes=int(text_bytes), n=int(n))
+    check(lib.gtars_hgvs_transcript_ids_device(b._h, C.byref(c), C.c_void_p(d_status), C.c_void_p(d_detail), C.c_void_p(d_warnings),
+                                               C.c_void_p(d_tx), C.c_void_p(d_start), C.c_void_p(d_end), C.c_void_p(d_digests),
+                                               C.c_void_p(d_anchors), C.c_void_p(stream)))
+
+
+def hgvs_to_transcript_vrs_ids(genome, store, strings: Sequence, on_host: bool = False, threads: int = 0) -> dict:
+    """VRS identifiers of a batch of ``c.`` / ``n.`` expressions, anchored on the transcripts' mature mRNAs: {"ids":
+    "ga4gh:VA...." per string (None for one that failed), "statuses" (see STATUS_NAMES), "details" (the mapping status of
+    ``gtars.reftx`` for status 7 -- 8, TX_NOT_EXONIC: intronic or outside the mature mRNA --, the status of ``gtars.vrs`` for
+    status 11), "warnings" (bit 0: uncertain expression), "transcripts" (numbers in the store, 2^32 - 1 for a row that
+    failed), "accessions" ("SQ...." of the mRNA, None for a row that failed), "starts", "ends" (the normalized interval on the
+    mRNA)}.  ``store``: a ReadonlyTxStore, or a BoundTxStore that is kept between calls.  Never raises for data."""
+    b = _bound(genome, store)
+    _genome_handle(b.genome)
+    text, off, _ = _blob(strings)
+    n = len(off) - 1
+    status, detail, warnings = (np.zeros(n, dtype=np.uint8) for _ in range(3))
+    tx = np.full(n, NONE_U32, dtype=np.uint32)
+    ns, ne = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    digests, anchors = np.zeros(32 * n, dtype=np.uint8), np.zeros(32 * n, dtype=np.uint8)
+    check(lib.gtars_hgvs_to_transcript_vrs(b._h, ptr(text), ptr(off), n, 1 if on_host else 0, int(threads), ptr(status), ptr(detail),
+                                           ptr(warnings), ptr(tx), ptr(ns), ptr(ne), ptr(digests), ptr(anchors)))
+    raw, raw_a = digests.tobytes(), anchors.tobytes()
+    ok = [status[i] == 0 for i in range(n)]
+    ids: List[Optional[str]] = [VA_PREFIX + raw[32 * i:32 * i + 32].decode("ascii") if ok[i] else None for i in range(n)]
+    accs: List[Optional[str]] = ["SQ." + raw_a[32 * i:32 * i + 32].decode("ascii") if ok[i] else None for i in range(n)]
+    return {"ids": ids, "statuses": status, "details": detail, "warnings": warnings, "transcripts": tx, "accessions": accs, "starts": ns,
+            "ends": ne}
+
+
+def _tx_parts(b: BoundTxStore, s: str):
+    """build_transcript_allele_parts (bridge.rs:306-403) for one expression on the host, check for check: (accession, start,
+    end, mRNA, ALT), or ValueError with BridgeError's Display"""
+    st, row, raw = _parse_row(s)
+    if st == UNSUPPORTED_REFERENCE_TYPE or row.ref_type not in (1, 2):
+        raise ValueError(f"unsupported reference type: {_REF_LETTER[_REF_TYPES[row.ref_type]].upper()} (v1 supports g., c., n.)")
+    store, acc = b.store, _span(raw, row.acc_off, row.acc_len)
+    if looks_like_gene_symbol(acc):
+        mane = store.lookup_mane(acc)
+        if mane is None:
+            raise ValueError(f"provider error: No MANE Select transcript for gene: {acc}")
+        acc = mane.accession
+    if row.edit in (E_INV, E_UNKNOWN, E_COPY, E_REPEAT) or row.loc > L_RANGE:
+        raise ValueError("unsupported edit: " + ("ins position range" if row.edit == E_INS else _unsupported_edit(row)))
+    index = store.index_of(acc)
+    if index < 0:
+        raise ValueError(f"provider error: Transcript not found: {acc}")
+
+    def one(kind, pos, offset, star):
+        tx_i, kinds = np.array([index], dtype=np.uint32), np.array([kind], dtype=np.uint8)
+        poss, offs = np.array([pos], dtype=np.uint64).view(np.int64), np.array([offset], dtype=np.int64)
+        stars, out, code = np.array([star], dtype=np.uint8), np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint8)
+        check(lib.gtars_txstore_map(store._h, ptr(tx_i), ptr(kinds), ptr(poss), ptr(offs), ptr(stars), 1, 1, ptr(out), ptr(code)))
+        return int(out[0]), int(code[0])
+
+    def forward(p):  # position_to_genomic_interbase
+        g, code = one(row.ref_type - 1, p.base % (1 << 64), p.offset, 1 if p.datum == 2 else 0)
+        if code:
+            raise ValueError("provider error: Mapping error: " + _mapping_text(code, acc, p.base, p.offset))
+        return g
+
+    def back(g):  # map_g_to_tx
+        off, code = one(2, g, 0, 0)
+        if code == TX_NOT_EXONIC:
+            raise ValueError(f"position {g} on {acc} is intronic or outside the mature mRNA (no transcript-mRNA coordinate)")
+        if code:
+            raise ValueError("provider error: Mapping error: " + _mapping_text(code, acc, g, 0))
+        return off
+
+    if row.loc == L_SINGLE:
+        a = back(forward(row.pos[0]))
+        start, end = (a + 1, a + 1) if row.edit == E_INS else (a, a + 1)
+    else:
+        ga, gb = forward(row.pos[0]), forward(row.pos[2])
+        a, c = back(ga), back(gb)
+        if row.edit == E_INS:
+            if abs(a - c) != 1:
+                raise ValueError(f"inconsistent edit: ins range positions are not adjacent on the transcript: offsets {a} and {c}")
+            start = end = max(a, c)
+        else:
+            start, end = min(a, c), max(a, c) + 1
+    try:
+        mrna = mature_mrna(b.genome, b, acc, on_host=True)
+    except ValueError as e:
+        raise ValueError(f"refget error: {e}") from None
+    if end > len(mrna):
+        raise ValueError(f"coordinate {end} out of bounds for {acc} (len={len(mrna)})")
+    actual = mrna[start:end]
+    alt = {E_DEL: "", E_DUP: actual + actual, E_IDENTITY: actual}.get(row.edit)
+    if alt is None:
+        alt = _span(raw, row.alt_off, row.alt_len)
+    if row.flags & _HAS_REF and _span(raw, row.ref_off, row.ref_len) != actual:
+        raise ValueError(f"REF mismatch at {acc}:{start}: HGVS says {_span(raw, row.ref_off, row.ref_len)}, sequence has {actual}")
+    return acc, start, end, mrna, alt
+
+
+def hgvs_to_transcript_allele(hgvs_str: str, genome, store) -> dict:
+    """the non-normalized VRS Allele of one ``c.`` / ``n.`` expression on its transcript's mature mRNA, as a dict:
+    ``location.sequenceReference.refgetAccession`` ("SQ." + the digest of the derived mRNA), ``location.start`` / ``end``
+    (0-based interbase on the mRNA) and ``state.sequence`` (ALT as written; the span once or twice for ``=`` and ``dup``).
+    Host code: one expression, nothing to spread over a device.  HgvsError / ValueError as ``hgvs_to_transcript_vrs_id``."""
+    b = _bound(genome, store)
+    _, start, end, mrna, alt = _tx_parts(b, hgvs_str)
+    return {"type": "Allele",
+            "location": {"type": "SequenceLocation", "sequenceReference": {"type": "SequenceReference", "refgetAccession": "SQ." + sha512t24u(mrna)},
+                         "start": start, "end": end},
+            "state": {"type": "LiteralSequenceExpression", "sequence": alt}}
+
+
+def hgvs_to_transcript_vrs_id(hgvs_str: str, genome, store, on_host: bool = False) -> str:
+    """parse + bridge + normalize + digest of one expression on its transcript's mature mRNA: the "ga4gh:VA...." identifier
+    whose location references "SQ." + the digest of the derived mRNA.  HgvsError for an expression that does not parse,
+    ValueError with BridgeError's text for every other failure (a position that is intronic or outside the mature mRNA:
+    "position N on ACC is intronic or outside the mature mRNA (no transcript-mRNA coordinate)")."""
+    b = _bound(genome, store)
+    _parse_row(hgvs_str)  # (HgvsError before anything else)
+    r = hgvs_to_transcript_vrs_ids(genome, b, [hgvs_str], on_host, 1)
+    if r["statuses"][0] != OK:
+        _tx_parts(b, hgvs_str)  # (raises the failure's text: it makes the same checks in the same order)
+        raise ValueError("normalize error: " + _VRS_STATUS_NAMES[int(r["details"][0])])  # what is left: K18 refused the allele
     return r["ids"][0]

@@ -11,6 +11,8 @@ silent fallback.
 Only literal sequence states are computed.  ``ReferenceLengthExpression`` states, the refget store and sequence
 collections are not part of this module.  The HGVS parser and the HGVS-to-VRS bridge are ``gtars_amd.hgvs``, which is
 reachable from here as ``vrs.hgvs`` (``gtars.vrs.hgvs``), as in the reference; transcripts are ``gtars_amd.reftx``.
+``transcript_vrs_ids`` is the batch call for alleles that lie on transcripts: they are normalized over the mature mRNAs, which
+are derived from the assembly for the call (csrc/hgvs_tx.hip, K23).
 """
 from __future__ import annotations
 
@@ -182,6 +184,33 @@ def ids_device(genome, d_chrom: int, d_start: int, d_pool: int, pool_bytes: int,
                                    C.c_void_p(d_pool), int(pool_bytes), C.c_void_p(d_ref_off), C.c_void_p(d_ref_len),
                                    C.c_void_p(d_alt_off), C.c_void_p(d_alt_len), int(n), C.c_void_p(d_status), C.c_void_p(d_new_start),
                                    C.c_void_p(d_new_end), C.c_void_p(d_digests), C.c_void_p(stream)))
+
+
+def transcript_vrs_ids(genome, store, accessions_or_indices, starts, refs, alts, on_host: bool = False, threads: int = 0) -> dict:
+    """VRS identifiers of alleles that lie on transcripts: allele i on the mature mRNA of transcript
+    ``accessions_or_indices[i]`` (an accession of the store, or its number there) at 0-based interbase ``starts[i]``, REF and ALT
+    in transcript orientation.  The mRNAs are derived from the assembly for the call, normalization is over the mRNA alone
+    (csrc/hgvs_tx.hip, K23: the layer ``gtars.vrs.hgvs.hgvs_to_transcript_vrs_ids`` sits on).  {"ids" (None for an allele
+    that failed), "statuses" (see STATUS_NAMES; 4: no such transcript, or the assembly cannot give its sequence),
+    "accessions" ("SQ...." of the mRNA or None), "starts", "ends"}.  ``store``: a ReadonlyTxStore or a BoundTxStore."""
+    from .hgvs import _bound  # (hgvs imports this module)
+
+    b = _bound(genome, store)
+    _genome_handle(b.genome)
+    names = [a for a in accessions_or_indices if not isinstance(a, (int, np.integer))]
+    found = dict(zip(names, b.store.indices_of(names, threads).tolist())) if names else {}
+    cols = _Columns(b.genome, [a if isinstance(a, (int, np.integer)) else found[a] for a in accessions_or_indices], starts, refs, alts)
+    n = cols.n
+    status = np.zeros(n, dtype=np.uint8)
+    ns, ne = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    digests, anchors = np.zeros(32 * n, dtype=np.uint8), np.zeros(32 * n, dtype=np.uint8)
+    check(lib.gtars_vrs_transcript_ids(b._h, ptr(cols.chrom), ptr(cols.start), ptr(cols.pool), cols.pool.size, ptr(cols.ref_off),
+                                       ptr(cols.ref_len), ptr(cols.alt_off), ptr(cols.alt_len), n, 1 if on_host else 0, int(threads),
+                                       ptr(status), ptr(ns), ptr(ne), ptr(digests), ptr(anchors)))
+    raw, raw_a = digests.tobytes(), anchors.tobytes()
+    ids = [VA_PREFIX + raw[32 * i:32 * i + 32].decode("ascii") if status[i] == 0 else None for i in range(n)]
+    accs = ["SQ." + raw_a[32 * i:32 * i + 32].decode("ascii") if status[i] == 0 else None for i in range(n)]
+    return {"ids": ids, "statuses": status, "accessions": accs, "starts": ns, "ends": ne}
 
 
 class VrsResults:

@@ -966,6 +966,33 @@ gtars_status gtars_hgvs_ids_device(gtars_txbind_t *b, const gtars_hgvs_columns *
                                    uint8_t *d_detail, uint8_t *d_warnings, uint32_t *d_chrom, uint64_t *d_start, uint64_t *d_end,
                                    char *d_digests, void *stream);
 
+/* ---- K23: the transcript-anchored bridge (bridge.rs:226-534; csrc/hgvs_tx.hip, csrc/hgvs_tx_core.h) -----------------------
+ * The allele of a c. / n. expression on the transcript's own mature mRNA: its anchor is "SQ." + sha512t24u of the mRNA
+ * derived from the assembly, coordinates, REF, ALT and the normalization are in mRNA space and in transcript orientation
+ * (nothing is reverse-complemented; ALT is taken as written).  g. m. r. p. rows get status 2.  A position that is intronic
+ * or outside the mature mRNA gets status 7 with detail 8 (the TX_NOT_EXONIC of gtars_txbind_map); a transcript whose
+ * chromosome the assembly lacks 6, one with an exon past the chromosome's end 8, one with bad exons 7 with detail 10.
+ * to_transcript_vrs takes the strings (as gtars_hgvs_to_vrs; gene symbols go through the MANE index);
+ * transcript_ids_device takes resolved columns, text and outputs that are device memory, queued on `stream`, which is
+ * drained before the call returns (the current device must be the assembly's; the digest columns 8-byte aligned).
+ * vrs_transcript_ids is the layer under the bridge: allele i lies on the mRNA of transcript tx[i] (index in the store) at
+ * 0-based interbase start[i], REF and ALT in the byte pool as for gtars_vrs_alleles; its statuses are gtars_vrs_alleles'
+ * (4: no such transcript, or the assembly cannot give its sequence).
+ * Outputs of n entries, any may be NULL: status, detail, warnings, the transcript's index (2^32 - 1 for a row the bridge
+ * refused), the normalized interval on the mRNA, the 32 characters of the Allele digest and the 32 characters of the
+ * anchor's digest (both zero bytes for a row that failed).  A call never fails for data.  on_host != 0: the library's host
+ * path, no device. */
+gtars_status gtars_hgvs_to_transcript_vrs(gtars_txbind_t *b, const uint8_t *text, const uint64_t *offsets, uint64_t n, int on_host,
+                                          uint32_t threads, uint8_t *status, uint8_t *detail, uint8_t *warnings, uint32_t *tx, uint64_t *start,
+                                          uint64_t *end, char *digests, char *anchors);
+gtars_status gtars_hgvs_transcript_ids_device(gtars_txbind_t *b, const gtars_hgvs_columns *d_cols, uint8_t *d_status, uint8_t *d_detail,
+                                              uint8_t *d_warnings, uint32_t *d_tx, uint64_t *d_start, uint64_t *d_end, char *d_digests,
+                                              char *d_anchors, void *stream);
+gtars_status gtars_vrs_transcript_ids(gtars_txbind_t *b, const uint32_t *tx, const uint64_t *start, const uint8_t *pool, uint64_t pool_bytes,
+                                      const uint32_t *ref_off, const uint32_t *ref_len, const uint32_t *alt_off, const uint32_t *alt_len,
+                                      uint64_t n, int on_host, uint32_t threads, uint8_t *status, uint64_t *new_start, uint64_t *new_end,
+                                      char *digests, char *anchors);
+
 /* ---- K21: refget (gtars-refget/src/digest, store/readonly.rs; csrc/refget.cpp, csrc/refget.hip) -------------------------
  * Scalar calls, host code: md5 gives 32 lower-case hex characters and a NUL; alphabet the class of n bytes read upper-cased
  * (0 dna2bit, 1 dna3bit, 2 dnaio, 3 protein, 4 ASCII; no bytes: dna2bit); class_table the class of every byte value;

@@ -3,6 +3,7 @@ kernel, per entry and for the Python call, against the library's own host path o
 restatement, on the synthetic hg38-shaped assembly and store of tools/reftx_bench.py.
 
   python tools/hgvs_bench.py [--scale 1.0] [--transcripts 200000] [--strings 10000000] [--reps 5] [--json profiles/hgvs_bench.json]
+                             [--tx-json profiles/hgvs_tx_bench.json]
 
 The expressions: 60 % c., 15 % n., 25 % g.; 60 % SNVs with the assembly's base as REF, the rest deletions, duplications,
 insertions and delins of 1 to 3 bases (none that starts on an N: the assembly's gaps), half of the g. indels inside CAG repeats
@@ -14,6 +15,11 @@ warm-up.  The Python call is split into host parse + accession lookup (gtars_hgv
 columns, and the device entry on resident columns.  Baselines, in the same run: the library's host path (on_host) on 16
 threads over everything, and tests/hgvs_ref.py on the first --sample rows.  Checks, in the run: every status, detail,
 interval and identifier of the device equals the host path's, and the restatement's on the sample.
+
+The transcript-anchored bridge (csrc/hgvs_tx.hip, K23) runs in the same run on the exonic c. / n. rows of the same
+expressions: per kernel, the device entry on resident columns, the library's host path on 16 threads, the genome-anchored
+device entry on the same rows (the ratio never mixes runs) and the share of the entry taken by the mRNA image's fill and
+digests; every output of the device is checked against the host path.
 """
 from __future__ import annotations
 
@@ -144,6 +150,77 @@ def say(text):
     print(f"[hgvs_bench] {text}", file=sys.stderr, flush=True)
 
 
+def transcript_section(g, bound, strings, cols, text, off, threads, reps, dev):
+    """K23 (csrc/hgvs_tx.hip) on the exonic c. / n. rows of the run's own expressions: the library's host path on `threads`
+    threads, the device entry on resident columns with its per-kernel times, and -- on the same rows, in the same run -- the
+    genome-anchored device entry it is compared with.  Every status, detail, interval, identifier and anchor of the device
+    is checked against the host path."""
+    keep = np.flatnonzero(((cols["kind"] == 1) | (cols["kind"] == 2)) & (cols["off1"] == 0) & (cols["off2"] == 0) & (cols["pre"] == 0))
+    n = int(keep.size)
+    sec = {"rows": n}
+    if not n:
+        return sec
+    # the kept rows as a batch of their own: text and offsets, then the resolved columns
+    lens = (off[1:] - off[:-1])[keep].astype(np.int64)
+    sub_off = np.concatenate([np.zeros(1, np.uint64), np.cumsum(lens).astype(np.uint64)])
+    idx = np.repeat(off[:-1][keep].astype(np.int64) - sub_off[:-1].astype(np.int64), lens) + np.arange(int(sub_off[-1]), dtype=np.int64)
+    sub_text = text[idx].copy()
+    sub = {name: np.zeros(n, dtype=dt) for name, dt in H.COLUMN_DTYPES}
+    c = H._CColumns(**{name: sub[name].ctypes.data for name, _ in H.COLUMN_DTYPES})
+    _lib.check(_lib.lib.gtars_hgvs_resolve(bound._h, _lib.ptr(sub_text), _lib.ptr(sub_off), n, None, None, None, 0, threads, C.byref(c)))
+    sub["text"] = sub_text
+
+    def outputs():
+        return (np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint64),
+                np.zeros(n, np.uint64), np.zeros(32 * n, np.uint8), np.zeros(32 * n, np.uint8))
+
+    def to_tx(on_host, res):
+        _lib.check(_lib.lib.gtars_hgvs_to_transcript_vrs(bound._h, _lib.ptr(sub_text), _lib.ptr(sub_off), n, 1 if on_host else 0, threads,
+                                                         *(_lib.ptr(a) for a in res)))
+
+    host = outputs()
+    t0 = time.perf_counter()
+    to_tx(True, host)
+    sec["host_path_s"], sec["host_path_threads"] = time.perf_counter() - t0, threads
+    sec["status_counts"] = np.bincount(host[0], minlength=12).tolist()
+    got = outputs()
+    to_tx(False, got)
+    for a, b in zip(got, host):
+        assert (a == b).all()
+    sec["library_call_s"] = median_wall(lambda: to_tx(False, got), max(2, reps // 2))
+    signed = {np.dtype(np.uint8): np.uint8, np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64, np.dtype(np.int64): np.int64}
+    resident = {name: torch.from_numpy(a.view(signed[a.dtype])).to(dev) for name, a in sub.items()}
+    ptrs = {k: v.data_ptr() for k, v in resident.items()}
+    o_st, o_de, o_wa = (torch.zeros(n, dtype=torch.uint8, device=dev) for _ in range(3))
+    o_tx = torch.zeros(n, dtype=torch.int32, device=dev)
+    o_ns, o_ne = torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev)
+    o_dig, o_anc = torch.zeros(32 * n, dtype=torch.uint8, device=dev), torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def tx_entry():
+        H.transcript_ids_device(g, bound, ptrs, sub_text.size, n, o_st.data_ptr(), o_de.data_ptr(), o_wa.data_ptr(), o_tx.data_ptr(),
+                                o_ns.data_ptr(), o_ne.data_ptr(), o_dig.data_ptr(), o_anc.data_ptr(), stream)
+
+    def genome_entry():
+        H.ids_device(g, bound, ptrs, sub_text.size, n, o_st.data_ptr(), o_de.data_ptr(), o_wa.data_ptr(), o_tx.data_ptr(), o_ns.data_ptr(),
+                     o_ne.data_ptr(), o_dig.data_ptr(), stream)
+
+    tx_entry()
+    for t, h in zip((o_st, o_de, o_wa, o_tx, o_ns, o_ne, o_dig, o_anc), host):
+        assert (t.cpu().numpy().view(h.dtype) == h).all()
+    sec["device_entry_s"] = median_wall(tx_entry, reps)
+    kernels = {}
+    for prefix in ("k_hgvs_tx", "k_tx_", "k_vrs"):
+        kernels.update(kernel_medians(tx_entry, reps, prefix))
+    sec["kernel_ms_median"] = kernels
+    genome_entry()
+    sec["genome_entry_same_rows_s"] = median_wall(genome_entry, reps)
+    sec["ratio_to_genome_entry"] = sec["device_entry_s"] / sec["genome_entry_same_rows_s"]
+    sec["image_fill_and_digest_share"] = (kernels.get("k_hgvs_tx_image", 0.0) + kernels.get("k_tx_digest", 0.0)) / (1e3 * sec["device_entry_s"])
+    sec["host_over_device_entry"] = sec["host_path_s"] / sec["device_entry_s"]
+    return sec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0)
@@ -153,6 +230,7 @@ def main():
     ap.add_argument("--sample", type=int, default=2000)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--tx-json", default=None, help="the transcript-anchored section on its own (profiles/hgvs_tx_bench.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available() and gtars_amd.device_count() > 0, "hgvs_bench needs an MI355X"
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -242,6 +320,8 @@ def main():
         out["kernel_ms_median"] = {**kernel_medians(entry, args.reps, "k_hgvs"), **kernel_medians(entry, args.reps, "k_vrs")}
 
         say("device entry done")
+        out["transcript_anchored"] = transcript_section(g, bound, strings, cols, text, off, threads, args.reps, dev)
+        say("transcript-anchored section done")
         # the restatement on a sample
         k = min(args.sample, n)
         if nt <= 250_000:
@@ -261,6 +341,10 @@ def main():
     if args.json:
         with open(args.json, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
+    if args.tx_json:
+        head = {k: out[k] for k in ("device", "scale", "transcripts", "strings", "reps", "assembly_bytes")}
+        with open(args.tx_json, "w") as f:
+            f.write(json.dumps({**head, "genome_device_entry_all_rows_s": out["device_entry_s"], **out["transcript_anchored"]}, indent=1) + "\n")
 
 
 if __name__ == "__main__":
