@@ -207,6 +207,20 @@ _HOST_SIG = {
     "gtars_uniwig_format_counts": (C.c_int, [vp, u64, pp, pu64]),
     "gtars_uniwig_format_pairs": (C.c_int, [vp, vp, u64, pp, pu64]),
     "gtars_uniwig_format_bedgraph": (C.c_int, [cstr, vp, vp, vp, u64, pp, pu64]),
+    "gtars_uniwig_stream_parse": (C.c_int, [cstr, vp, u64, pp]),
+    "gtars_uniwig_rows_free": (None, [vp]),
+    "gtars_uniwig_rows_len": (u64, [vp]),
+    "gtars_uniwig_rows_n_chrom": (u32, [vp]),
+    "gtars_uniwig_rows_chrom_name": (cstr, [vp, u32]),
+    "gtars_uniwig_rows_columns": (C.c_int, [vp, pp, pp, pp, pp]),
+    "gtars_uniwig_stream": (C.c_int, [vp, vp, vp, vp, u64, vp, u32, u32, u32, C.c_int, i64, u64, pp, pp, pp, pu64, pp, pu64]),
+    "gtars_uniwig_stream_plan_device": (C.c_int, [vp, vp, vp, vp, u64, vp, u32, u32, C.c_int, i64, pp]),
+    "gtars_uniwig_plan_free": (None, [vp]),
+    "gtars_uniwig_plan_segments": (u64, [vp]),
+    "gtars_uniwig_plan_total": (u64, [vp]),
+    "gtars_uniwig_plan_table": (C.c_int, [vp, vp, vp, vp, vp]),
+    "gtars_uniwig_stream_device": (C.c_int, [vp, u64, u64, vp, vp]),
+    "gtars_uniwig_format_bedgraph_bases": (C.c_int, [cstr, u32, u32, vp, u64, pp, pu64]),
     "gtars_assembly_from_fasta": (C.c_int, [cstr, pp]),
     "gtars_assembly_from_fab": (C.c_int, [cstr, pp]),
     "gtars_fab_write_from_fasta": (C.c_int, [cstr, cstr]),

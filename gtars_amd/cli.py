@@ -12,6 +12,11 @@
                              [--outputtype wig|bedGraph|npy] [--counttype all|start|end|core] [--wigstep fixed|variable]
       gtars-cli/src/uniwig/cli.rs:38-178, handlers.rs:48-160 for BED input: the coverage tracks of gtars_amd.uniwig.  BAM
       input (--filetype bam) and bigWig output (--outputtype bw) are not provided and exit with a message.
+  python -m gtars_amd uniwig --streaming [--file F.bed[.gz]|-] [--chromref G.chrom.sizes] --smoothsize M --stepsize S
+                             [--counttype start|end|core|all] [--outputtype wig|bedgraph|bg] [--dense N] [--stdout]
+                             [--fileheader PREFIX]
+      gtars-cli/src/uniwig/handlers.rs:162-274: the streaming uniwig of gtars_amd.uniwig (scores, sparse output, gap
+      filling, any step).  Input from a file or stdin, output to PREFIX_{start,end,core}.wig|bedgraph or stdout.
   python -m gtars_amd uniwig bamqc --input X.bam --output Y.tsv [--threads N]
       gtars-cli/src/uniwig/cli.rs, gtars-uniwig/src/bamqc.rs: the library-complexity QC of a coordinate-sorted BAM as a TSV.
 
@@ -175,6 +180,50 @@ def run_uniwig(a) -> int:
     return 0
 
 
+STREAM_COUNT_TYPES = {"all": ("start", "end", "core"), "start": ("start",), "end": ("end",), "core": ("core",)}
+
+
+def run_uniwig_streaming(a, stdin=None, stdout=None) -> int:
+    """run_uniwig_streaming (handlers.rs:162-274).  -> exit status.  ``stdin`` / ``stdout``: binary file objects (the
+    process's own by default)."""
+    from .uniwig import read_chrom_sizes, uniwig_streaming
+
+    chrom_sizes = read_chrom_sizes(a.chromref) if a.chromref else {}
+    labels = STREAM_COUNT_TYPES.get(a.counttype)
+    if labels is None:
+        sys.stderr.write(f"Error: unknown count type '{a.counttype}' for streaming mode\n")
+        return 1
+    if a.smoothsize is None or a.stepsize is None:
+        sys.stderr.write("uniwig: --smoothsize and --stepsize are required\n")
+        return 2
+    if a.outputtype == "wig":
+        extension = "wig"
+    elif a.outputtype in ("bedgraph", "bg"):
+        extension = "bedgraph"
+    else:
+        sys.stderr.write(f"Error: output type '{a.outputtype}' not supported in streaming mode (use wig or bedgraph)\n")
+        return 1
+    if not a.stdout and a.fileheader is None:
+        sys.stderr.write("uniwig: --fileheader required for file output in streaming mode\n")
+        return 2
+    if a.file is None or a.file == "-":
+        # read once, whatever the number of count types (the reference buffers stdin only when there are several)
+        source = (stdin if stdin is not None else sys.stdin.buffer).read()
+    else:
+        source = a.file
+    sink = stdout if stdout is not None else getattr(sys.stdout, "buffer", sys.stdout)
+    for label in labels:
+        if a.stdout:
+            if len(labels) > 1:
+                sink.write(f"# count_type={label}\n".encode())
+            uniwig_streaming(source, sink, chrom_sizes, a.smoothsize, a.stepsize, label, extension, a.dense)
+            sink.flush()
+        else:
+            uniwig_streaming(source, f"{a.fileheader}_{label}.{extension}", chrom_sizes, a.smoothsize, a.stepsize, label, extension,
+                             a.dense)
+    return 0
+
+
 def bamqc_parser() -> argparse.ArgumentParser:
     q = argparse.ArgumentParser(prog="python -m gtars_amd uniwig bamqc", description="Library-complexity QC of a coordinate-sorted BAM file")
     q.add_argument("--input", "-i", required=True, help="Path to the BAM file")
@@ -208,18 +257,28 @@ def main(argv: Sequence[str] = None) -> int:
     s.add_argument("--database", "-d", required=True)
     s.add_argument("--query", "-q", required=True)
     w = sub.add_parser("uniwig", help="Create accumulation files from a BED file")
-    w.add_argument("--file", "-f", required=True, help="Path to the combined bed file we want to transform")
+    w.add_argument("--file", "-f", help="Path to the combined bed file we want to transform ('-' or absent with --streaming: stdin)")
     w.add_argument("--filetype", "-t", default="bed", help="Input file type, 'bed' or 'narrowpeak'")
-    w.add_argument("--chromref", "-c", required=True, help="Path to chromreference")
-    w.add_argument("--smoothsize", "-m", type=int, required=True, help="Integer value for smoothing")
-    w.add_argument("--stepsize", "-s", type=int, required=True, help="Integer value for stepsize")
-    w.add_argument("--fileheader", "-l", required=True, help="Name of the file")
+    w.add_argument("--chromref", "-c", help="Path to chromreference (optional with --streaming)")
+    w.add_argument("--smoothsize", "-m", type=int, help="Integer value for smoothing")
+    w.add_argument("--stepsize", "-s", type=int, help="Integer value for stepsize")
+    w.add_argument("--fileheader", "-l", help="Name of the file")
     w.add_argument("--outputtype", "-y", default="wig", help="Output as wig, bedGraph or npy")
     w.add_argument("--counttype", "-u", default="all", help="Select to only output start, end, or core. Defaults to all.")
     w.add_argument("--score", "-o", action="store_true", help="Count via score (not provided)")
     w.add_argument("--wigstep", "-w", default="fixed", help="'fixed' (every position) or 'variable' (non-zero only)")
+    w.add_argument("--streaming", action="store_true", help="Use the streaming processor (scores, sparse output, BED only)")
+    w.add_argument("--dense", type=int, default=0,
+                   help="Streaming: widest gap to fill with zeros. 0 = sparse, -1 = fully dense, N = fill gaps <= N (default 0)")
+    w.add_argument("--stdout", action="store_true", help="Streaming: write to stdout instead of files")
     a = ap.parse_args(argv)
     if a.cmd == "uniwig":
+        if a.streaming:
+            return run_uniwig_streaming(a)
+        # the batch path needs them all, as before the streaming mode made them optional
+        missing = [f"--{k}" for k in ("file", "chromref", "smoothsize", "stepsize", "fileheader") if getattr(a, k) is None]
+        if missing:
+            w.error("the following arguments are required: " + ", ".join(missing))
         return run_uniwig(a)
     if a.cmd == "overlaprs":
         run_overlaprs(a.universe, a.query, a.backend)

@@ -38,6 +38,8 @@
 #include "setops.h"
 #include "annot.h"
 #include "uniwig.h"
+#include "uniwig_stream.h"
+#include "uniwig_stream_parse.h"
 #include "tokbatch.h"
 #include "guard.h"
 #include "host_threads.h"
@@ -4576,6 +4578,104 @@ gtars_status gtars_uniwig_format_bedgraph(const char *chrom, const uint32_t *run
             put_u32(text, run_end[i]);
             text.push_back('\t');
             put_u32(text, run_count[i]);
+            text.push_back('\n');
+        }
+        return give_text(text, out_text, out_len);
+    });
+}
+
+// ---- the streaming uniwig (K24, gtars-uniwig/src/stream.rs): the device work is uniwig_stream.hip's ---------------------
+struct gtars_uniwig_rows {
+    gtars::swparse::Rows rows;
+};
+
+gtars_status gtars_uniwig_stream_parse(const char *path, const void *data, uint64_t n, gtars_uniwig_rows **out) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out || (!path && n && !data)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *out = nullptr;
+        std::string raw, err;
+        if (path) {
+            size_t n_raw = 0;
+            if (!read_file_padded(path, raw, n_raw)) return fail(GTARS_ERR_IO, std::string("Failed to open file: \"") + path + "\": " + strerror(errno));
+            raw.resize(n_raw);
+            data = raw.data(), n = n_raw;
+        }
+        std::unique_ptr<gtars_uniwig_rows> h(new gtars_uniwig_rows());
+        if (!gtars::swparse::parse_buffer((const unsigned char *)data, (size_t)n, h->rows, err)) return fail(GTARS_ERR_PARSE, err);
+        *out = h.release();
+        return GTARS_OK;
+    });
+}
+
+void gtars_uniwig_rows_free(gtars_uniwig_rows *h) { delete h; }
+uint64_t gtars_uniwig_rows_len(const gtars_uniwig_rows *h) { return h ? h->rows.cid.size() : 0; }
+uint32_t gtars_uniwig_rows_n_chrom(const gtars_uniwig_rows *h) { return h ? (uint32_t)h->rows.names.size() : 0; }
+const char *gtars_uniwig_rows_chrom_name(const gtars_uniwig_rows *h, uint32_t i) {
+    return h && i < h->rows.names.size() ? h->rows.names[i].c_str() : nullptr;
+}
+gtars_status gtars_uniwig_rows_columns(const gtars_uniwig_rows *h, const uint32_t **cid, const int32_t **start, const int32_t **end,
+                                       const uint32_t **score) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!h || !cid || !start || !end || !score) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        *cid = h->rows.cid.data(), *start = h->rows.start.data(), *end = h->rows.end.data(), *score = h->rows.score.data();
+        return GTARS_OK;
+    });
+}
+
+gtars_status gtars_uniwig_stream(const uint32_t *cid, const uint32_t *start, const uint32_t *end, const uint32_t *score, uint64_t n,
+                                 const uint32_t *sizes_by_cid, uint32_t n_chrom, uint32_t smoothsize, uint32_t step, int kind,
+                                 int64_t max_gap, uint64_t max_device_bytes, uint32_t **seg_cid, uint32_t **seg_first,
+                                 uint32_t **seg_len, uint64_t *n_seg, uint32_t **counts, uint64_t *n_counts) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!seg_cid || !seg_first || !seg_len || !n_seg || !counts || !n_counts) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        return gtars::uniwig_stream(cid, start, end, score, n, sizes_by_cid, n_chrom, smoothsize, step, kind, max_gap, max_device_bytes,
+                                    seg_cid, seg_first, seg_len, n_seg, counts, n_counts);
+    });
+}
+
+gtars_status gtars_uniwig_stream_plan_device(const uint32_t *d_cid, const uint32_t *d_start, const uint32_t *d_end,
+                                             const uint32_t *d_score, uint64_t n, const uint32_t *sizes_by_cid, uint32_t n_chrom,
+                                             uint32_t smoothsize, int kind, int64_t max_gap, gtars_uniwig_plan **plan) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!plan) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        return gtars::uniwig_stream_plan(d_cid, d_start, d_end, d_score, n, 1, sizes_by_cid, n_chrom, smoothsize, kind, max_gap,
+                                         (gtars::SwPlan **)plan);
+    });
+}
+
+void gtars_uniwig_plan_free(gtars_uniwig_plan *plan) { gtars::uniwig_stream_plan_free((gtars::SwPlan *)plan); }
+uint64_t gtars_uniwig_plan_segments(const gtars_uniwig_plan *plan) { return gtars::uniwig_stream_plan_segments((const gtars::SwPlan *)plan); }
+uint64_t gtars_uniwig_plan_total(const gtars_uniwig_plan *plan) { return gtars::uniwig_stream_plan_total((const gtars::SwPlan *)plan); }
+gtars_status gtars_uniwig_plan_table(const gtars_uniwig_plan *plan, uint32_t *seg_cid, uint32_t *seg_first, uint32_t *seg_len,
+                                     uint64_t *seg_off) {
+    return gtars::guarded(
+        [&]() -> gtars_status { return gtars::uniwig_stream_plan_table((const gtars::SwPlan *)plan, seg_cid, seg_first, seg_len, seg_off); });
+}
+
+gtars_status gtars_uniwig_stream_device(const gtars_uniwig_plan *plan, uint64_t window_first, uint64_t window_len, uint32_t *d_counts,
+                                        void *stream) {
+    return gtars::guarded([&]() -> gtars_status {
+        return gtars::uniwig_stream_device((const gtars::SwPlan *)plan, window_first, window_len, d_counts, stream);
+    });
+}
+
+gtars_status gtars_uniwig_format_bedgraph_bases(const char *chrom, uint32_t first, uint32_t step, const uint32_t *counts, uint64_t n,
+                                                char **out_text, uint64_t *out_len) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!out_text || !out_len || !chrom || (n && !counts)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        if (!first || !step || (n && (uint64_t)first + (n - 1) * step > 0x7FFFFFFFull))
+            return fail(GTARS_ERR_INVALID_ARG, "uniwig stream: positions out of the i32 range");
+        std::string text;
+        text.reserve((size_t)n * (strlen(chrom) + 28));
+        uint32_t pos = first;
+        for (uint64_t i = 0; i < n; ++i, pos += step) {
+            text += chrom;
+            text.push_back('\t');
+            put_u32(text, pos - 1);
+            text.push_back('\t');
+            put_u32(text, pos);
+            text.push_back('\t');
+            put_u32(text, counts[i]);
             text.push_back('\n');
         }
         return give_text(text, out_text, out_len);

@@ -306,21 +306,6 @@ gtars_status cov_prepare(const u32 *opens, const u32 *closes, u64 n, u32 chrom_s
     return fr.drain();
 }
 
-template <class T>
-struct MallocArray {  // malloc'ed, handed to the caller with release()
-    T *p = nullptr;
-    ~MallocArray() { free(p); }
-    bool alloc(u64 n) {
-        p = (T *)malloc(std::max<u64>(n, 1) * sizeof(T));
-        return p != nullptr;
-    }
-    T *release() {
-        T *r = p;
-        p = nullptr;
-        return r;
-    }
-};
-
 // the flag / scan / scatter chain over the first `len` entries of the track in d_counts; the outputs reach the host
 template <int MODE>
 gtars_status cov_compact(const u32 *d_counts, u64 len, u32 S, u32 **o0, u32 **o1, u32 **o2, u64 *n_out) {

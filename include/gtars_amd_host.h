@@ -313,6 +313,61 @@ gtars_status gtars_uniwig_format_bedgraph(const char *chrom, const uint32_t *run
                                           const uint32_t *run_count, uint64_t n, char **out_text, uint64_t *out_len);
 
 /* ------------------------------------------------------------------------
+ * Streaming uniwig  (K24; gtars-uniwig/src/stream.rs: scored, sparse, gap-filled, any step)
+ *
+ * Rows are (chromosome id, start, end, score) in FILE ORDER; no order is required.  Per row a window [ws, we], 1-based
+ * and inclusive: START c = start + 1, ws = max(1, c - m), we = c + m; END c = end, the same; CORE ws = start + 1,
+ * we = end - 1, and a CORE row with we < ws is dropped before anything else.  A run is a maximal run of consecutive equal
+ * chromosome ids.  Inside a run, with M the inclusive prefix maximum of ws and B the exclusive prefix maximum of we, row
+ * i adds its score to [M_i, we_i]; it opens a segment when it is the run's first row, or when M_i > B_i + 1 and the gap
+ * M_i - B_i - 1 is not filled (filled: max_gap < 0, or gap <= max_gap).  A segment spans its head's M to the largest we
+ * of its rows; with max_gap < 0 a run's one segment starts at 1 and reaches at least sizes_by_cid[id] (0: no size).
+ * The counts are the positions of the segments one after the other ("compacted" coordinates), each the sum of the
+ * scores of the rows that cover it, modulo 2^32.  start, end, end + m + 1 and start + m + 1 must fit an i32 and a score
+ * must be below 2^31: otherwise GTARS_ERR_INVALID_ARG names the first such row.
+ * ---------------------------------------------------------------------- */
+typedef struct gtars_uniwig_rows gtars_uniwig_rows;
+typedef struct gtars_uniwig_plan gtars_uniwig_plan;
+/* parse_bed_line and the line loop of stream.rs over a file (path) or, with path NULL, over data[0, n): plain text, or
+ * gzip when it starts with 1f 8b (only the first member is decoded).  Lines are trimmed and split on any white space;
+ * empty lines, lines whose first byte is '#' and lines that start with "track" or "browser" are skipped; the score is
+ * column 5 as an i32, 1 when it is absent or no i32, 0 when negative.  A bad line is GTARS_ERR_PARSE with the
+ * reference's message, and no row is returned. */
+gtars_status gtars_uniwig_stream_parse(const char *path, const void *data, uint64_t n, gtars_uniwig_rows **out);
+void gtars_uniwig_rows_free(gtars_uniwig_rows *rows);
+uint64_t gtars_uniwig_rows_len(const gtars_uniwig_rows *rows);
+uint32_t gtars_uniwig_rows_n_chrom(const gtars_uniwig_rows *rows);
+const char *gtars_uniwig_rows_chrom_name(const gtars_uniwig_rows *rows, uint32_t i); /* first-seen order */
+/* the columns, owned by the handle: chromosome id, start and end as parsed (i32, may be negative), score */
+gtars_status gtars_uniwig_rows_columns(const gtars_uniwig_rows *rows, const uint32_t **cid, const int32_t **start,
+                                       const int32_t **end, const uint32_t **score);
+/* host columns in; out: the segments that hold positions (chromosome id, first position, length at step 1; gtars_free
+ * each) and the counts of the positions with (pos - 1) % step == 0, segment after segment (gtars_free).  The device holds
+ * at most max_device_bytes of counts at a time (0: the library's default, 1 GiB). */
+gtars_status gtars_uniwig_stream(const uint32_t *cid, const uint32_t *start, const uint32_t *end, const uint32_t *score, uint64_t n,
+                                 const uint32_t *sizes_by_cid, uint32_t n_chrom, uint32_t smoothsize, uint32_t step, int kind,
+                                 int64_t max_gap, uint64_t max_device_bytes, uint32_t **seg_cid, uint32_t **seg_first,
+                                 uint32_t **seg_len, uint64_t *n_seg, uint32_t **counts, uint64_t *n_counts);
+/* the plan of device-resident columns (sizes_by_cid is host memory): the segment table and, on the device, the event
+ * columns that gtars_uniwig_stream_device reads.  The table has n_seg entries (seg_off: n_seg + 1, the last one the
+ * compacted length) and keeps segments of length 0; a NULL column is skipped. */
+gtars_status gtars_uniwig_stream_plan_device(const uint32_t *d_cid, const uint32_t *d_start, const uint32_t *d_end,
+                                             const uint32_t *d_score, uint64_t n, const uint32_t *sizes_by_cid, uint32_t n_chrom,
+                                             uint32_t smoothsize, int kind, int64_t max_gap, gtars_uniwig_plan **plan);
+void gtars_uniwig_plan_free(gtars_uniwig_plan *plan);
+uint64_t gtars_uniwig_plan_segments(const gtars_uniwig_plan *plan);
+uint64_t gtars_uniwig_plan_total(const gtars_uniwig_plan *plan);
+gtars_status gtars_uniwig_plan_table(const gtars_uniwig_plan *plan, uint32_t *seg_cid, uint32_t *seg_first, uint32_t *seg_len,
+                                     uint64_t *seg_off);
+/* compacted positions window_first .. window_first + window_len - 1 (step 1) into d_counts (device memory, 16-byte
+ * aligned), queued on `stream` (a hipStream_t); nothing is synchronised */
+gtars_status gtars_uniwig_stream_device(const gtars_uniwig_plan *plan, uint64_t window_first, uint64_t window_len,
+                                        uint32_t *d_counts, void *stream);
+/* write_records_as_bedgraph (stream.rs:450-466): "chrom\tpos-1\tpos\tcount\n" for pos = first, first + step, ... */
+gtars_status gtars_uniwig_format_bedgraph_bases(const char *chrom, uint32_t first, uint32_t step, const uint32_t *counts,
+                                                uint64_t n, char **out_text, uint64_t *out_len);
+
+/* ------------------------------------------------------------------------
  * Genome assemblies, GC content and dinucleotide frequencies  (gtars-genomicdist/src/models.rs:145-492,
  * statistics.rs:331-483; gtars-python/src/models/genome_assembly.rs, genomic_distributions/tools.rs:8-70)
  *
