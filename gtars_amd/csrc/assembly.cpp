@@ -22,6 +22,7 @@
 
 using gtars::fail;
 using gtars::guarded;
+using gtars::MallocArray;
 
 // the handle's device image, built at the first call on the device current then
 gtars_status gtars::assembly_device_image(gtars_assembly *a, gtars::Assembly **out) {
@@ -131,21 +132,6 @@ bool valid_utf8(const unsigned char *p, size_t n) {
     }
     return true;
 }
-
-template <class T>
-struct MallocArray {  // malloc'ed, handed to the caller with release()
-    T *p = nullptr;
-    ~MallocArray() { free(p); }
-    bool alloc(uint64_t n) {
-        p = (T *)malloc((n ? n : 1) * sizeof(T));
-        return p != nullptr;
-    }
-    T *release() {
-        T *r = p;
-        p = nullptr;
-        return r;
-    }
-};
 
 // the rows of rs the reference's loops reach, in their order (iter_chroms: chromosomes by first appearance, set order
 // within one), with the assembly's chromosome ids; src = the row of rs

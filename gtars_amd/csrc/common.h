@@ -180,8 +180,9 @@ const char *cfg_get(const char *name);
 inline bool cfg_flag(const char *name) { return cfg_get(name) != nullptr; }
 long cfg_int(const char *name, long dflt);
 // GTARS_GRID_CAP (test switch; unset or 0: none): the most workgroups a grid-stride launch gets, so that a small input walks
-// the kernel's loop more than once.  Parsed once per snapshot.  note_grid_clip: a launch helper reports that this cap, and
-// not its own, cut a grid short (gtars_debug_grid_clips counts the reports).
+// the kernel's loop more than once; the coverage tile launcher (cov_tile.h) obeys it too, so that a workgroup's span is
+// several tiles.  Parsed once per snapshot.  note_grid_clip: a launch helper reports that this cap, and not its own, cut a
+// grid short (gtars_debug_grid_clips counts the reports).
 u32 grid_cap_switch();
 void note_grid_clip();
 

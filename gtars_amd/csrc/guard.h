@@ -1,7 +1,9 @@
-// guard.h -- the error status and the exception guard of the C entry points, for the HIP translation units (through
-// common.h) and the plain C++ host layers alike: no HIP headers here.
+// guard.h -- the error status, the exception guard and the malloc'ed result array of the C entry points, for the HIP
+// translation units (through common.h) and the plain C++ host layers alike: no HIP headers here.
 #pragma once
 
+#include <cstdint>
+#include <cstdlib>
 #include <exception>
 #include <new>
 #include <string>
@@ -24,5 +26,21 @@ inline gtars_status guarded(F &&f) {
         return fail(GTARS_ERR_INTERNAL, std::string("internal error: ") + e.what());
     }
 }
+
+// an array that a C entry point hands to its caller (gtars_free): malloc'ed, freed here unless release()d
+template <class T>
+struct MallocArray {
+    T *p = nullptr;
+    ~MallocArray() { free(p); }
+    bool alloc(uint64_t n) {
+        p = (T *)malloc((n ? n : 1) * sizeof(T));
+        return p != nullptr;
+    }
+    T *release() {
+        T *r = p;
+        p = nullptr;
+        return r;
+    }
+};
 
 }  // namespace gtars

@@ -9,29 +9,11 @@
 // closes the track is  count(pos) = #{a <= pos} - #{e <= pos}  for pos = a_0 .. max(chrom_size, a_{n-1} - 1).
 #pragma once
 
-#include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 
 #include "../../include/gtars_amd_host.h"
 
 namespace gtars {
-
-// an array that a C entry point hands to its caller (gtars_free): malloc'ed, freed here unless release()d
-template <class T>
-struct MallocArray {
-    T *p = nullptr;
-    ~MallocArray() { free(p); }
-    bool alloc(uint64_t n) {
-        p = (T *)malloc(std::max<uint64_t>(n, 1) * sizeof(T));
-        return p != nullptr;
-    }
-    T *release() {
-        T *r = p;
-        p = nullptr;
-        return r;
-    }
-};
 
 // first reported position and number of reported positions of a track (0, 0 for n == 0); checks the arguments
 gtars_status uniwig_extent(const uint32_t *opens, const uint32_t *closes, uint64_t n, uint32_t chrom_size, uint32_t smoothsize,

@@ -8,14 +8,11 @@
 //     start / end track:  a_i = max(1, p_i - m),  e_i = p_i + m + 1     p = sorted positions, m = smoothsize
 //     core track:         a_i = max(1, s_i),      e_i = t_i             s = sorted start + 1, t = sorted ends
 //
-//   * k_cov_tile, one pass, the output written once: a workgroup owns a SPAN of consecutive positions, finds the first
-//     open and the first close at or behind its first position by binary search (their difference is the count that
-//     enters the span), then walks the span in tiles of COV_TILE positions: the tile's events are streamed from the two
-//     sorted columns in chunks of one per thread and added into an LDS difference tile (runs of equal positions inside
-//     a wave collapse into one LDS atomic, so a pile-up costs one atomic per wave, not one per event), the tile is
-//     scanned in LDS and leaves as 16-byte stores.  The transform p -> (max(1, p - m), p + m + 1) is applied on load, so
-//     the start and the end track read the position column as it is.  Global traffic: 4 bytes per position out, 8 bytes
-//     per event in; there is no difference array in global memory.
+//   * k_cov_tile, one pass, the output written once: the coverage tile skeleton of cov_tile.h (spans, the LDS
+//     difference tile, the scan, the 16-byte stores) over the event source CovSrc -- unit weights, so the count that
+//     enters a span is the difference of the two search results, and the transform p -> (max(1, p - m), p + m + 1)
+//     applied on load, so the start and the end track read the position column as it is.  Global traffic: 4 bytes per
+//     position out, 8 bytes per event in.
 //   * k_cov_flag_count / k_cov_compact: the run-length form (bedGraph) and the non-zero form (variableStep wig) of a
 //     track that sits in device memory: flags per position, block counts, the exclusive scan of kernels.hip, scatter.
 //     Only the runs / pairs cross to the host.
@@ -25,6 +22,7 @@
 #include <memory>
 
 #include "common.h"
+#include "cov_tile.h"
 #include "pipeline.h"
 #include "scan.h"
 #include "uniwig.h"
@@ -33,133 +31,50 @@ namespace gtars {
 
 namespace {
 
-constexpr int COV_TPB = 256;
-constexpr u32 COV_PER = 16;                   // consecutive positions per thread in the scan
-constexpr u32 COV_TILE = COV_TPB * COV_PER;   // 4096 positions: 16 KiB of counts
-// a thread's 16 words are followed by 4 words of padding: the 16 lanes of a ds_read_b128 group then read 16 different
-// 16-byte slots of the 256-byte bank row (stride 80 bytes: slot 5 * lane mod 16)
-constexpr u32 COV_LDS_WORDS = COV_TILE + COV_TILE / COV_PER * 4;
-constexpr u32 COV_WG_PER_CU = 8;              // 20 KiB of LDS per workgroup
-constexpr u64 COV_MAX_N = 0xFFFFF000u;
-constexpr u64 COV_DEFAULT_WINDOW = 1ull << 28;  // positions the host call keeps on the device at a time (1 GiB)
+// K11's event source: two u32 columns, the transform p -> (max(1, p - sub_open), p + add_close) applied on load in i64, so
+// the start and the end track read the position column as it is; every event weighs 1
+struct CovSrc {
+    const u32 *__restrict__ A, *__restrict__ E;
+    u32 n, sub_open, add_close;
+    static constexpr bool WEIGHTED = false;
 
-__device__ __forceinline__ u32 cov_phys(u32 i) { return i + ((i >> 4) << 2); }
-
-__device__ __forceinline__ i64 cov_open(const u32 *__restrict__ a, u64 i, u32 sub) {
-    const i64 v = (i64)a[i] - (i64)sub;
-    return v < 1 ? 1 : v;
-}
-__device__ __forceinline__ i64 cov_close(const u32 *__restrict__ e, u64 i, u32 add) { return (i64)e[i] + (i64)add; }
-
-// number of events in front of position pos: the first index whose (transformed) value is >= pos
-template <bool OPEN>
-__device__ __forceinline__ u32 cov_lower_bound(const u32 *__restrict__ x, u32 n, u32 m, i64 pos) {
-    u32 lo = 0, hi = n;
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        const i64 v = OPEN ? cov_open(x, mid, m) : cov_close(x, mid, m);
-        if (v >= pos) hi = mid;
-        else lo = mid + 1;
+    __device__ __forceinline__ i64 open_at(u64 i) const {
+        const i64 v = (i64)A[i] - (i64)sub_open;
+        return v < 1 ? 1 : v;
     }
-    return lo;
-}
+    __device__ __forceinline__ i64 close_at(u64 i) const { return (i64)E[i] + (i64)add_close; }
 
-// adds `sign` per event into the difference tile; key = the event's offset in the tile, 0xFFFFFFFF for a lane without
-// one.  The keys of a wave ascend, so equal keys are neighbours: the last lane of a run adds the run's length.  Every
-// lane of the wave calls this.
-__device__ __forceinline__ void cov_add_runs(u32 *__restrict__ d, u32 key, u32 sign, int lane) {
-    const u32 prev = __shfl_up(key, 1, 64), next = __shfl_down(key, 1, 64);
-    const bool head = lane == 0 || prev != key;
-    const bool tail = lane == 63 || next != key;
-    const int head_lane = wave_inclusive_max_nonneg(head ? lane : 0);
-    if (tail && key != 0xFFFFFFFFu) atomicAdd(&d[cov_phys(key)], sign * (u32)(lane - head_lane + 1));
-}
+    // number of events in front of position pos: the first index whose (transformed) value is >= pos
+    template <bool OPEN>
+    __device__ __forceinline__ u32 lower_bound(i64 pos) const {
+        u32 lo = 0, hi = n;
+        while (lo < hi) {
+            const u32 mid = lo + ((hi - lo) >> 1);
+            if ((OPEN ? open_at(mid) : close_at(mid)) >= pos) hi = mid;
+            else lo = mid + 1;
+        }
+        return lo;
+    }
+    __device__ __forceinline__ u32 first_open(u64 pos) const { return lower_bound<true>((i64)pos); }
+    __device__ __forceinline__ u32 first_close(u64 pos) const { return lower_bound<false>((i64)pos); }
+    __device__ __forceinline__ u32 entering(u32 ia, u32 ie) const { return ia - ie; }
+
+    // (v >= t0 holds for ascending columns: a caller's unsorted one must not leave the tile)
+    __device__ __forceinline__ void open(u64 i, u64 t0, u64 t1, u32 &key, u32 &) const {
+        const i64 v = open_at(i);
+        if (v >= (i64)t0 && v < (i64)t1) key = (u32)(v - (i64)t0);
+    }
+    __device__ __forceinline__ void close(u64 i, u64 t0, u64 t1, u32 &key, u32 &) const {
+        const i64 v = close_at(i);
+        if (v >= (i64)t0 && v < (i64)t1) key = (u32)(v - (i64)t0);
+    }
+};
 
 // positions w0 + [0, len) of the track into out[0, len); out is 16-byte aligned, span a multiple of COV_TILE
 __global__ void __launch_bounds__(COV_TPB)
 k_cov_tile(const u32 *__restrict__ A, const u32 *__restrict__ E, u32 n, u32 sub_open, u32 add_close, u64 w0, u64 len, u64 span,
            u32 *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) u32 d[COV_LDS_WORDS];
-    __shared__ u32 red[COV_TPB / 64];
-    __shared__ u32 cur[2];
-    const u32 tid = threadIdx.x;
-    const int lane = tid & 63;
-    const u64 c0 = (u64)blockIdx.x * span;
-    if (c0 >= len) return;
-    const u64 c1 = min(len, c0 + span);
-    if (tid == 0) cur[0] = cov_lower_bound<true>(A, n, sub_open, (i64)(w0 + c0));
-    if (tid == 64) cur[1] = cov_lower_bound<false>(E, n, add_close, (i64)(w0 + c0));
-    for (u32 i = tid; i < COV_LDS_WORDS; i += COV_TPB) d[i] = 0;
-    __syncthreads();
-    u32 ia = cur[0], ie = cur[1];
-    u32 carry = ia - ie;  // the count in front of the span (mod 2^32, as every sum below: the counts themselves fit)
-    for (u64 c = c0; c < c1; c += COV_TILE) {
-        const i64 t0 = (i64)(w0 + c);
-        const i64 t1 = t0 + (i64)min((u64)COV_TILE, c1 - c);
-        // the tile's events, a chunk of COV_TPB opens and COV_TPB closes per round; the columns ascend, so the events
-        // inside the tile are a prefix of every chunk and a chunk that is not all inside ends the stream
-        bool more_a = true, more_e = true;
-        while (more_a || more_e) {
-            u32 key_a = 0xFFFFFFFFu, key_e = 0xFFFFFFFFu;
-            if (more_a) {
-                const u64 i = (u64)ia + tid;
-                if (i < n) {
-                    const i64 v = cov_open(A, i, sub_open);
-                    if (v >= t0 && v < t1) key_a = (u32)(v - t0);  // (v >= t0 holds for ascending columns: a caller's unsorted one must not leave the tile)
-                }
-            }
-            if (more_e) {
-                const u64 i = (u64)ie + tid;
-                if (i < n) {
-                    const i64 v = cov_close(E, i, add_close);
-                    if (v >= t0 && v < t1) key_e = (u32)(v - t0);
-                }
-            }
-            cov_add_runs(d, key_a, 1u, lane);
-            cov_add_runs(d, key_e, 0xFFFFFFFFu, lane);
-            const u32 na = (u32)__syncthreads_count(key_a != 0xFFFFFFFFu);
-            const u32 ne = (u32)__syncthreads_count(key_e != 0xFFFFFFFFu);
-            ia += na;
-            ie += ne;
-            more_a = na == COV_TPB;
-            more_e = ne == COV_TPB;
-        }
-        // scan: 16 consecutive differences per thread, the workgroup's exclusive scan of the thread sums, the running
-        // counts back into LDS
-        u32 v[COV_PER];
-        uint4 *mine = (uint4 *)&d[tid * (COV_PER + 4)];
-#pragma unroll
-        for (u32 k = 0; k < COV_PER / 4; ++k) {
-            const uint4 x = mine[k];
-            v[4 * k] = x.x, v[4 * k + 1] = x.y, v[4 * k + 2] = x.z, v[4 * k + 3] = x.w;
-        }
-#pragma unroll
-        for (u32 k = 1; k < COV_PER; ++k) v[k] += v[k - 1];
-        u32 total;
-        const u32 base = carry + block_exclusive_scan<COV_TPB>(v[COV_PER - 1], red, total);
-        carry += total;
-#pragma unroll
-        for (u32 k = 0; k < COV_PER / 4; ++k)
-            mine[k] = make_uint4(v[4 * k] + base, v[4 * k + 1] + base, v[4 * k + 2] + base, v[4 * k + 3] + base);
-        __syncthreads();
-        // out: consecutive lanes store consecutive 16-byte vectors; the tile is left zeroed for the next round
-#pragma unroll
-        for (u32 j = 0; j < COV_PER / 4; ++j) {
-            const u32 q = j * COV_TPB + tid;
-            uint4 *src = (uint4 *)&d[4 * (q + (q >> 2))];
-            const uint4 x = *src;
-            *src = make_uint4(0, 0, 0, 0);
-            const u64 g = c + 4ull * q;
-            if (g + 4 <= c1) {
-                *(uint4 *)(out + g) = x;
-            } else {
-                if (g < c1) out[g] = x.x;
-                if (g + 1 < c1) out[g + 1] = x.y;
-                if (g + 2 < c1) out[g + 2] = x.z;
-            }
-        }
-        __syncthreads();
-    }
+    cov_tile_body(CovSrc{A, E, n, sub_open, add_close}, w0, len, span, out);
 }
 
 // ---- run-length and non-zero forms of a track in device memory -------------------------------------------------------
@@ -258,27 +173,9 @@ void cov_transform(int kind, u32 smoothsize, u32 *sub_open, u32 *add_close) {
     *add_close = kind == GTARS_UNIWIG_CORE ? 0u : smoothsize + 1u;
 }
 
-u32 cov_max_workgroups() {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-        cus = 256;
-    return (u32)cus * COV_WG_PER_CU;
-}
-
 gtars_status launch_cov(const u32 *open, const u32 *close, u32 n, u32 sub_open, u32 add_close, u64 w_first, u64 w_len, u32 *d_out,
                         hipStream_t st) {
-    if (!w_len) return GTARS_OK;
-    if ((uintptr_t)d_out & 15) return fail(GTARS_ERR_INVALID_ARG, "uniwig: the device counts must be 16-byte aligned");
-    const u64 tiles = (w_len + COV_TILE - 1) / COV_TILE;
-    const u64 want = std::min<u64>(tiles, cov_max_workgroups());
-    const u64 span = (tiles + want - 1) / want * COV_TILE;
-    const u64 grid = (w_len + span - 1) / span;
-    ProfScope ps("k_cov_tile", st);
-    hipLaunchKernelGGL(k_cov_tile, dim3((unsigned)grid), dim3(COV_TPB), 0, st, open, close, n, sub_open, add_close, w_first, w_len, span,
-                       d_out);
-    GT_HIP(hipGetLastError());
-    return GTARS_OK;
+    return cov_tile_launch("k_cov_tile", "uniwig", k_cov_tile, st, w_first, w_len, d_out, open, close, n, sub_open, add_close);
 }
 
 // one column, ascending, on the device
@@ -405,8 +302,7 @@ gtars_status uniwig_counts(const uint32_t *opens, const uint32_t *closes, uint64
     if (!h.alloc(t.len)) return fail(GTARS_ERR_INTERNAL, "out of host memory");
     if (t.len) {
         // window after window: the count at a window's left edge comes from the same two searches as any span's
-        u64 window = max_device_bytes ? std::max<u64>(max_device_bytes / sizeof(u32) / COV_TILE, 1) * COV_TILE : COV_DEFAULT_WINDOW;
-        window = std::min(window, t.len);
+        const u64 window = cov_window(max_device_bytes, t.len);
         StreamFrame fr(nullptr);
         u32 *d;
         GT_TRY(fr.alloc(&d, (size_t)window));

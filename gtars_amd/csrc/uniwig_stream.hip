@@ -18,10 +18,9 @@
 //      (run, we + 1), as a run's segments ascend -- and the scores go along.  A row that adds nothing (score 0, or
 //      we_i < M_i) keeps its place in both columns with weight 0 and closes where it opens.  Exclusive prefix sums of the
 //      weights in both orders (scan_total; read modulo 2^32).
-//   4. k_sw_tile, the weighted form of K11's k_cov_tile over the compacted index space: a workgroup owns a span, finds
-//      the first open and the first close at or behind it by binary search, enters with prefix_open[ia] - prefix_close[ie],
-//      streams the events into the LDS difference tile (a run of equal keys inside a wave adds the SUM of its weights with
-//      one LDS atomic: a segmented sum over the wave from one DPP scan and one shuffle), scans and stores as K11 does.
+//   4. k_sw_tile: the coverage tile skeleton of cov_tile.h, which K11's k_cov_tile shares, over the compacted index space
+//      with the event source SwSrc -- u64 keys, a weight per event, so a span is entered with
+//      prefix_open[ia] - prefix_close[ie] and a run of equal keys inside a wave adds the SUM of its weights.
 //      A close one past its segment's end lands on the next segment's first slot, where the count has to drop anyway.
 //   5. step > 1: the window is computed at step 1 and k_sw_decimate keeps the positions with (pos - 1) % step == 0.
 #include <algorithm>
@@ -30,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "cov_tile.h"
 #include "pipeline.h"
 #include "scan.h"
 #include "uniwig.h"
@@ -48,21 +48,13 @@ struct SwPlan {
 
 namespace {
 
-constexpr int SW_TPB = 256;
-constexpr u32 SW_PER = 16;                  // consecutive positions per thread in the scan
-constexpr u32 SW_TILE = SW_TPB * SW_PER;    // 4096 positions: 16 KiB of counts
-constexpr u32 SW_LDS_WORDS = SW_TILE + SW_TILE / SW_PER * 4;  // the padded 80-byte stride of K11
-constexpr u32 SW_WG_PER_CU = 8;
-constexpr u64 SW_MAX_N = 0xFFFFF000u;
-constexpr u64 SW_DEFAULT_WINDOW = 1ull << 28;
-constexpr u32 SW_NONE = 0xFFFFFFFFu;
+constexpr u32 SW_NO_ROW = 0xFFFFFFFFu;  // k_sw_window found no row out of range
 constexpr int PL_TPB = 256;
 constexpr int PL_IPT = 8;
 constexpr u32 PL_TILE = PL_TPB * PL_IPT;
 
 using SMax = SegMax<u32>;
 
-__device__ __forceinline__ u32 sw_phys(u32 i) { return i + ((i >> 4) << 2); }
 __device__ __forceinline__ u32 sw_is_head(const u32 *__restrict__ cid, u64 i) { return i == 0 || cid[i] != cid[i - 1]; }
 
 // ---- 1. windows ---------------------------------------------------------------------------------------------------------
@@ -211,115 +203,44 @@ __global__ void k_sw_closes(const u32 *__restrict__ perm, const u32 *__restrict_
 }
 
 // ---- 4. the tile kernel ---------------------------------------------------------------------------------------------------
-// the first index whose value is >= pos
-__device__ __forceinline__ u32 sw_lower_bound(const u64 *__restrict__ x, u32 n, u64 pos) {
-    u32 lo = 0, hi = n;
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        if (x[mid] >= pos) hi = mid;
-        else lo = mid + 1;
+// K24's event source over the compacted index space: u64 keys, a u32 weight per event, the exclusive weight sums of both
+// columns (read modulo 2^32)
+struct SwSrc {
+    const u64 *__restrict__ A, *__restrict__ E;
+    const u32 *__restrict__ SA, *__restrict__ SE;
+    const u64 *__restrict__ PA, *__restrict__ PE;
+    u32 n;
+    static constexpr bool WEIGHTED = true;
+
+    // the first index whose value is >= pos
+    __device__ __forceinline__ u32 lower_bound(const u64 *__restrict__ x, u64 pos) const {
+        u32 lo = 0, hi = n;
+        while (lo < hi) {
+            const u32 mid = lo + ((hi - lo) >> 1);
+            if (x[mid] >= pos) hi = mid;
+            else lo = mid + 1;
+        }
+        return lo;
     }
-    return lo;
-}
+    __device__ __forceinline__ u32 first_open(u64 pos) const { return lower_bound(A, pos); }
+    __device__ __forceinline__ u32 first_close(u64 pos) const { return lower_bound(E, pos); }
+    __device__ __forceinline__ u32 entering(u32 ia, u32 ie) const { return (u32)PA[ia] - (u32)PE[ie]; }
 
-// adds the weights of the wave's events into the difference tile (negated for closes); key = the event's offset in the
-// tile, SW_NONE for a lane without one.  The keys of a wave ascend, so equal keys are neighbours: the last lane of a run adds
-// the run's sum, the wave's inclusive sum at that lane minus the exclusive one at the run's first lane.  Every lane of the
-// wave calls this.
-__device__ __forceinline__ void sw_add_runs(u32 *__restrict__ d, u32 key, u32 w, bool negate, int lane) {
-    const u32 prev = __shfl_up(key, 1, 64), next = __shfl_down(key, 1, 64);
-    const bool head = lane == 0 || prev != key;
-    const bool tail = lane == 63 || next != key;
-    const int head_lane = wave_inclusive_max_nonneg(head ? lane : 0);
-    const u32 inc = wave_inclusive_scan_u32(w, lane);
-    const u32 before = __shfl(inc - w, head_lane, 64);
-    const u32 sum = inc - before;
-    if (tail && key != SW_NONE && sum) atomicAdd(&d[sw_phys(key)], negate ? 0u - sum : sum);
-}
+    __device__ __forceinline__ void open(u64 i, u64 t0, u64 t1, u32 &key, u32 &w) const {
+        const u64 v = A[i];
+        if (v >= t0 && v < t1) key = (u32)(v - t0), w = SA[i];
+    }
+    __device__ __forceinline__ void close(u64 i, u64 t0, u64 t1, u32 &key, u32 &w) const {
+        const u64 v = E[i];
+        if (v >= t0 && v < t1) key = (u32)(v - t0), w = SE[i];
+    }
+};
 
-// compacted positions w0 + [0, len) into out[0, len); out is 16-byte aligned, span a multiple of SW_TILE
-__global__ void __launch_bounds__(SW_TPB)
+// compacted positions w0 + [0, len) into out[0, len); out is 16-byte aligned, span a multiple of COV_TILE
+__global__ void __launch_bounds__(COV_TPB)
 k_sw_tile(const u64 *__restrict__ A, const u64 *__restrict__ E, const u32 *__restrict__ SA, const u32 *__restrict__ SE,
           const u64 *__restrict__ PA, const u64 *__restrict__ PE, u32 n, u64 w0, u64 len, u64 span, u32 *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) u32 d[SW_LDS_WORDS];
-    __shared__ u32 red[SW_TPB / 64];
-    __shared__ u32 cur[2];
-    const u32 tid = threadIdx.x;
-    const int lane = tid & 63;
-    const u64 c0 = (u64)blockIdx.x * span;
-    if (c0 >= len) return;
-    const u64 c1 = min(len, c0 + span);
-    if (tid == 0) cur[0] = sw_lower_bound(A, n, w0 + c0);
-    if (tid == 64) cur[1] = sw_lower_bound(E, n, w0 + c0);
-    for (u32 i = tid; i < SW_LDS_WORDS; i += SW_TPB) d[i] = 0;
-    __syncthreads();
-    u32 ia = cur[0], ie = cur[1];
-    u32 carry = (u32)PA[ia] - (u32)PE[ie];  // the count in front of the span, modulo 2^32 as every sum below
-    for (u64 c = c0; c < c1; c += SW_TILE) {
-        const u64 t0 = w0 + c;
-        const u64 t1 = t0 + min((u64)SW_TILE, c1 - c);
-        // a chunk of SW_TPB opens and SW_TPB closes per round; the columns ascend, so the events inside the tile are a
-        // prefix of every chunk and a chunk that is not all inside ends the stream
-        bool more_a = true, more_e = true;
-        while (more_a || more_e) {
-            u32 key_a = SW_NONE, key_e = SW_NONE, w_a = 0, w_e = 0;
-            if (more_a) {
-                const u64 i = (u64)ia + tid;
-                if (i < n) {
-                    const u64 v = A[i];
-                    if (v >= t0 && v < t1) key_a = (u32)(v - t0), w_a = SA[i];
-                }
-            }
-            if (more_e) {
-                const u64 i = (u64)ie + tid;
-                if (i < n) {
-                    const u64 v = E[i];
-                    if (v >= t0 && v < t1) key_e = (u32)(v - t0), w_e = SE[i];
-                }
-            }
-            sw_add_runs(d, key_a, w_a, false, lane);
-            sw_add_runs(d, key_e, w_e, true, lane);
-            const u32 na = (u32)__syncthreads_count(key_a != SW_NONE);
-            const u32 ne = (u32)__syncthreads_count(key_e != SW_NONE);
-            ia += na;
-            ie += ne;
-            more_a = na == SW_TPB;
-            more_e = ne == SW_TPB;
-        }
-        u32 v[SW_PER];
-        uint4 *mine = (uint4 *)&d[tid * (SW_PER + 4)];
-#pragma unroll
-        for (u32 k = 0; k < SW_PER / 4; ++k) {
-            const uint4 x = mine[k];
-            v[4 * k] = x.x, v[4 * k + 1] = x.y, v[4 * k + 2] = x.z, v[4 * k + 3] = x.w;
-        }
-#pragma unroll
-        for (u32 k = 1; k < SW_PER; ++k) v[k] += v[k - 1];
-        u32 total;
-        const u32 base = carry + block_exclusive_scan<SW_TPB>(v[SW_PER - 1], red, total);
-        carry += total;
-#pragma unroll
-        for (u32 k = 0; k < SW_PER / 4; ++k)
-            mine[k] = make_uint4(v[4 * k] + base, v[4 * k + 1] + base, v[4 * k + 2] + base, v[4 * k + 3] + base);
-        __syncthreads();
-        // out: consecutive lanes store consecutive 16-byte vectors; the tile is left zeroed for the next round
-#pragma unroll
-        for (u32 j = 0; j < SW_PER / 4; ++j) {
-            const u32 q = j * SW_TPB + tid;
-            uint4 *src = (uint4 *)&d[4 * (q + (q >> 2))];
-            const uint4 x = *src;
-            *src = make_uint4(0, 0, 0, 0);
-            const u64 g = c + 4ull * q;
-            if (g + 4 <= c1) {
-                *(uint4 *)(out + g) = x;
-            } else {
-                if (g < c1) out[g] = x.x;
-                if (g + 1 < c1) out[g + 1] = x.y;
-                if (g + 2 < c1) out[g + 2] = x.z;
-            }
-        }
-        __syncthreads();
-    }
+    cov_tile_body(SwSrc{A, E, SA, SE, PA, PE, n}, w0, len, span, out);
 }
 
 // ---- 5. step > 1 ----------------------------------------------------------------------------------------------------------
@@ -347,26 +268,9 @@ __global__ void k_sw_decimate(const u32 *__restrict__ in, u64 w0, u64 len, const
 // one thread per element, no loop in the kernels: n is at most 2^32, the grid at most 2^24 workgroups
 unsigned sw_blocks(u64 n) { return (unsigned)std::max<u64>(1, (n + 255) / 256); }
 
-u32 sw_max_workgroups() {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-        cus = 256;
-    return (u32)cus * SW_WG_PER_CU;
-}
-
 gtars_status launch_sw(const SwPlan &p, u64 w_first, u64 w_len, u32 *d_out, hipStream_t st) {
-    if (!w_len) return GTARS_OK;
-    if ((uintptr_t)d_out & 15) return fail(GTARS_ERR_INVALID_ARG, "uniwig stream: the device counts must be 16-byte aligned");
-    const u64 tiles = (w_len + SW_TILE - 1) / SW_TILE;
-    const u64 want = std::min<u64>(tiles, sw_max_workgroups());
-    const u64 span = (tiles + want - 1) / want * SW_TILE;
-    const u64 grid = (w_len + span - 1) / span;
-    ProfScope ps("k_sw_tile", st);
-    hipLaunchKernelGGL(k_sw_tile, dim3((unsigned)grid), dim3(SW_TPB), 0, st, p.A.p, p.E.p, p.SA.p, p.SE.p, p.PA.p, p.PE.p, (u32)p.n, w_first,
-                       w_len, span, d_out);
-    GT_HIP(hipGetLastError());
-    return GTARS_OK;
+    return cov_tile_launch("k_sw_tile", "uniwig stream", k_sw_tile, st, w_first, w_len, d_out, p.A.p, p.E.p, p.SA.p, p.SE.p, p.PA.p, p.PE.p,
+                           (u32)p.n);
 }
 
 // positions of [first, first + len) with (pos - 1) % step == 0
@@ -408,13 +312,13 @@ gtars_status build_plan(SwPlan &p, const u32 *cid, const u32 *start, const u32 *
                            bad);
         GT_HIP(hipGetLastError());
     }
-    u32 h_bad = SW_NONE;
+    u32 h_bad = SW_NO_ROW;
     GT_TRY(fr.download(&h_bad, bad, 1));
     u64 n = n0;
     if (kind == GTARS_UNIWIG_CORE) {
         u64 *koff;
         GT_TRY(scan_total(fr, keep, n0, &koff, &n));
-        if (h_bad == SW_NONE && n != n0 && n) {
+        if (h_bad == SW_NO_ROW && n != n0 && n) {
             u32 *c2, *ws2, *we2, *sc2;
             GT_TRY(fr.alloc(&c2, (size_t)n));
             GT_TRY(fr.alloc(&ws2, (size_t)n));
@@ -428,7 +332,7 @@ gtars_status build_plan(SwPlan &p, const u32 *cid, const u32 *start, const u32 *
     } else {
         GT_TRY(fr.drain());
     }
-    if (h_bad != SW_NONE)
+    if (h_bad != SW_NO_ROW)
         return fail(GTARS_ERR_INVALID_ARG, "uniwig stream: row " + std::to_string(h_bad) +
                                                " is out of range (start, end and end + smoothsize + 1 must fit an i32, the score "
                                                "an i32, the chromosome id the size table)");
@@ -515,7 +419,7 @@ gtars_status uniwig_stream_plan(const uint32_t *cid, const uint32_t *start, cons
     *plan = nullptr;
     if (kind != GTARS_UNIWIG_START && kind != GTARS_UNIWIG_END && kind != GTARS_UNIWIG_CORE)
         return fail(GTARS_ERR_INVALID_ARG, "uniwig stream: unknown track kind " + std::to_string(kind));
-    if (n > SW_MAX_N) return fail(GTARS_ERR_INVALID_ARG, "uniwig stream: too many rows (" + std::to_string(n) + ")");
+    if (n > COV_MAX_N) return fail(GTARS_ERR_INVALID_ARG, "uniwig stream: too many rows (" + std::to_string(n) + ")");
     if (smoothsize > 0x3FFFFFFFu) return fail(GTARS_ERR_INVALID_ARG, "uniwig stream: smooth size out of the i32 range");
     if (n && (!cid || !start || !end || !score)) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
     if (n_chrom && !sizes_by_cid) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
@@ -576,8 +480,7 @@ gtars_status uniwig_stream(const uint32_t *cid, const uint32_t *start, const uin
     MallocArray<u32> h;
     if (!h.alloc(n_kept)) return fail(GTARS_ERR_INTERNAL, "out of host memory");
     if (total) {
-        u64 window = max_device_bytes ? std::max<u64>(max_device_bytes / sizeof(u32) / SW_TILE, 1) * SW_TILE : SW_DEFAULT_WINDOW;
-        window = std::min(window, total);
+        const u64 window = cov_window(max_device_bytes, total);
         StreamFrame fr(nullptr);
         u32 *d, *dk = nullptr;
         u64 *d_koff = nullptr;

@@ -154,6 +154,7 @@ def _capped(c, monkeypatch):
     import gtars_amd
     import gtars_amd.engine  # noqa: F401
     import gtars_amd.refget  # noqa: F401
+    import gtars_amd.uniwig  # noqa: F401
 
     real = gtars_amd._lib.lib
     assert gtars_amd.device_count() > 0, "no MI355X visible: -m gpu tests must run on the GPU box"
@@ -458,6 +459,64 @@ def test_bulk_union_except_of_many_sets(cap):
             got_full, got_ex = rsl.bulk_union_except()
         assert SL._plain(got_full) == want[0] and [SL._tuples(g) for g in got_ex] == want[1]
         assert len({tuple(u) for u in want[1]}) >= 3  # the unions without a set that has regions differ from the others
+
+
+# ---- csrc/cov_tile.h: the coverage tile launcher ---------------------------------------------------------------------------------
+# Its grid is one workgroup per tile up to 8 per CU, so a workgroup walks a second tile of its span only past 8 million
+# positions.  Under the cap a track of 7 tiles + 11 positions is one span of 8 tiles (C = 1) or spans of 3, 3 and 2 tiles, the
+# last one ragged (C = 3): the carry across tiles, the re-zeroed LDS tile and the event cursors that run on from tile to tile.
+# (Neither file takes its geometry from grid_for / stream_grid: no COVERED entries.)
+def test_coverage_tracks_of_several_tiles_per_workgroup(cap):
+    """K11, all three kinds: the events of test_events_on_tile_boundaries; then 3,000 equal positions in tile 4, the second
+    tile of its span under both caps, which the core track enters with a non-zero count and which takes twelve rounds of
+    256 events"""
+    import test_gpu_uniwig as UW
+
+    tile, first = UW.TILE, 5
+    chrom_size = first + 7 * tile + 11
+    edges = []
+    for k in (0, 1, 2, 5):
+        edges += [first + k * tile, first + (k + 1) * tile - 1, first + (k + 1) * tile]
+    start = np.array([e - 1 for e in edges], dtype=np.uint32)
+    for m in (0, 3):
+        p = sorted({e + m for e in edges} | {e - m - 1 for e in edges if e - m - 1 > first + m} | {first + m})
+        p = np.array(p + p[:4], dtype=np.uint32)
+        with cap.run(True, "uniwig_counts"):
+            UW._check_tracks_vs_restatement(p - np.uint32(1), p + np.uint32(tile), chrom_size, m)
+            for width in (1, tile - 1, tile, tile + 1):
+                UW._check_tracks_vs_restatement(start, start + np.uint32(width), chrom_size, m)
+        # the pile-up opens on the second position of the core track's tile 4 and closes 49 positions on (start and end track:
+        # windows of 2 m + 1 inside their tile 4); one long row covers tiles 3 .. 5, so the core track enters tile 4 with 1
+        t4 = first + 4 * tile
+        s = np.concatenate([start, [t4 - tile + 7], np.full(3000, t4, dtype=np.uint32)]).astype(np.uint32)
+        e = np.concatenate([start + np.uint32(9), [t4 + tile + 9], np.full(3000, t4 + 50, dtype=np.uint32)]).astype(np.uint32)
+        assert int((s + 1 < t4).sum()) - int((e < t4).sum()) > 0  # the core track's count in front of tile 4
+        with cap.run(True, "uniwig_counts"):
+            UW._check_tracks_vs_restatement(s, e, chrom_size, m)
+
+
+def test_streamed_tracks_of_several_tiles_per_workgroup(cap):
+    """K24, kinds core and start: one segment of 7 tiles + 11 compacted positions with a pile of rows inside it and 300 rows
+    of mixed scores that open on one position of tile 4; then, with one workgroup, device windows of two tiles, each
+    entered with the count that the prefix columns give"""
+    import random as _random
+
+    import test_gpu_uniwig_stream as SW
+
+    tile = SW.TILE
+    rng = _random.Random(24)
+    rows = [("chr1", 0, 7 * tile + 12, 2)] + SW._pile(rng, 400, 1, 7 * tile - 50, 45)
+    rows += [("chr1", 4 * tile + 50, 4 * tile + 60 + rng.randrange(0, 30), rng.choice([1, 2, 3, 0, 1000, 65536])) for _ in range(300)]
+    rows = sorted(rows, key=lambda r: r[1]) + [("chr2", 7, 20, 1)]
+    # core: the long row's window is [1, 7 * tile + 11]; start (windows of 7 positions): dense up to chr1's size
+    for kind, m, max_gap, sizes in (("core", 0, 0, None), ("start", 3, -1, {"chr1": 7 * tile + 11})):
+        with cap.run(True, "uniwig_stream"):
+            track, want = SW.check(rows, m, 1, kind, max_gap, sizes)
+            if cap.c == 1:
+                SW.check(rows, m, 1, kind, max_gap, sizes, max_device_bytes=2 * tile * 4)
+        assert track.seg_len.tolist()[0] == 7 * tile + 11 and track.seg_first.tolist()[0] == 1
+        at = 4 * tile + 50 - m  # the compacted index (position - 1) on which the 300 rows open
+        assert 4 * tile <= at < 5 * tile and want[at][2] - want[at - 1][2] > 1000
 
 
 # ---- csrc/annot.hip ------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import uniwig_ref as R
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-TILE = 4096  # COV_TILE of uniwig.hip: positions per LDS tile
+TILE = 4096  # COV_TILE of cov_tile.h: positions per LDS tile
 
 
 def _pairs(v):

@@ -12,7 +12,7 @@ import uniwig_stream_ref as R
 
 pytestmark = pytest.mark.gpu
 
-TILE = 4096  # SW_TILE of uniwig_stream.hip: compacted positions per LDS tile, and per workgroup span at these sizes
+TILE = 4096  # COV_TILE of cov_tile.h: compacted positions per LDS tile, and per workgroup span at these sizes
 I31 = (1 << 31) - 1
 
 
