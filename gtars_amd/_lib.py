@@ -289,6 +289,8 @@ _HOST_SIG = {
     "gtars_host_threads": (u32, [u32]),
     "gtars_read_file": (C.c_int, [cstr, pp, pu64]),
     "gtars_fragsplit_last_stages": (None, [vp]),
+    "gtars_fragsplit_last_inflate": (None, [vp]),
+    "gtars_bgzf_members": (C.c_int, [vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
     "gtars_gtok_write": (C.c_int, [cstr, vp, u64]),
     "gtars_gtok_read": (C.c_int, [cstr, pp, pu64]),
     "gtars_fragments_read": (C.c_int, [cstr, pp]),
@@ -429,6 +431,7 @@ _DEBUG_SIG = {
     "gtars_debug_set_handle_device": (C.c_int, [vp, C.c_int, C.c_int]),
     "gtars_debug_set_assembly_device": (C.c_int, [vp, C.c_int]),
     "gtars_debug_inflate_streams": (C.c_int, [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+    "gtars_debug_inflate_members": (C.c_int, [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp]),
     "gtars_debug_sort_perm": (C.c_int, [vp, vp, vp, u64, u32, vp]),
     "gtars_debug_scan_u32": (C.c_int, [vp, u64, vp]),
     "gtars_debug_seg_max": (C.c_int, [vp, vp, vp, u64, u32, C.c_int, vp]),

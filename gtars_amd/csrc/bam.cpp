@@ -29,34 +29,27 @@ gtars_status block_table(BamFile &f) {
     uint64_t at = 0, uoff = 0;
     while (at < n) {
         const uint64_t i = f.blocks.size();
-        if (n - at < 18) return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " is truncated (" + std::to_string(n - at) + " bytes left in the file)");
-        if (p[at] != 0x1f || p[at + 1] != 0x8b || p[at + 2] != 8)
-            return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " at offset " + std::to_string(at) + " does not start with the gzip magic");
-        if (p[at + 3] != 4) return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " has gzip flags other than FEXTRA: not BGZF");
-        const uint64_t xlen = le16(p + at + 10), x0 = at + 12, x1 = x0 + xlen;
-        if (x1 + 8 > n) return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + ": the extra field runs past the end of the file");
+        BamBlock b;
         uint64_t bsize = 0;
-        bool have = false;
-        for (uint64_t x = x0; x + 4 <= x1;) {
-            const uint64_t slen = le16(p + x + 2);
-            if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= x1) {
-                bsize = le16(p + x + 4);
-                have = true;
-                break;
-            }
-            x += 4 + slen;
+        switch (bgzf_member_at(p, n, at, uoff, b, &bsize)) {
+            case BgzfFrame::ok: break;
+            case BgzfFrame::truncated:
+                return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " is truncated (" + std::to_string(n - at) + " bytes left in the file)");
+            case BgzfFrame::no_magic:
+                return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " at offset " + std::to_string(at) + " does not start with the gzip magic");
+            case BgzfFrame::flags: return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " has gzip flags other than FEXTRA: not BGZF");
+            case BgzfFrame::extra_past_end: return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + ": the extra field runs past the end of the file");
+            case BgzfFrame::no_bc: return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " has no BC subfield (gzip, but not BGZF)");
+            case BgzfFrame::past_end:
+                return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " runs past the end of the file (BSIZE " + std::to_string(bsize) + " at offset " +
+                                                 std::to_string(at) + ", file of " + std::to_string(n) + " bytes)");
+            case BgzfFrame::bsize_small: return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + ": BSIZE is smaller than the member's header and trailer");
+            case BgzfFrame::isize_large:
+                return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + ": ISIZE " + std::to_string(le32(p + at + bsize + 1 - 4)) + " > 65536");
         }
-        if (!have) return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " has no BC subfield (gzip, but not BGZF)");
-        const uint64_t csize = bsize + 1, doff = 12 + xlen;
-        if (at + csize > n)
-            return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + " runs past the end of the file (BSIZE " + std::to_string(bsize) + " at offset " +
-                                             std::to_string(at) + ", file of " + std::to_string(n) + " bytes)");
-        if (csize < doff + 8) return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + ": BSIZE is smaller than the member's header and trailer");
-        const uint32_t isize = le32(p + at + csize - 4);
-        if (isize > BGZF_MAX_ISIZE) return fail(GTARS_ERR_PARSE, f.path + ": " + blk(i) + ": ISIZE " + std::to_string(isize) + " > 65536");
-        f.blocks.push_back(BamBlock{at, (uint32_t)csize, (uint32_t)doff, isize, le32(p + at + csize - 8), uoff});
-        uoff += isize;
-        at += csize;
+        f.blocks.push_back(b);
+        uoff += b.isize;
+        at += b.csize;
     }
     f.n_bytes = uoff;
     return GTARS_OK;

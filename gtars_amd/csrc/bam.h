@@ -8,23 +8,10 @@
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
+#include "bgzf.h"
 #include "guard.h"
 
 namespace gtars {
-
-constexpr uint32_t BGZF_MAX_ISIZE = 65536;
-
-// One BGZF block (a gzip member whose extra field carries BSIZE in a "BC" subfield): where it lies in the file, what its
-// trailer promises, and where its bytes go in the inflated stream.  The table is what a device decoder needs: thousands of
-// independent members of <= 64 KiB with both sizes known before a byte is decoded.
-struct BamBlock {
-    uint64_t coff;   // of the member's first byte in the file
-    uint32_t csize;  // BSIZE + 1: the whole member
-    uint32_t doff;   // of the raw deflate stream inside the member (behind the gzip header)
-    uint32_t isize;  // inflated bytes (trailer), <= BGZF_MAX_ISIZE
-    uint32_t crc;    // CRC-32 of the inflated bytes (trailer)
-    uint64_t uoff;   // prefix sum of isize: the block's first byte in the inflated stream
-};
 
 struct BamRef {
     std::string name;

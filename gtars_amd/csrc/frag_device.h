@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/gtars_amd_host.h"
+#include "bgzf.h"
 
 namespace gtars {
 
@@ -113,6 +114,15 @@ struct FragFileIn {
     // newline the caller may append behind the last line is not part of any member.
     const FragGzMember *members = nullptr;
     uint32_t n_members = 0;
+    // The COMPRESSED form (GTARS_FRAG_INFLATE=device, BGZF files): `text` is null, `comp` is the file as it lies on the disk -- in a
+    // pinned block, readable for 64 bytes behind n_comp --, `blocks` its member table, n = the members' ISIZEs together, + 1 when
+    // `add_newline` (the host has inflated the last non-empty member to learn the text's last byte).  The device inflates every
+    // member to its place in the text and checks length, input used and CRC-32; the appended newline belongs to no member.
+    const unsigned char *comp = nullptr;
+    uint64_t n_comp = 0;
+    const BamBlock *blocks = nullptr;
+    uint32_t n_blocks = 0;
+    bool add_newline = false;
 };
 
 // What comes back for a wave: the token ids of its routed, tokenized fragments REGROUPED BY (file, barcode) on the device (round 5,
@@ -131,9 +141,13 @@ struct FragWaveOut {
     HostArray<uint32_t> run_line;   // [slots]: the wave-wide number of the line that opens the run (lines count through the files in order)
     std::vector<uint64_t> n_reads, n_written;  // per file: lines, routed lines ('#' lines included)
     int64_t first_error_file = -1;     // first file (wave order) with a line the reference fails on, or with a gzip member whose
-                                       // CRC-32 is not its trailer's; -1: none.  The caller reads that file again on the host (zlib's
+                                       // CRC-32 is not its trailer's or which the device decoder refused; -1: none.  The caller reads that file again on the host (zlib's
                                        // own check, the host parser) for the reference's message.
     double t_h2d = 0, t_parse = 0, t_group = 0, t_tok = 0, t_d2h = 0;  // seconds (GTARS_HOST_TIMING)
+    // the device inflate of the wave's compressed files: members, compressed bytes copied, the member kernel's seconds by the
+    // device's clock (measured only with GTARS_HOST_TIMING; part of t_h2d's span)
+    uint64_t n_inflated = 0, comp_bytes = 0;
+    double t_inflate = 0;
 };
 
 // the tokenizer's chromosome dictionary as a device table; created once per pipeline call
@@ -142,9 +156,10 @@ gtars_status frag_chroms_create(const std::vector<std::string> &names, FragChrom
 void frag_chroms_free(FragChroms *c);
 
 // One wave on the calling thread's current device.  The text of all files together must stay below 4 GiB.
+// inflate_ring_kib: the ring of the member kernel (inflate_dev.hip) for files in the compressed form, 8 or 32.
 // unk_id: the id a fragment without hits contributes.  GTARS_ERR_CAPACITY: the wave yields more than 4e9 ids (the caller parses on the host).
 gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms, const std::vector<FragFileIn> &files, uint32_t n_clusters,
-                              uint32_t unk_id, FragWaveOut &out);
+                              uint32_t unk_id, FragWaveOut &out, uint32_t inflate_ring_kib = 32);
 int frag_current_device();  // the calling thread's current HIP device (the wave thread selects the caller's)
 gtars_status frag_select_device(int device);
 

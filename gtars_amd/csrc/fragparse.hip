@@ -15,6 +15,8 @@
 //                     fragments of one (file, barcode) are one run in line order; the runs' ids are written one after the other
 //                     (the unk id where a fragment has none), with where every run starts and which line opens it;
 //   k_crc_*           the gzip members' CRC-32 (the host threads decode the deflate streams raw).
+//   k_inflate<>       (inflate_dev.hip) with GTARS_FRAG_INFLATE=device the members of BGZF files are inflated here, one wave each,
+//                     straight to their places in the text; k_inflate_verdict / k_frag_seal note what the decoder refused.
 // Back to the host go the regrouped ids and two words per (file, barcode) slot; the host is left with one dictionary lookup and
 // one memcpy per run (host.cpp).
 // A line the reference would fail on is only DETECTED here (first file in wave order); the host re-parses that file for the
@@ -29,6 +31,10 @@
 #include <mutex>
 
 namespace gtars {
+
+// inflate_dev.hip: one wave per raw DEFLATE stream, any byte offsets on both sides; ring_kib 8 | 32
+gtars_status launch_inflate_members(const unsigned char *comp, const u64 *in_off, const u32 *in_len, unsigned char *out, const u64 *out_off,
+                                    const u32 *out_cap, u32 n_streams, u32 *out_len, u32 *consumed, u32 *status, u32 ring_kib, hipStream_t st);
 
 namespace {
 
@@ -500,6 +506,28 @@ __global__ void k_crc_members(const CrcMember *__restrict__ mem, u32 n_mem, cons
     if ((s ^ 0xFFFFFFFFu) != m.crc) atomicMin(err_file, m.file);
 }
 
+// ---- the compressed form of a file (GTARS_FRAG_INFLATE=device): what the member kernel (inflate_dev.hip) made of the members
+// A member the decoder refused, or that did not come out at its ISIZE, or whose stream does not end where its trailer starts:
+// the file goes back to the host, like one whose CRC-32 is wrong.
+__global__ void k_inflate_verdict(const u32 *__restrict__ status, const u32 *__restrict__ out_len, const u32 *__restrict__ used,
+                                  const u32 *__restrict__ cap, const u32 *__restrict__ in_len, const u32 *__restrict__ file, u32 n,
+                                  u32 *__restrict__ err_file) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (status[i] != 0u || out_len[i] != cap[i] || used[i] != in_len[i]) atomicMin(err_file, file[i]);
+}
+// The last byte of a compressed file's text is a newline -- the one the caller asked to have appended (bit 31 of the file word), or
+// the one the caller has seen there on the host.  A damaged member may have left anything: the line split behind this relies on
+// the newline, so it is written, and the file is noted.
+__global__ void k_frag_seal(unsigned char *__restrict__ text, const u32 *__restrict__ seal, u32 n, u32 *__restrict__ err_file) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 pos = seal[2 * i], fw = seal[2 * i + 1];
+    if (pos == 0xFFFFFFFFu) return;
+    if (!(fw & 0x80000000u) && text[pos] != '\n') atomicMin(err_file, fw & 0x7FFFFFFFu);
+    text[pos] = '\n';
+}
+
 // the three tables, built once per process on the host
 const CrcTables &crc_tables_host() {
     static const CrcTables t = [] {
@@ -719,7 +747,7 @@ static gtars_status wait_stream(hipStream_t st) {
 }
 
 gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms, const std::vector<FragFileIn> &files, uint32_t n_clusters,
-                              uint32_t unk_id, FragWaveOut &out) {
+                              uint32_t unk_id, FragWaveOut &out, uint32_t inflate_ring_kib) {
     const u32 n_files = (u32)files.size();
     out.n = 0;
     out.n_ids = 0;
@@ -727,12 +755,14 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
     out.n_reads.assign(n_files, 0);
     out.n_written.assign(n_files, 0);
     out.first_error_file = -1;
+    out.n_inflated = out.comp_bytes = 0;
+    out.t_inflate = 0;
     out.ids.reset();
     if (!n_files) return GTARS_OK;
     if (n_clusters >= NO_CLUSTER || n_files >= 65535) return fail(GTARS_ERR_INVALID_ARG, "fragment wave: too many clusters or files for the device path");
     u64 total = 0, total_slots = 0, total_keys = 0;
     for (const FragFileIn &f : files) {
-        if (f.n && f.text[f.n - 1] != '\n') return fail(GTARS_ERR_INTERNAL, "fragment wave: a file's text must end with a newline");
+        if (f.n && !f.comp && f.text[f.n - 1] != '\n') return fail(GTARS_ERR_INTERNAL, "fragment wave: a file's text must end with a newline");
         total += f.n;
         total_slots += f.n_slots;
         total_keys += f.n_key_bytes;
@@ -784,7 +814,26 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
     // instead of two per file and three small ones from pageable memory (1000 files: 2000 calls of 20 us each before).
     // staging: file_off | slot_off | key_off [m1 words each] | slots | keys | gzip members
     size_t n_members = 0;
-    for (const FragFileIn &f : files) n_members += f.n_members;
+    size_t n_zmem = 0, n_zfiles = 0, comp_total = 0;  // the compressed form: members to inflate here, their files, compressed bytes
+    for (const FragFileIn &f : files) {
+        n_members += f.n_members;
+        if (!f.comp) continue;
+        if (f.n_members) return fail(GTARS_ERR_INTERNAL, "fragment wave: a compressed file has no host-inflated members");
+        // (the member kernel writes where this table says: every member inside its file, on both sides, before anything is launched)
+        u64 u = 0;
+        for (u32 k = 0; k < f.n_blocks; ++k) {
+            const BamBlock &b = f.blocks[k];
+            if (b.coff + b.csize > f.n_comp || b.csize < b.doff + 8u || b.isize > BGZF_MAX_ISIZE || b.uoff != u)
+                return fail(GTARS_ERR_INTERNAL, "fragment wave: a BGZF member table does not fit its file");
+            u += b.isize;
+        }
+        if (u + (f.add_newline ? 1u : 0u) != f.n) return fail(GTARS_ERR_INTERNAL, "fragment wave: a BGZF member table does not add up to its text");
+        n_members += f.n_blocks;
+        n_zmem += f.n_blocks;
+        n_zfiles += 1;
+        comp_total += (f.n_comp + 15) & ~(size_t)15;
+    }
+    if (n_zmem >= 0xFFFFFFF0ull) return fail(GTARS_ERR_INVALID_ARG, "fragment wave: too many BGZF members");
     const size_t stage_slots = pad(3 * m1 * 4), stage_keys = stage_slots + pad(total_slots * sizeof(FragSlot)),
                  stage_mem = stage_keys + pad(total_keys + 16), stage_bytes = stage_mem + pad(n_members * sizeof(CrcMember)) + 256;
     char *staging = (char *)fr.host(stage_bytes);
@@ -802,7 +851,8 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
         file_off[f + 1] = file_off[f] + (u32)files[f].n;
         slot_off[f + 1] = slot_off[f] + files[f].n_slots;
         key_off[f + 1] = key_off[f] + files[f].n_key_bytes;
-        if (files[f].n) GT_HIP(hipMemcpyAsync(d_text.as<char>() + file_off[f], files[f].text, files[f].n, hipMemcpyHostToDevice, st));
+        if (files[f].n && !files[f].comp)
+            GT_HIP(hipMemcpyAsync(d_text.as<char>() + file_off[f], files[f].text, files[f].n, hipMemcpyHostToDevice, st));
         if (files[f].n_slots) memcpy(staging + stage_slots + (size_t)slot_off[f] * sizeof(FragSlot), files[f].slots, (size_t)files[f].n_slots * sizeof(FragSlot));
         if (files[f].n_key_bytes) memcpy(staging + stage_keys + key_off[f], files[f].keys, files[f].n_key_bytes);
     }
@@ -816,13 +866,77 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
     GT_HIP(hipMemcpyAsync(d_file_off, file_off, 3 * m1 * 4, hipMemcpyHostToDevice, st));
     GT_HIP(hipMemsetAsync(d_written, 0, (size_t)n_files * 4, st));
     GT_HIP(hipMemsetAsync(d_err, 0xFF, 4, st));
-    // ---- the gzip members' CRC-32 (the host threads inflated them raw) ----
+    // ---- the compressed files: their bytes to the device, one wave per member inflates them to their places in the text ----
+    hipEvent_t ev_inf[2] = {nullptr, nullptr};
+    struct EvEnd {
+        hipEvent_t *e;
+        ~EvEnd() {
+            for (int k = 0; k < 2; ++k)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } ev_end{ev_inf};
+    if (n_zfiles) {
+        // work list (host, pinned): in_off | out_off [u64] | in_len | cap | file [u32 per member] | seal: pos | file + flag [per file]
+        const size_t wl_bytes = n_zmem * (8 + 8 + 4 + 4 + 4) + n_zfiles * 8 + 64;
+        char *wl = (char *)fr.host(wl_bytes);
+        if (!wl) return fail(GTARS_ERR_INTERNAL, "out of host memory");
+        u64 *h_in_off = (u64 *)wl, *h_out_off = h_in_off + n_zmem;
+        u32 *h_in_len = (u32 *)(h_out_off + n_zmem), *h_cap = h_in_len + n_zmem, *h_file = h_cap + n_zmem, *h_seal = h_file + n_zmem;
+        Workspace &ws_z = tls_workspace(10, st);
+        if ((s = ws_z.reserve(pad(comp_total + 256) + pad(wl_bytes) + pad(n_zmem * 12 + 64) + 1024))) return s;
+        Carve cz{(char *)ws_z.ptr, 0};
+        unsigned char *d_comp = cz.take<unsigned char>(comp_total + 256);  // (256-byte aligned; the decoder reads up to 48 bytes past a stream)
+        char *d_wl = cz.take<char>(wl_bytes);
+        u32 *d_zres = cz.take<u32>(n_zmem * 3 + 16);  // out_len | consumed | status
+        size_t at = 0, k = 0, zf = 0;
+        for (u32 f = 0; f < n_files; ++f) {
+            const FragFileIn &fi = files[f];
+            if (!fi.comp) continue;
+            if (fi.n_comp) GT_HIP(hipMemcpyAsync(d_comp + at, fi.comp, fi.n_comp, hipMemcpyHostToDevice, st));
+            for (u32 b = 0; b < fi.n_blocks; ++b, ++k) {
+                const BamBlock &bb = fi.blocks[b];
+                h_in_off[k] = at + bb.coff + bb.doff;
+                h_in_len[k] = bb.csize - bb.doff - 8u;
+                h_out_off[k] = (u64)file_off[f] + bb.uoff;
+                h_cap[k] = bb.isize;
+                h_file[k] = f;
+            }
+            // the text's last byte: the newline the caller asked for, or the one the caller has seen there
+            h_seal[2 * zf] = fi.n ? file_off[f + 1] - 1u : 0xFFFFFFFFu;
+            h_seal[2 * zf + 1] = f | (fi.add_newline ? 0x80000000u : 0u);
+            ++zf;
+            at += (fi.n_comp + 15) & ~(size_t)15;
+        }
+        GT_HIP(hipMemcpyAsync(d_wl, wl, wl_bytes, hipMemcpyHostToDevice, st));
+        const u64 *d_in_off = (const u64 *)d_wl, *d_out_off = d_in_off + n_zmem;
+        const u32 *d_in_len = (const u32 *)(d_out_off + n_zmem), *d_cap = d_in_len + n_zmem, *d_zfile = d_cap + n_zmem, *d_seal = d_zfile + n_zmem;
+        u32 *d_zlen = d_zres, *d_zused = d_zlen + n_zmem, *d_zst = d_zused + n_zmem;
+        const bool timed = cfg_get("GTARS_HOST_TIMING") != nullptr;
+        if (timed) {
+            GT_HIP(hipEventCreate(&ev_inf[0]));
+            GT_HIP(hipEventCreate(&ev_inf[1]));
+            GT_HIP(hipEventRecord(ev_inf[0], st));
+        }
+        GT_TRY(launch_inflate_members(d_comp, d_in_off, d_in_len, d_text.as<unsigned char>(), d_out_off, d_cap, (u32)n_zmem, d_zlen, d_zused, d_zst,
+                                      inflate_ring_kib, st));
+        if (timed) GT_HIP(hipEventRecord(ev_inf[1], st));
+        if (n_zmem)
+            hipLaunchKernelGGL(k_inflate_verdict, dim3(((u32)n_zmem + 255) / 256), dim3(256), 0, st, (const u32 *)d_zst, (const u32 *)d_zlen,
+                               (const u32 *)d_zused, d_cap, d_in_len, d_zfile, (u32)n_zmem, d_err);
+        hipLaunchKernelGGL(k_frag_seal, dim3(((u32)n_zfiles + 255) / 256), dim3(256), 0, st, d_text.as<unsigned char>(), d_seal, (u32)n_zfiles, d_err);
+        GT_HIP(hipGetLastError());
+        out.n_inflated = n_zmem;
+        for (const FragFileIn &fi : files)
+            if (fi.comp) out.comp_bytes += fi.n_comp;
+    }
+    // ---- the gzip members' CRC-32 (the host threads inflated them raw; the device, the compressed files') ----
     CrcMember *h_mem_p = (CrcMember *)(staging + stage_mem);
     size_t h_mem_n = 0;
     u32 crc_chunks = 0, crc_groups = 0;
     for (u32 f = 0; f < n_files; ++f)
-        for (u32 k = 0; k < files[f].n_members; ++k) {
-            const FragGzMember &gm = files[f].members[k];
+        for (u32 k = 0; k < files[f].n_members + (files[f].comp ? files[f].n_blocks : 0u); ++k) {
+            const FragGzMember gm = files[f].comp ? FragGzMember{files[f].blocks[k].uoff, files[f].blocks[k].isize, files[f].blocks[k].crc}
+                                                  : files[f].members[k];
             if (gm.off + gm.len > files[f].n) return fail(GTARS_ERR_INTERNAL, "fragment wave: a gzip member lies outside its file's text");
             CrcMember m{file_off[f] + (u32)gm.off, (u32)gm.len, gm.crc, f, crc_chunks, crc_groups};
             const u32 n_ch = ((u32)gm.len + CRC_CHUNK - 1) / CRC_CHUNK;
@@ -851,6 +965,11 @@ gtars_status frag_wave_device(const gtars_index_t *ix, const FragChroms *chroms,
     GT_TRY(wait_stream(st));
     const double t1 = now_s();
     out.t_h2d = t1 - t0;
+    if (ev_inf[1]) {
+        float ms = 0;
+        GT_HIP(hipEventElapsedTime(&ms, ev_inf[0], ev_inf[1]));
+        out.t_inflate = ms * 1e-3;
+    }
     // ---- line ends ----
     u32 *d_cnt = d_chunks.as<u32>(), *d_base = d_cnt + n_chunks + 1;
     u32 n_lines = 0;

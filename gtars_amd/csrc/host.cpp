@@ -239,6 +239,44 @@ bool inflate_gzip_members_raw(const unsigned char *p, size_t n, Out &out, std::v
     return true;
 }
 
+// The member table of a BGZF file -- what bgzip writes, hence cellranger-atac's fragments.tsv.gz and anything tabix-indexed --
+// without inflating a byte: the fragment pipeline's device inflate (GTARS_FRAG_INFLATE=device) takes such a file compressed, as
+// thousands of independent streams of <= 64 KiB whose sizes their headers and trailers carry.  -> false unless EVERY member is a
+// BGZF block (bgzf.h: FEXTRA alone with a BC subfield of length 2) and BSIZE + 1 leads from member to member to exactly the end
+// of the file: plain gzip, a plain member behind BGZF ones, bytes behind the last member, a truncated last member are all "not
+// BGZF" and take the ordinary reader, with its checks and messages.
+bool bgzf_member_table(const unsigned char *p, size_t n, std::vector<gtars::BamBlock> &blocks) {
+    blocks.clear();
+    if (n < 18) return false;
+    uint64_t at = 0, uoff = 0;
+    while (at < n) {
+        gtars::BamBlock b;
+        uint64_t bsize = 0;
+        if (gtars::bgzf_member_at(p, n, at, uoff, b, &bsize) != gtars::BgzfFrame::ok) {
+            blocks.clear();
+            return false;
+        }
+        blocks.push_back(b);
+        uoff += b.isize;
+        at += b.csize;
+    }
+    return true;
+}
+// The last byte of such a file's text, by inflating its last non-empty member on the host (at most 64 KiB): the loader appends a
+// newline to a text that lacks one, and reserves its byte before the device has inflated anything.  -> the byte | -1: the file has
+// no text | -2: the host decoder refuses the member (the file then takes the ordinary reader).  `p` readable 16 bytes beyond the file.
+int bgzf_last_byte(const unsigned char *p, const std::vector<gtars::BamBlock> &blocks) {
+    for (size_t k = blocks.size(); k-- > 0;) {
+        const gtars::BamBlock &b = blocks[k];
+        if (!b.isize) continue;
+        std::string out;
+        size_t used = 0, done = 0;
+        if (!gtars::fastinf::inflate_raw(p + b.coff + b.doff, (size_t)b.csize - b.doff - 8, &used, out, done) || done != b.isize) return -2;
+        return (unsigned char)out[done - 1];
+    }
+    return -1;
+}
+
 // by_magic: gunzip whatever starts with the gzip magic, whatever the extension (open_vcf, gtars-vrs/src/vcf.rs:56-73)
 bool read_all(const std::string &path, std::string &out, std::string &err, bool by_magic = false) {
     out.clear();
@@ -3738,16 +3776,68 @@ struct TextBuf {
 struct TextFile {
     TextBuf data;
     std::vector<gtars::FragGzMember> members;  // gzip members whose CRC-32 the device still has to check
+    // the compressed form (a BGZF file under GTARS_FRAG_INFLATE=device): `data` stays empty, the file's bytes lie in `comp`
+    // (n_comp of them, then 64 zero bytes), `blocks` is its member table and n_text what the device will make of it
+    gtars::HostBlock comp;
+    size_t n_comp = 0, n_text = 0;
+    std::vector<gtars::BamBlock> blocks;
+    bool compressed = false, add_newline = false;
+    size_t text_bytes() const { return compressed ? n_text : data.size(); }
     std::vector<gtars::FragSlot> slots;
     std::string keys;
     gtars_status st = GTARS_OK;
     std::string err;
 };
 
-void load_text_file(const std::string &path, const gtars_barcode_map &m, TextFile &out) {
+// GTARS_FRAG_INFLATE = host (default) | device: who inflates the BGZF files of the device route.  Anything but BGZF -- plain gzip,
+// plain text -- is inflated by the host threads either way.
+bool frag_inflate_on_device() {
+    const char *e = cfg_get("GTARS_FRAG_INFLATE");
+    return e && strcmp(e, "device") == 0;
+}
+// GTARS_FRAG_INFLATE_RING = 32 (default) | 8: the member kernel's ring in KiB (inflate_dev.hip)
+uint32_t frag_inflate_ring_kib() {
+    const char *e = cfg_get("GTARS_FRAG_INFLATE_RING");
+    return e && atoi(e) == 8 ? 8u : 32u;
+}
+
+// the file as it is, in a pinned block with 64 zero bytes behind it, if it is BGZF whose last byte the host can tell
+bool load_bgzf_compressed(const std::string &path, TextFile &out) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    struct Close {
+        FILE *f;
+        ~Close() { fclose(f); }
+    } close_f{f};
+    struct stat sb;
+    if (fstat(fileno(f), &sb) != 0 || sb.st_size < 18 || !S_ISREG(sb.st_mode)) return false;
+    const size_t n = (size_t)sb.st_size;
+    if (!out.comp.alloc(n + 64)) throw std::bad_alloc();
+    unsigned char *p = (unsigned char *)out.comp.p;
+    if (fread(p, 1, n, f) != n || fgetc(f) != EOF) return false;  // (a file that changes under the reader: the ordinary path)
+    memset(p + n, 0, 64);
+    if (!bgzf_member_table(p, n, out.blocks)) return false;
+    const int last = bgzf_last_byte(p, out.blocks);
+    if (last == -2) return false;
+    out.n_comp = n;
+    out.add_newline = last >= 0 && last != '\n';  // (BufRead::lines: a last line without one still counts)
+    out.n_text = (out.blocks.empty() ? 0 : (size_t)(out.blocks.back().uoff + out.blocks.back().isize)) + (out.add_newline ? 1 : 0);
+    out.compressed = true;
+    return true;
+}
+
+// on_device: BGZF files may stay compressed (the device route under GTARS_FRAG_INFLATE=device)
+void load_text_file(const std::string &path, const gtars_barcode_map &m, TextFile &out, bool on_device = false) {
     std::string err;
     bool have = false;
-    if (extension_of(path) == "gz" && !cfg_get("GTARS_FRAG_HOST_CRC")) {  // (the switch: A/B and tests)
+    if (on_device && extension_of(path) == "gz") {
+        have = load_bgzf_compressed(path, out);
+        if (!have) {
+            out.comp.reset();
+            out.blocks.clear();
+        }
+    }
+    if (!have && extension_of(path) == "gz" && !cfg_get("GTARS_FRAG_HOST_CRC")) {  // (the switch: A/B and tests)
         std::string raw;
         size_t n_raw = 0;
         if (read_file_padded(path, raw, n_raw)) have = inflate_gzip_members_raw((const unsigned char *)raw.data(), n_raw, out.data, out.members);
@@ -3762,7 +3852,7 @@ void load_text_file(const std::string &path, const gtars_barcode_map &m, TextFil
         }
         out.data.assign(plain);
     }
-    if (!out.data.empty() && out.data.back() != '\n') out.data.push_back('\n');  // (BufRead::lines: a last line without one still counts)
+    if (!out.compressed && !out.data.empty() && out.data.back() != '\n') out.data.push_back('\n');  // (BufRead::lines: a last line without one still counts)
     const std::string prefix = remove_all_extensions(path) + "+";
     auto lo = std::lower_bound(m.sorted.begin(), m.sorted.end(), prefix, [](const auto &a, const std::string &p) { return *a.first < p; });
     auto hi = lo;
@@ -3792,10 +3882,16 @@ void load_text_file(const std::string &path, const gtars_barcode_map &m, TextFil
 template <class Sink, class Idle, class Failed>
 gtars_status stream_text_files(const std::vector<std::string> &files, const gtars_barcode_map &m, uint64_t byte_limit, int device, Sink &&sink,
                                Idle &&wait_idle, Failed &&failed, bool *too_large) {
+
     const size_t n = files.size();
     if (!n) return GTARS_OK;
+    const bool z_on_device = frag_inflate_on_device();
     const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_thread_budget(64), n));
-    const size_t window = (size_t)nt * 4, max_batch = std::min<size_t>((size_t)nt * 4, 60000);
+    // (files that stay compressed are "loaded" as fast as they are read, and the device inflates a batch in the time of its
+    // longest member as long as the members do not outnumber the waves the chip holds -- some 370 members per 24 MB of text against
+    // 1024 to 2048: such files count a quarter of their text against the default batch size, and four times as many may be in flight)
+    const size_t z_weight = z_on_device ? 4 : 1;
+    const size_t window = (size_t)nt * 4 * z_weight, max_batch = std::min<size_t>((size_t)nt * 4 * z_weight, 60000);
     // A batch's text: 24 MB at most.  The loaders finish their last files together -- a third of a 48-file folder is ready at once --
     // and ONE batch of it keeps one device thread busy for 3.6 ms behind the last file while the other has nothing to do; smaller
     // batches run side by side and the last one is short (same box, median of 7 calls: 14.7 ms uncapped, 14.6 at 40 MB, 12.8 at
@@ -3821,7 +3917,7 @@ gtars_status stream_text_files(const std::vector<std::string> &files, const gtar
                 if (stop) return;
             }
             try {
-                load_text_file(files[i], m, tf[i]);
+                load_text_file(files[i], m, tf[i], z_on_device);
             } catch (const std::exception &ex) {  // (out of memory on a loader thread: the file's error, not the process's end)
                 tf[i].st = GTARS_ERR_INTERNAL;
                 tf[i].err = std::string("fragment pipeline: ") + ex.what();
@@ -3847,14 +3943,18 @@ gtars_status stream_text_files(const std::vector<std::string> &files, const gtar
         wait_idle();
         if (failed()) break;
         size_t hi = lo;
-        uint64_t bytes = 0;
+        uint64_t bytes = 0, budget = 0;  // the batch's text; ... as it counts against batch_bytes
         {
             std::unique_lock<std::mutex> lk(mx);
             cvx.wait(lk, [&] { return done[lo] != 0; });
-            // (a batch is at least one file -- of up to byte_limit --, and grows while it stays below batch_bytes)
+            // (a batch is at least one file -- of up to byte_limit --, and grows while it stays below batch_bytes; an explicit
+            // GTARS_FRAG_BATCH_MB counts every file's text in full)
+            auto cost = [&](const TextFile &f) { return f.compressed && !bmb ? f.text_bytes() / z_weight : f.text_bytes(); };
             while (hi < n && done[hi] && !tf[hi].st && hi - lo < max_batch &&
-                   (hi == lo ? tf[hi].data.size() < byte_limit : bytes + tf[hi].data.size() < std::min(byte_limit, batch_bytes))) {
-                bytes += tf[hi].data.size();
+                   (hi == lo ? tf[hi].text_bytes() < byte_limit
+                             : bytes + tf[hi].text_bytes() < byte_limit && budget + cost(tf[hi]) < batch_bytes)) {
+                bytes += tf[hi].text_bytes();
+                budget += cost(tf[hi]);
                 ++hi;
             }
         }
@@ -3907,6 +4007,7 @@ gtars_status for_each_split_wave(const std::vector<std::string> &files, const gt
 // device while the next one is being read.
 
 thread_local double g_frag_stages[12];  // gtars_fragsplit_last_stages
+thread_local double g_frag_inflate[4];  // gtars_fragsplit_last_inflate
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -3918,6 +4019,10 @@ struct FragStages {
     double t_enter = now_s(), t_begin = 0, t_split_done = 0, t_tok_done = 0;  // clock readings
     double t_append = 0;              // host route: the per-cluster appends between two waves
     double td[5] = {0, 0, 0, 0, 0};   // device route: the waves' five device stages
+    // device route, GTARS_FRAG_INFLATE=device: BGZF members inflated on the device, files handed back to the host's decoders,
+    // compressed bytes copied to the device, the member kernel's seconds (by the device's clock; part of td[0]'s span)
+    uint64_t z_members = 0, z_back = 0, z_bytes = 0;
+    double z_kernel = 0;
     // t_tok: the wave workers' busy seconds
     void publish(size_t n_files, size_t n_waves, size_t n_clusters, double t_tok) const {
         const double t_end = now_s();
@@ -3930,6 +4035,7 @@ struct FragStages {
         g[5] = t_tok_done - t_split_done;  // ... of which behind the last wave's files
         g[6] = t_end - t_tok_done;         // regroup by barcode
         for (int k = 0; k < 5; ++k) g[7 + k] = td[k];
+        g_frag_inflate[0] = (double)z_members, g_frag_inflate[1] = (double)z_back, g_frag_inflate[2] = (double)z_bytes, g_frag_inflate[3] = z_kernel;
         if (!cfg_get("GTARS_HOST_TIMING")) return;
         fprintf(stderr, "[gtars host timing] fragsplit_tokenize: %zu files in %zu wave(s), %s %.3f s, per-cluster append %.3f s, %s %.3f s (of which %.3f s after the last wave was read; %llu fragments), regroup of %zu clusters %.3f s\n",
                 n_files, n_waves, on_device ? "gunzip (host threads)" : "gunzip + parse + route", g[2], t_append,
@@ -3939,6 +4045,9 @@ struct FragStages {
         if (on_device)
             fprintf(stderr, "[gtars host timing]   device waves: text to the device %.3f s, line split + parse + sort by cluster %.3f s, gather %.3f s, tokenize %.3f s, results to the host %.3f s\n",
                     td[0], td[1], td[2], td[3], td[4]);
+        if (on_device && frag_inflate_on_device())
+            fprintf(stderr, "[gtars host timing]   device inflate: %llu BGZF members inflated on the device, %llu files handed back to the host, %llu compressed bytes copied, member kernel %.6f s\n",
+                    (unsigned long long)z_members, (unsigned long long)z_back, (unsigned long long)z_bytes, z_kernel);
     }
 };
 
@@ -4044,6 +4153,9 @@ struct DeviceWave {
     std::vector<std::vector<FragRun>> runs;  // [n_clusters]
     uint64_t n = 0, reads = 0;               // tokenized fragments, lines
     double td[5] = {0, 0, 0, 0, 0};
+    // the device inflate: members inflated there, files handed back to the host threads, compressed bytes copied, kernel seconds
+    uint64_t z_members = 0, z_back = 0, z_bytes = 0;
+    double z_kernel = 0;
     gtars_status st = GTARS_OK;
     std::string err;
 };
@@ -4071,12 +4183,42 @@ void cut_device_runs(DeviceWave &w, size_t nc) {
 void run_device_wave(const gtars_tokenizer *t, const gtars::FragChroms *d_chroms, const std::vector<std::string> &files,
                      const gtars_barcode_map &m, DeviceWave &w) {
     const size_t nc = m.labels.size();
-    std::vector<gtars::FragFileIn> in;
-    for (TextFile &f : w.tf)
-        in.push_back({f.data.data(), f.data.size(), f.slots.data(), (uint32_t)f.slots.size(), f.keys.data(), (uint32_t)f.keys.size(),
-                      f.members.data(), (uint32_t)f.members.size()});
+    const uint32_t ring_kib = frag_inflate_ring_kib();
     gtars::FragWaveOut o;
-    w.st = gtars::frag_wave_device(t->index, d_chroms, in, (uint32_t)nc, t->unk_id, o);
+    for (;;) {
+        std::vector<gtars::FragFileIn> in;
+        for (TextFile &f : w.tf) {
+            gtars::FragFileIn fi;
+            fi.text = f.compressed ? nullptr : f.data.data();
+            fi.n = f.text_bytes();
+            fi.slots = f.slots.data(), fi.n_slots = (uint32_t)f.slots.size();
+            fi.keys = f.keys.data(), fi.n_key_bytes = (uint32_t)f.keys.size();
+            fi.members = f.members.data(), fi.n_members = (uint32_t)f.members.size();
+            if (f.compressed) {
+                fi.comp = (const unsigned char *)f.comp.p, fi.n_comp = f.n_comp;
+                fi.blocks = f.blocks.data(), fi.n_blocks = (uint32_t)f.blocks.size();
+                fi.add_newline = f.add_newline;
+            }
+            in.push_back(fi);
+        }
+        w.st = gtars::frag_wave_device(t->index, d_chroms, in, (uint32_t)nc, t->unk_id, o, ring_kib);
+        if (w.st || o.first_error_file < 0 || !w.tf[(size_t)o.first_error_file].compressed) break;
+        // The device refused a member of a compressed file, or its CRC-32 is wrong: the file is read again by the host's decoders --
+        // what they refuse ends the wave with their message, as under GTARS_FRAG_INFLATE=host; what they accept (a valid stream of
+        // the one class the device decoder refuses by design) joins the wave as text, and the wave runs again.
+        const size_t k = (size_t)o.first_error_file;
+        TextFile again;
+        load_text_file(files[w.first_file + k], m, again);
+        w.z_back += 1;
+        if (again.st) {
+            w.st = again.st;
+            w.err = again.err;
+            for (TextFile &f : w.tf) f.data.release(), f.comp.reset();
+            return;
+        }
+        w.tf[k] = std::move(again);
+    }
+    w.z_members = o.n_inflated, w.z_bytes = o.comp_bytes, w.z_kernel = o.t_inflate;
     if (w.st) {  // (GTARS_ERR_CAPACITY: more ids than the device route's 32-bit positions -- the whole call on the host route)
         w.err = gtars_last_error();
     } else if (o.first_error_file >= 0) {
@@ -4092,7 +4234,7 @@ void run_device_wave(const gtars_tokenizer *t, const gtars::FragChroms *d_chroms
         w.dev = std::move(o);
         cut_device_runs(w, nc);
     }
-    for (TextFile &f : w.tf) f.data.release();  // the text is on the device (or no longer needed): the block back to the pool
+    for (TextFile &f : w.tf) f.data.release(), f.comp.reset();  // the text is on the device (or no longer needed): the blocks back to the pool
 }
 
 // *redo_on_host: this input is not for the device route (a file beyond its text limit, a wave with more ids than its 32-bit
@@ -4145,6 +4287,7 @@ gtars_status fragsplit_tokenize_device(const gtars_tokenizer *t, const std::vect
         reads += w.reads;
         rep.n_fragments += w.n;
         for (int k = 0; k < 5; ++k) rep.td[k] += w.td[k];
+        rep.z_members += w.z_members, rep.z_back += w.z_back, rep.z_bytes += w.z_bytes, rep.z_kernel += w.z_kernel;
     }
     // Every cluster regrouped by barcode.  The waves arrive regrouped by (file, barcode) (FragWaveOut): what is left is, per cluster,
     // the runs in the order their first lines appear -- wave after wave, and inside a wave by line number: the first-seen barcode
@@ -4349,6 +4492,34 @@ static gtars_status gtars_fragsplit_impl(const char *files_dir, const gtars_barc
 
 void gtars_fragsplit_last_stages(double *out12) {
     if (out12) memcpy(out12, g_frag_stages, sizeof g_frag_stages);
+}
+
+void gtars_fragsplit_last_inflate(double *out4) {
+    if (out4) memcpy(out4, g_frag_inflate, sizeof g_frag_inflate);
+}
+
+gtars_status gtars_bgzf_members(const void *data, uint64_t n, uint64_t cap, uint64_t *n_members, uint64_t *stream_off, uint32_t *stream_len,
+                                uint32_t *isize, uint32_t *crc, uint64_t *uoff, int32_t *last_byte) {
+    return gtars::guarded([&]() -> gtars_status {
+        if ((!data && n) || !n_members) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        std::string raw((const char *)data, (size_t)n);
+        raw.append(16, '\0');  // (the host decoder may read into them)
+        std::vector<gtars::BamBlock> blocks;
+        *n_members = 0;
+        if (last_byte) *last_byte = -1;
+        if (!bgzf_member_table((const unsigned char *)raw.data(), (size_t)n, blocks)) return GTARS_ERR_PARSE;
+        *n_members = blocks.size();
+        for (size_t k = 0; k < blocks.size() && k < cap; ++k) {
+            const gtars::BamBlock &b = blocks[k];
+            if (stream_off) stream_off[k] = b.coff + b.doff;
+            if (stream_len) stream_len[k] = b.csize - b.doff - 8;
+            if (isize) isize[k] = b.isize;
+            if (crc) crc[k] = b.crc;
+            if (uoff) uoff[k] = b.uoff;
+        }
+        if (last_byte) *last_byte = bgzf_last_byte((const unsigned char *)raw.data(), blocks);
+        return GTARS_OK;
+    });
 }
 
 // the pipeline over an explicit list of files, visited in the order given (the directory form passes its regular files in byte

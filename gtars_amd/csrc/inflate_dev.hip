@@ -15,7 +15,9 @@
 //   input    2 KiB ring (+ 16 mirrored bytes), refilled a KiB at a time, the next KiB already in registers
 //   tables   literal/length: 512 entries (9 bits), distance: 256 entries (8 bits), u32 each; a longer code -- rare -- is decoded
 //            bit by bit from the canonical code's per-length counts and its symbols in code order (what zlib's puff.c does)
-// = 39.5 KiB per wave: four streams per CU, 1024 at once on the chip.
+// = 39.5 KiB per wave: four streams per CU, 1024 at once on the chip.  The body is a template on the ring's size: the members of a
+// BGZF file inflate to 64 KiB at most and straight into the text they are part of, so an 8-KiB ring (14.5 KiB per wave) serves
+// them, with the rare far match read back from the result (see k_inflate).
 //
 // The decoder REFUSES rather than diagnoses, like the host's inflate_fast.h: status != 0 (invalid code, distance in front of the
 // stream, input or output exhausted) sends the file back to the host path, whose checks and messages are the ones a user sees.
@@ -30,7 +32,7 @@ namespace gtars {
 
 namespace {
 
-constexpr u32 INF_WIN = 32768, INF_WIN_MASK = INF_WIN - 1u;
+constexpr u32 INF_WIN = 32768;  // the format's largest distance: a ring of this size holds every match source
 constexpr u32 INF_IN = 2048, INF_CHUNK = 1024;
 constexpr u32 INF_LL_BITS = 9, INF_D_BITS = 8;
 constexpr u32 INF_FLUSH = 4096;
@@ -66,9 +68,10 @@ __device__ __forceinline__ u32 d_entry(u32 sym) {
 }
 __device__ __forceinline__ u32 bitrev(u32 code, u32 len) { return __brev(code) >> (32u - len); }
 
-// per-wave LDS
+// per-wave LDS; WIN: the window ring's bytes (a power of two)
+template <u32 WIN>
 struct InfLds {
-    unsigned char win[INF_WIN];
+    alignas(16) unsigned char win[WIN];
     unsigned char in[INF_IN + 16];
     u32 ll[1u << INF_LL_BITS];
     u32 dd[1u << INF_D_BITS];
@@ -79,8 +82,8 @@ struct InfLds {
 };
 
 struct BitReader {
-    const unsigned char *src;  // the stream (global)
-    u32 n;                     // its length
+    const unsigned char *src;  // the stream's first byte, aligned down to 16 (global)
+    u32 n;                     // the stream's end, counted from src
     u64 bb;                    // bit buffer
     u32 bn;                    // valid bits
     u32 ip;                    // bytes of the stream consumed into the buffer
@@ -93,11 +96,12 @@ struct BitReader {
 // this lane's 16 bytes of the chunk at `at` (zeros beyond the stream: the decoder notices exhaustion by ip > n)
 __device__ __forceinline__ uint4 inf_fetch(const BitReader &r, u32 at, int lane) {
     const u32 o = at + (u32)lane * 16u;
-    // (the stream's buffer is padded to a multiple of 16 bytes + 16 by the caller, and its start is 16-byte aligned)
+    // (src is 16-byte aligned; the caller's buffer is readable for 48 bytes behind the stream's end: o + 16 <= n + 31)
     if (o < r.n + 16u) return *reinterpret_cast<const uint4 *>(r.src + o);
     return make_uint4(0, 0, 0, 0);
 }
-__device__ __forceinline__ void inf_stage(InfLds &L, BitReader &r, int lane) {
+template <class LDS>
+__device__ __forceinline__ void inf_stage(LDS &L, BitReader &r, int lane) {
     // write the pre-fetched chunk into its half of the ring, request the next one
     const u32 slot = r.staged & (INF_IN - 1u);
     *reinterpret_cast<uint4 *>(L.in + slot + (u32)lane * 16u) = r.pre;
@@ -107,13 +111,15 @@ __device__ __forceinline__ void inf_stage(InfLds &L, BitReader &r, int lane) {
 }
 // request the two aligned words around ip (all lanes the same address: a broadcast).  Aligned reads: an 8-byte LDS read at an
 // arbitrary byte offset is no fast path.
-__device__ __forceinline__ void inf_request(InfLds &L, BitReader &r, int lane) {
+template <class LDS>
+__device__ __forceinline__ void inf_request(LDS &L, BitReader &r, int lane) {
     while (r.ip + 16u > r.staged) inf_stage(L, r, lane);  // (the bytes [ip & ~7, + 16) must be staged)
     const u32 at = r.ip & (INF_IN - 1u) & ~7u;
     r.w0 = *reinterpret_cast<const u64 *>(L.in + at);
     r.w1 = *reinterpret_cast<const u64 *>(L.in + at + 8u);
 }
-__device__ __forceinline__ void inf_refill(InfLds &L, BitReader &r, int lane) {
+template <class LDS>
+__device__ __forceinline__ void inf_refill(LDS &L, BitReader &r, int lane) {
     // the eight bytes at ip, out of the two words requested by the previous refill
     const u32 sh = (r.ip & 7u) * 8u;
     const u64 a = ((u64)uni((u32)(r.w0 >> 32)) << 32) | uni((u32)r.w0), b = ((u64)uni((u32)(r.w1 >> 32)) << 32) | uni((u32)r.w1);
@@ -155,7 +161,8 @@ __device__ u32 inf_slow(BitReader &r, const unsigned short *cnt, const unsigned 
 // Decode tables of a canonical Huffman code given as code lengths in L.lens[base, base + n).  Lanes work on symbols side by side.
 // kind 0: literal/length, 1: distance.  -> false: over-subscribed or incomplete (a distance code of no symbol, or of a single
 // 1-bit one, is accepted)
-__device__ bool inf_build(InfLds &L, u32 base, u32 n, int kind, int lane) {
+template <class LDS>
+__device__ bool inf_build(LDS &L, u32 base, u32 n, int kind, int lane) {
     u32 *table = kind ? L.dd : L.ll;
     unsigned short *cnt = kind ? L.d_cnt : L.ll_cnt, *syms = kind ? L.d_sym : L.ll_sym;
     const u32 tb = kind ? INF_D_BITS : INF_LL_BITS;
@@ -247,36 +254,63 @@ __device__ unsigned long long g_inf_stats[8];  // literals, matches, blocks, cyc
 #endif
 // status: 0 ok | 1 invalid block type / stored length | 2 invalid code lengths | 3 invalid symbol or distance | 4 input exhausted |
 // 5 output capacity exceeded
+//
+// A stream may start at ANY byte of `comp` and its output at ANY byte of `out` (the members of a BGZF file lie back to back, in
+// the file and in the inflated text): the input is fetched from the 16-byte boundary below the stream and the bit reader starts at
+// the misalignment; `comp` (16-byte aligned) must be readable for 48 bytes behind the end of every stream -- the loads may touch
+// a neighbour's compressed bytes, never more.  Output positions are counted from the 16-byte boundary below the stream's first
+// output byte (op, flushed and cap below start at the misalignment `omis`), so a ring position is congruent to its global address
+// modulo 16: the flush stores the aligned interior as 16-byte vectors and the head and tail byte by byte, and no store touches a
+// byte outside [out_off, out_off + min(out_len, out_cap)) -- the bytes around it are other waves'.
+//
+// WIN < 32768 (the small-ring instantiation, for members whose output is short and lies in global memory anyway): a match source
+// that the ring no longer holds is read back from the result, through the pointer the flush stores through.  The ring holds
+// position s intact until position s + WIN is written, so a source byte s of a match [op, op + len) comes from the ring iff
+// s + WIN >= op + len and from the result otherwise; the flush keeps op - flushed < INF_FLUSH between symbols, hence
+// op + len - flushed <= INF_FLUSH + 258 <= WIN and every byte not served by the ring lies below `flushed`.
+template <u32 WIN>
 __global__ void __launch_bounds__(64)
-k_inflate_streams(const unsigned char *__restrict__ comp, const u64 *__restrict__ in_off, const u32 *__restrict__ in_len,
-                  unsigned char *__restrict__ out, const u64 *__restrict__ out_off, const u32 *__restrict__ out_cap, u32 n_streams,
-                  u32 *__restrict__ out_len, u32 *__restrict__ consumed, u32 *__restrict__ status) {
-    __shared__ InfLds L;
+k_inflate(const unsigned char *__restrict__ comp, const u64 *__restrict__ in_off, const u32 *__restrict__ in_len, unsigned char *out,
+          const u64 *__restrict__ out_off, const u32 *__restrict__ out_cap, u32 n_streams, u32 *__restrict__ out_len,
+          u32 *__restrict__ consumed, u32 *__restrict__ status) {
+    static_assert((WIN & (WIN - 1u)) == 0 && WIN <= INF_WIN && WIN >= INF_FLUSH + 258u + 16u, "ring size");
+    constexpr u32 INF_WIN_MASK = WIN - 1u;
+    __shared__ InfLds<WIN> L;
     const int lane = threadIdx.x;
     for (u32 sid = blockIdx.x; sid < n_streams; sid += gridDim.x) {
         BitReader r;
-        r.src = comp + in_off[sid];
-        r.n = in_len[sid];
-        r.bb = 0, r.bn = 0, r.ip = 0, r.staged = 0;
+        const u64 in0 = in_off[sid];
+        const u32 imis = (u32)(in0 & 15u);
+        r.src = comp + (in0 - imis);
+        r.n = imis + in_len[sid];
+        r.bb = 0, r.bn = 0, r.ip = imis, r.staged = 0;
         r.pre = inf_fetch(r, 0, lane);
         inf_request(L, r, lane);
-        unsigned char *dst = out + out_off[sid];
-        const u32 cap = out_cap[sid];
-        u32 op = 0, flushed = 0, st = 0;
+        const uintptr_t dst0 = (uintptr_t)out + out_off[sid];
+        const u32 omis = (u32)(dst0 & 15u);
+        unsigned char *dst = out + out_off[sid] - omis;  // (never dereferenced below dst + omis)
+        const u32 cap = omis + out_cap[sid];
+        u32 op = omis, flushed = omis, st = 0;
 #if INF_STATS
         u64 is_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const u64 is_t0 = INF_CLOCK();
 #endif
-        auto flush = [&](u32 upto) {  // whole 4-KiB pieces of the ring to the result
-            while (flushed + INF_FLUSH <= upto) {
-#pragma unroll
-                for (u32 k = 0; k < INF_FLUSH / 1024u; ++k) {
-                    const u32 o = flushed + k * 1024u + (u32)lane * 16u;
+        auto flush_to = [&](u32 upto) {  // the ring's positions [flushed, upto) to the result: 16 bytes per lane where they are whole
+            if (upto <= flushed) return;
+            for (u32 u0 = flushed & ~15u; u0 < upto; u0 += 1024u) {
+                const u32 o = u0 + (u32)lane * 16u;
+                if (o >= flushed && o + 16u <= upto) {
                     *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(L.win + (o & INF_WIN_MASK));
+                } else {
+                    const u32 hi = min(o + 16u, upto);
+                    for (u32 b = max(o, flushed); b < hi; ++b) dst[b] = L.win[b & INF_WIN_MASK];
                 }
-                flushed += INF_FLUSH;
             }
+            flushed = upto;
+            // (small ring: lanes read back what other lanes of this wave stored -- the stores have left the wave before it goes on)
+            if constexpr (WIN < INF_WIN) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         };
+        auto flush = [&](u32 upto) { flush_to(upto & ~(INF_FLUSH - 1u)); };  // whole 4-KiB pieces (upto has just crossed a boundary)
         bool last = false;
         while (!last && !st) {
             [[maybe_unused]] const u64 is_tb = INF_CLOCK();
@@ -475,7 +509,7 @@ k_inflate_streams(const unsigned char *__restrict__ comp, const u64 *__restrict_
                 const u32 dist = (d >> 16) + ((u32)r.bb & ((1u << dxb) - 1u));
                 r.bb >>= dxb;
                 r.bn -= dxb;
-                if (__builtin_expect((d & IE_BAD) != 0u || dist > op, 0)) {
+                if (__builtin_expect((d & IE_BAD) != 0u || dist > op - omis, 0)) {
                     st = 3;
                     break;
                 }
@@ -484,7 +518,13 @@ k_inflate_streams(const unsigned char *__restrict__ comp, const u64 *__restrict_
                 const u32 from = op - dist;
                 INF_COUNT(1, 1);
                 INF_COUNT(6, len);
-                if (__builtin_expect(dist >= len, 1)) {
+                if (WIN < INF_WIN && __builtin_expect(dist + len > WIN, 0)) {
+                    // (small ring, a far source: the bytes the ring has given up come from the result; dist > len here)
+                    for (u32 i0 = 0; i0 < len; i0 += 64) {
+                        const u32 i = i0 + (u32)lane, s = from + i;
+                        if (i < len) L.win[(op + i) & INF_WIN_MASK] = s + WIN >= op + len ? L.win[s & INF_WIN_MASK] : dst[s];
+                    }
+                } else if (__builtin_expect(dist >= len, 1)) {
                     for (u32 i0 = 0; i0 < len; i0 += 64) {
                         const u32 i = i0 + (u32)lane;
                         if (i < len) L.win[(op + i) & INF_WIN_MASK] = L.win[(from + i) & INF_WIN_MASK];
@@ -516,33 +556,54 @@ k_inflate_streams(const unsigned char *__restrict__ comp, const u64 *__restrict_
             INF_COUNT(4, INF_CLOCK() - is_ts);
             if (r.ip - (r.bn >> 3) > r.n) st = st ? st : 4;
         }
-        // the rest of the output, byte by byte
+        // the rest of the output
         if (!st && op > cap) st = 5;
-        if (!st)
-            for (u32 o = flushed + (u32)lane; o < op; o += 64) dst[o] = L.win[o & INF_WIN_MASK];
+        if (!st) flush_to(op);
 #if INF_STATS
         is_acc[5] = INF_CLOCK() - is_t0;
         if (lane == 0)
             for (int k = 0; k < 8; ++k) atomicAdd(&g_inf_stats[k], is_acc[k]);
 #endif
         if (lane == 0) {
-            out_len[sid] = op;
-            consumed[sid] = r.ip - (r.bn >> 3);
+            out_len[sid] = op - omis;
+            consumed[sid] = r.ip - (r.bn >> 3) - imis;
             status[sid] = st;
         }
     }
 }
 
-gtars_status launch_inflate_streams(const unsigned char *comp, const u64 *in_off, const u32 *in_len, unsigned char *out, const u64 *out_off,
-                                    const u32 *out_cap, u32 n_streams, u32 *out_len, u32 *consumed, u32 *status, hipStream_t st) {
-    if (!n_streams) return GTARS_OK;
+namespace {
+template <u32 WIN>
+gtars_status launch_inflate(const unsigned char *comp, const u64 *in_off, const u32 *in_len, unsigned char *out, const u64 *out_off,
+                            const u32 *out_cap, u32 n_streams, u32 *out_len, u32 *consumed, u32 *status, hipStream_t st) {
+    // as many waves as the LDS lets a CU hold (one wave per workgroup), each taking streams in strides
+    static const int per_cu = [] {
+        int n = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate<WIN>, 64, 0) == hipSuccess && n > 0 ? n : 4;
+    }();
     int dev = 0, cus = 256;
     GT_HIP(hipGetDevice(&dev));
     GT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const u32 grid = std::min<u32>(n_streams, (u32)cus * 4u);
-    hipLaunchKernelGGL(k_inflate_streams, dim3(grid), dim3(64), 0, st, comp, in_off, in_len, out, out_off, out_cap, n_streams, out_len, consumed, status);
+    const u32 grid = std::min<u32>(n_streams, (u32)cus * (u32)per_cu);
+    hipLaunchKernelGGL(k_inflate<WIN>, dim3(grid), dim3(64), 0, st, comp, in_off, in_len, out, out_off, out_cap, n_streams, out_len, consumed, status);
     GT_HIP(hipGetLastError());
     return GTARS_OK;
+}
+}  // namespace
+
+// ring_kib: 32 (every match source in LDS) | 8 (a third of the LDS per wave; far sources from the result).  The work list is
+// generic: stream k is comp[in_off[k], + in_len[k]) and goes to out[out_off[k], + out_cap[k]) at most, any byte offsets.
+gtars_status launch_inflate_members(const unsigned char *comp, const u64 *in_off, const u32 *in_len, unsigned char *out, const u64 *out_off,
+                                    const u32 *out_cap, u32 n_streams, u32 *out_len, u32 *consumed, u32 *status, u32 ring_kib, hipStream_t st) {
+    if (ring_kib != 8 && ring_kib != 32) return fail(GTARS_ERR_INVALID_ARG, "device inflate: the ring is 8 or 32 KiB");
+    if (!n_streams) return GTARS_OK;
+    if (((uintptr_t)comp & 15u) != 0) return fail(GTARS_ERR_INVALID_ARG, "device inflate: the compressed buffer must be 16-byte aligned");
+    return ring_kib == 8 ? launch_inflate<8192>(comp, in_off, in_len, out, out_off, out_cap, n_streams, out_len, consumed, status, st)
+                         : launch_inflate<INF_WIN>(comp, in_off, in_len, out, out_off, out_cap, n_streams, out_len, consumed, status, st);
+}
+gtars_status launch_inflate_streams(const unsigned char *comp, const u64 *in_off, const u32 *in_len, unsigned char *out, const u64 *out_off,
+                                    const u32 *out_cap, u32 n_streams, u32 *out_len, u32 *consumed, u32 *status, hipStream_t st) {
+    return launch_inflate_members(comp, in_off, in_len, out, out_off, out_cap, n_streams, out_len, consumed, status, 32, st);
 }
 
 }  // namespace gtars
@@ -563,4 +624,13 @@ extern "C" int gtars_debug_inflate_streams(const void *comp, const uint64_t *in_
                                            void *stream) {
     return (int)gtars::launch_inflate_streams((const unsigned char *)comp, (const gtars::u64 *)in_off, in_len, (unsigned char *)out,
                                               (const gtars::u64 *)out_off, out_cap, n_streams, out_len, consumed, status, (hipStream_t)stream);
+}
+// ... streams at any byte offset of `comp` (16-byte aligned, readable for 48 bytes behind every stream) into any byte offset of
+// `out`; ring_kib 8 | 32
+extern "C" int gtars_debug_inflate_members(const void *comp, const uint64_t *in_off, const uint32_t *in_len, void *out, const uint64_t *out_off,
+                                           const uint32_t *out_cap, uint32_t n_streams, uint32_t *out_len, uint32_t *consumed, uint32_t *status,
+                                           uint32_t ring_kib, void *stream) {
+    return (int)gtars::launch_inflate_members((const unsigned char *)comp, (const gtars::u64 *)in_off, in_len, (unsigned char *)out,
+                                              (const gtars::u64 *)out_off, out_cap, n_streams, out_len, consumed, status, ring_kib,
+                                              (hipStream_t)stream);
 }

@@ -47,6 +47,13 @@ uint64_t gtars_debug_seq_stage_blocks(void);
 int gtars_debug_inflate_streams(const void *comp, const uint64_t *in_off, const uint32_t *in_len, void *out, const uint64_t *out_off,
                                 const uint32_t *out_cap, uint32_t n_streams, uint32_t *out_len, uint32_t *consumed, uint32_t *status,
                                 void *stream);
+/* The same decoder as the fused fragment pipeline launches it on the members of BGZF files (GTARS_FRAG_INFLATE=device): in_off and
+ * out_off are ANY byte offsets -- the streams and their outputs may lie back to back --, comp is 16-byte aligned and readable for
+ * 48 bytes behind the end of every stream, and no byte of out outside [out_off[i], out_off[i] + min(out_len[i], out_cap[i])) is
+ * written.  ring_kib: 32 -- the whole window in LDS -- or 8 -- a match source the ring no longer holds is read back from out. */
+int gtars_debug_inflate_members(const void *comp, const uint64_t *in_off, const uint32_t *in_len, void *out, const uint64_t *out_off,
+                                const uint32_t *out_cap, uint32_t n_streams, uint32_t *out_len, uint32_t *consumed, uint32_t *status,
+                                uint32_t ring_kib, void *stream);
 
 /* Test entries of the three device primitives under every index build and set operation (tests/test_gpu_primitives.py).  All
  * pointers are HOST memory; the calls run on the current device's null stream and return when the result is in the caller's

@@ -671,6 +671,20 @@ gtars_status gtars_fragsplit_tokenize_files(const gtars_tokenizer_t *t, const ch
  * regroup by barcode, then for the device waves: text to the device, line split + parse + sort by cluster, gather, tokenize,
  * results to the host }. */
 void gtars_fragsplit_last_stages(double *out12);
+/* ... and what the device inflate of that call did (GTARS_FRAG_INFLATE=device; zeros otherwise): out4 = { BGZF members inflated
+ * on the device, files handed back to the host's decoders, compressed bytes copied to the device, seconds in the member kernel by
+ * the device's clock (measured only under GTARS_HOST_TIMING) }. */
+void gtars_fragsplit_last_inflate(double *out4);
+
+/* The member table of a BGZF file held in memory (data[0, n)), nothing inflated: what the fragment pipeline hands to the device
+ * under GTARS_FRAG_INFLATE=device.  GTARS_ERR_PARSE (no message: it is an answer, not a failure) unless every member is a BGZF
+ * block -- a gzip member with FEXTRA alone and a "BC" subfield of length 2 -- and BSIZE + 1 leads from member to member to
+ * exactly the end of the data; such a file takes the ordinary gzip reader.  *n_members: the members; of the first `cap`, the
+ * offset and length of the raw deflate stream in the data, ISIZE and CRC-32 of the trailer and the prefix sum of ISIZE (any of
+ * the arrays may be NULL).  *last_byte (may be NULL): the last byte of the inflated data, found by inflating the last
+ * non-empty member on the host; -1 when every member is empty, -2 when the host decoder refuses that member. */
+gtars_status gtars_bgzf_members(const void *data, uint64_t n, uint64_t cap, uint64_t *n_members, uint64_t *stream_off,
+                                uint32_t *stream_len, uint32_t *isize, uint32_t *crc, uint64_t *uoff, int32_t *last_byte);
 
 /* Host threads one call of the file pipelines above starts at most: hardware threads, capped by the container's CPU quota
  * (cgroup v2 cpu.max) and by `cap`, divided by LOCAL_WORLD_SIZE when the process is one of several ranks of a launcher on this
