@@ -122,6 +122,7 @@ _SIG = {
     "gtars_refget_digests_device": (C.c_int, [vp, vp, vp, vp, vp]),
     "gtars_refget_substrings_device": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp, u64, pu64, vp]),
     "gtars_refget_packed_substrings_device": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, vp, u64, pu64, vp]),
+    "gtars_bed_digests_device": (C.c_int, [vp, u64, vp, vp, vp, vp, vp, u32, vp, vp, vp, C.c_int, vp, vp]),
     "gtars_prof_enable": (None, [C.c_int]),
     "gtars_prof_reset": (None, []),
     "gtars_prof_read": (C.c_int, [vp, vp, vp, C.c_int]),
@@ -171,6 +172,13 @@ _HOST_SIG = {
     "gtars_regionset_list_intersect_all": (C.c_int, [vp, u64, pp]),
     "gtars_regionset_list_union_except": (C.c_int, [vp, u64, u64, pp]),
     "gtars_regionset_list_bulk_union_except": (C.c_int, [vp, u64, pp, pp]),
+    "gtars_regionset_identifier": (C.c_int, [vp, vp]),
+    "gtars_regionset_file_digest": (C.c_int, [vp, vp]),
+    "gtars_regionset_bed_text": (C.c_int, [vp, C.c_int, pp, pu64]),
+    "gtars_regionset_write_bed": (C.c_int, [vp, cstr, C.c_int]),
+    "gtars_regionset_sort": (C.c_int, [vp]),
+    "gtars_regionset_list_digests": (C.c_int, [vp, u64, C.c_int, C.c_int, u32, vp]),
+    "gtars_regionset_list_identifier": (C.c_int, [vp, u64, C.c_int, u32, vp]),
     "gtars_regionset_disjoin": (C.c_int, [vp, pp]),
     "gtars_regionset_gaps": (C.c_int, [vp, vp, vp, u64, pp]),
     "gtars_regionset_consensus": (C.c_int, [vp, u64, pp, pp]),

@@ -667,6 +667,26 @@ std::vector<uint32_t> translate_chroms(const gtars_regionset *q, const Dict &d) 
     return out;
 }
 
+// the permutation that stably orders rows by (rank, start), rank < n_ranks: an LSD radix sort of the row indices -- start
+// (two 16-bit passes), then the rank.  RegionSet::sort (region_set.rs:502-505) with rank = the name's place in byte order.
+std::vector<uint32_t> rank_start_order(const std::vector<uint32_t> &rank, const std::vector<uint32_t> &start, size_t n_ranks) {
+    const size_t n = rank.size();
+    std::vector<uint32_t> perm(n), tmp(n);
+    std::iota(perm.begin(), perm.end(), 0u);
+    std::vector<size_t> cnt;
+    auto pass = [&](auto key_of, size_t n_keys) {
+        cnt.assign(n_keys + 1, 0);
+        for (size_t i = 0; i < n; ++i) ++cnt[(size_t)key_of(perm[i]) + 1];
+        for (size_t k = 0; k < n_keys; ++k) cnt[k + 1] += cnt[k];
+        for (size_t i = 0; i < n; ++i) tmp[cnt[key_of(perm[i])]++] = perm[i];
+        perm.swap(tmp);
+    };
+    pass([&](uint32_t i) { return start[i] & 0xFFFFu; }, 1u << 16);
+    pass([&](uint32_t i) { return start[i] >> 16; }, 1u << 16);
+    pass([&](uint32_t i) { return rank[i]; }, n_ranks);
+    return perm;
+}
+
 }  // namespace
 
 extern "C" uint32_t gtars_host_threads(uint32_t cap) { return host_thread_budget(cap ? cap : 0xFFFFFFFFu); }
@@ -797,22 +817,7 @@ static gtars_status gtars_regionset_from_bed_impl(const char *path, gtars_region
             }
         }
     }
-    // stable LSD radix sort of the row indices: start (two 16-bit passes), then chromosome rank
-    std::vector<uint32_t> perm(n), tmp(n);
-    std::iota(perm.begin(), perm.end(), 0u);
-    {
-        std::vector<size_t> cnt;
-        auto pass = [&](auto key_of, size_t n_keys) {
-            cnt.assign(n_keys + 1, 0);
-            for (size_t i = 0; i < n; ++i) ++cnt[(size_t)key_of(perm[i]) + 1];
-            for (size_t k = 0; k < n_keys; ++k) cnt[k + 1] += cnt[k];
-            for (size_t i = 0; i < n; ++i) tmp[cnt[key_of(perm[i])]++] = perm[i];
-            perm.swap(tmp);
-        };
-        pass([&](uint32_t i) { return col_s[i] & 0xFFFFu; }, 1u << 16);
-        pass([&](uint32_t i) { return col_s[i] >> 16; }, 1u << 16);
-        pass([&](uint32_t i) { return col_c[i]; }, n_names);
-    }
+    const std::vector<uint32_t> perm = rank_start_order(col_c, col_s, n_names);
     auto *rs = new gtars_regionset();
     for (uint32_t r = 0; r < n_names; ++r) rs->chroms.get_or_add(all.names[by_name[r]]);  // id = rank
     rs->chrom_ids.resize(n); rs->starts.resize(n); rs->ends.resize(n); rs->rest_off.assign(n, 0); rs->has_rest.resize(n);
@@ -871,6 +876,28 @@ const uint32_t *gtars_regionset_starts(const gtars_regionset_t *rs) { return rs 
 const uint32_t *gtars_regionset_ends(const gtars_regionset_t *rs) { return rs ? rs->ends.data() : nullptr; }
 const char *gtars_regionset_rest(const gtars_regionset_t *rs, uint64_t i) {
     return rs && i < rs->size() && rs->has_rest[i] ? rs->rest_arena.data() + rs->rest_off[i] : nullptr;
+}
+
+// RegionSet::sort (region_set.rs:502-505): stable by (chr bytewise, start), in place -- the order the file loader produces.
+// The rest column moves with its rows (the arena stays, the offsets move); the dictionary keeps its ids.
+gtars_status gtars_regionset_sort(gtars_regionset_t *rs) {
+    return gtars::guarded([&]() -> gtars_status {
+        if (!rs) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
+        const size_t n = rs->size(), n_names = rs->chroms.names.size();
+        std::vector<uint32_t> by_name(n_names), rank_of(n_names), rank(n);
+        std::iota(by_name.begin(), by_name.end(), 0u);
+        std::sort(by_name.begin(), by_name.end(), [&](uint32_t a, uint32_t b) { return rs->chroms.names[a] < rs->chroms.names[b]; });
+        for (uint32_t r = 0; r < n_names; ++r) rank_of[by_name[r]] = r;
+        for (size_t i = 0; i < n; ++i) rank[i] = rank_of[rs->chrom_ids[i]];
+        const std::vector<uint32_t> perm = rank_start_order(rank, rs->starts, n_names);
+        auto permuted = [&](auto &col) {
+            auto moved = col;
+            for (size_t i = 0; i < n; ++i) moved[i] = col[perm[i]];
+            col.swap(moved);
+        };
+        permuted(rs->chrom_ids), permuted(rs->starts), permuted(rs->ends), permuted(rs->rest_off), permuted(rs->has_rest);
+        return GTARS_OK;
+    });
 }
 
 // generate_region_to_id_map (gtars-core/src/utils.rs:202-214): dense ids in first-seen order over the whole Region

@@ -164,6 +164,42 @@ GT_MD5_HD void md5_stream(Md5 &s, Src &src, uint64_t len) {
     }
 }
 
+// The same for a source that yields eight message bytes per call: `uint64_t pair(uint64_t c)` gives bytes [8 c, 8 c + 8),
+// the first in the low byte; it is asked for c = 0, 1, ... in order and only while 8 c < len, and whatever it holds behind
+// len is dropped here.  A block's eight pairs go straight to their places (constant indices: the block stays in registers).
+// md5_tail_pairs goes on from a state that has taken in the first `first_block` blocks, all of them inside the message
+// (64 * first_block <= len): the source is asked from pair 8 * first_block on.
+template <class Src>
+GT_MD5_HD void md5_tail_pairs(Md5 &s, Src &src, uint64_t len, uint64_t first_block) {
+    const uint64_t n_blocks = md5_blocks(len);
+#if defined(__clang__)
+#pragma unroll 1
+#endif
+    for (uint64_t blk = first_block; blk < n_blocks; ++blk) {
+#if defined(__clang__)
+#pragma unroll
+#endif
+        for (int i = 0; i < 8; ++i) {
+            const uint64_t c = (blk << 3) + (uint64_t)i, at = c << 3;
+            uint64_t d = 0;
+            if (at < len) {
+                d = src.pair(c);
+                const uint64_t rem = len - at;
+                if (rem < 8) d = (d & ((1ull << (8 * rem)) - 1)) | (0x80ull << (8 * rem));
+            } else if (at == len) {
+                d = 0x80;
+            }
+            s.m[i] = md5_padded_pair(d, c, len);
+        }
+        md5_block(s);
+    }
+}
+template <class Src>
+GT_MD5_HD void md5_stream_pairs(Md5 &s, Src &src, uint64_t len) {
+    md5_init(s);
+    md5_tail_pairs(s, src, len, 0);
+}
+
 // the 16 digest bytes of a finished state
 GT_MD5_HD void md5_bytes(const Md5 &s, uint8_t out[16]) {
 #if defined(__clang__)

@@ -20,6 +20,12 @@ The structural operations and statistics of region_set.rs:288-531 are here too: 
 ``widths`` / ``region_widths``, ``mean_region_width`` and ``get_max_end_per_chr`` are elementwise host arithmetic.
 ``gaps`` pins the order the reference leaves open among names that share a karyotype key (start, then name bytewise).
 
+What names a set and writes it back out is here as well (region_set.rs:240-330, region_set_list.rs:85-98; csrc/bed_text.cpp
+and bed_text.hip, K25): ``RegionSet.identifier`` (the BEDbase bed digest, cached), ``file_digest``, ``to_bed``, ``to_bed_gz``
+and ``sort``, ``RegionSetList.identifier()`` and the additive batch calls ``RegionSetList.identifiers()`` / ``file_digests()``.
+One set is three sequential MD5 streams and stays on the host threads; a list hashes every stream of every set as one lane
+of a device kernel (``on_host=True`` keeps it on the host), and ``to_bed`` formats large sets on the device.
+
 The annotation side of the reference's ``gtars.models`` (gtars-python/src/models/{tss_index,gene_model,gda}.rs) is here
 too: ``TssIndex`` (distances to the nearest TSS / feature midpoint on the GPU, csrc/annot.hip, K10), ``GeneModel`` and
 ``GenomicDistAnnotation`` (a GTF read by host threads; genes, exons and the two UTR sets each merged by a strand-aware
@@ -196,6 +202,56 @@ class RegionSet:
 
     def __repr__(self) -> str:
         return f"RegionSet with {len(self)} regions."
+
+    # -- what names the set and writes it back out (gtars-python/src/models/region_set.rs:136-200; csrc/bed_text.cpp, K25) --
+    # Rows are taken in the set's order: a set read from a file is sorted by (chr, start), one built from regions or
+    # vectors is not until sort() is called.  One set is three sequential MD5 streams: these run on the host threads.
+    def _digest(self, fn) -> str:
+        out = C.create_string_buffer(33)
+        check(fn(self._h, out))
+        return out.value.decode()
+
+    @property
+    def identifier(self) -> str:
+        """the BEDbase bed digest: md5 of "c,s,e" over the md5s of the joined chromosome names, starts and ends (cached)"""
+        if getattr(self, "_identifier", None) is None:
+            self._identifier = self._digest(lib.gtars_regionset_identifier)
+        return self._identifier
+
+    @property
+    def file_digest(self) -> str:
+        """md5 of the BED text ``to_bed`` writes"""
+        return self._digest(lib.gtars_regionset_file_digest)
+
+    def to_bed(self, path) -> None:
+        """one line per region, rest included; parent directories are created, an existing file is replaced.  The text is
+        formatted on the host threads; GTARS_BED_TEXT_DEVICE_ROWS names the rows from which the GPU formats it instead
+        (unset: never -- with its upload and download the device path measured no faster up to 1e7 rows)."""
+        check(lib.gtars_regionset_write_bed(self._h, os.fspath(path).encode(), 0))
+
+    def to_bed_gz(self, path) -> None:
+        """the bytes of ``to_bed`` as one gzip member at the best compression level"""
+        check(lib.gtars_regionset_write_bed(self._h, os.fspath(path).encode(), 1))
+
+    def _bed_text(self, on_host: bool) -> bytes:
+        """the BED text, formatted on the host threads or on the device"""
+        p, n = C.c_void_p(), C.c_uint64()
+        check(lib.gtars_regionset_bed_text(self._h, int(bool(on_host)), C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            lib.gtars_free(p)
+
+    def sort(self) -> None:
+        """stable, in place, by (chr bytewise, start): the order of a set read from a file; rest and strands move with
+        their rows"""
+        if self._strands is not None and len(self):
+            names = [nm.encode() for nm in self.chrom_names]
+            rank = np.argsort(np.argsort(np.array(names, dtype=object), kind="stable"), kind="stable")
+            order = np.lexsort((self.starts, rank[self.chrom_ids]))
+            self._strands = [self._strands[i] for i in order]
+        check(lib.gtars_regionset_sort(self._h))
+        self._identifier = None
 
     # -- overlap operations (gtars-python/src/models/region_set.rs:445-478) ---------
     def count_overlaps(self, other: "RegionSet") -> List[int]:
@@ -481,6 +537,29 @@ class RegionSetList:
 
     def names(self) -> Optional[List[str]]:
         return None
+
+    # -- digests (region_set_list.rs:85-98; csrc/bed_text.hip, K25) ------------------------------------------------
+    # A list is the device's case: every stream of every set -- names, starts, ends, or the BED text -- is one lane of
+    # k_bed_md5.  on_host=True runs the same text on `threads` host threads (0: all of them).
+    def _digests(self, what: int, on_host: bool, threads: int) -> List[str]:
+        n = len(self._sets)
+        out = C.create_string_buffer(32 * n + 1)
+        check(lib.gtars_regionset_list_digests(self._handles(), n, what, int(bool(on_host)), _u32(threads, "threads"), out))
+        return [out.raw[32 * i:32 * i + 32].decode() for i in range(n)]
+
+    def identifiers(self, on_host: bool = False, threads: int = 0) -> List[str]:
+        """every member's ``identifier``, in list order"""
+        return self._digests(0, on_host, threads)
+
+    def file_digests(self, on_host: bool = False, threads: int = 0) -> List[str]:
+        """every member's ``file_digest``, in list order"""
+        return self._digests(1, on_host, threads)
+
+    def identifier(self, on_host: bool = False, threads: int = 0) -> str:
+        """md5 of the members' identifiers, sorted as strings and concatenated"""
+        out = C.create_string_buffer(33)
+        check(lib.gtars_regionset_list_identifier(self._handles(), len(self._sets), int(bool(on_host)), _u32(threads, "threads"), out))
+        return out.value.decode()
 
     def pairwise_jaccard(self) -> List[List[float]]:
         """N x N: M[i][j] = reduce(S_i).jaccard(reduce(S_j)), 1.0 on the diagonal; all pairs in one device pass"""

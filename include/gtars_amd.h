@@ -420,6 +420,27 @@ gtars_status gtars_refget_packed_substrings_device(gtars_seqpack_t *p, const uin
                                                    void *stream);
 
 /* ------------------------------------------------------------------------
+ * K25 (csrc/bed_text.hip): the bed digest ("identifier") or the file digest of
+ * every set of a batch, on columns that are resident on the device.
+ * Set b = the rows [set_off[b], set_off[b + 1]) of the concatenated columns;
+ * set_off is a HOST array of n_sets + 1 offsets that starts at 0 and never
+ * descends.  d_chrom[i] indexes ONE names table, a byte CSR: name c =
+ * d_names[d_name_off[c] .. d_name_off[c + 1]); an id outside it is
+ * GTARS_ERR_INVALID_ARG.  GTARS_BED_FILE_DIGEST also reads the rest column:
+ * row i carries d_rest[d_rest_off[i] .. d_rest_off[i + 1]) where d_has_rest[i]
+ * (d_rest_off: rows + 1 ascending offsets); the three may be NULL for
+ * GTARS_BED_IDENTIFIER.  d_digests: 16 digest bytes per set, 8-byte aligned.
+ * The text of a set is csrc/bed_text_core.h's; the stream is drained.
+ * ---------------------------------------------------------------------- */
+#define GTARS_BED_IDENTIFIER 0
+#define GTARS_BED_FILE_DIGEST 1
+gtars_status gtars_bed_digests_device(const uint64_t *set_off, uint64_t n_sets, const uint32_t *d_chrom,
+                                      const uint32_t *d_start, const uint32_t *d_end,
+                                      const uint64_t *d_name_off, const uint8_t *d_names, uint32_t n_names,
+                                      const uint64_t *d_rest_off, const uint8_t *d_rest,
+                                      const uint8_t *d_has_rest, int what, uint8_t *d_digests, void *stream);
+
+/* ------------------------------------------------------------------------
  * Instrumentation used by bench.py: when enabled every kernel launch made by
  * this library on the calling thread is bracketed by HIP events on its own
  * stream; gtars_prof_read() synchronises and returns accumulated times.

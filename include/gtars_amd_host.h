@@ -120,6 +120,31 @@ gtars_status gtars_regionset_list_bulk_union_except(const gtars_regionset_t *con
                                                     gtars_regionset_t **out_union, gtars_regionset_t ***out_except);
 
 /* ------------------------------------------------------------------------
+ * K25: what names a set and writes it back out (gtars-core/src/models/region_set.rs:240-330, 502-505,
+ * region_set_list.rs:85-98; csrc/bed_text_core.h states the text once for the host paths and the kernels).  Rows are in
+ * the handle's order; nothing but the sort entry sorts.
+ * identifier: the bed digest -- md5 of "c,s,e", c / s / e = md5 of the chromosome names / decimal starts / decimal
+ * ends joined by ','.  file_digest: md5 of the lines chr \t start \t end [\t rest] \n.  out33: 32 lower-case hex
+ * characters and a NUL.  The single-set entries run on the host threads.
+ * bed_text: those lines as one malloc'ed block (*out, gtars_free; *len bytes and a NUL), formatted on the host threads
+ * (on_host) or on the device.  write_bed: the lines to `path` (parent directories are created, an existing file is
+ * replaced), as they are or (gz) as one gzip member at the best compression level; formatted on the device from
+ * GTARS_BED_TEXT_DEVICE_ROWS rows up (unset: on the host threads whatever the size).
+ * sort: stable, in place, by (chr bytewise, start) -- the order the file loader produces; rest moves with its rows.
+ * list_digests: out[32 * i ..] = the identifier (what = GTARS_BED_IDENTIFIER) or file digest (GTARS_BED_FILE_DIGEST) of
+ * set i, not terminated; list_identifier: the member identifiers sorted as strings, concatenated, hashed.  Both run on the
+ * device -- every stream of every set one lane of k_bed_md5 -- or (on_host) on `threads` host threads (0: all). */
+gtars_status gtars_regionset_identifier(const gtars_regionset_t *rs, char *out33);
+gtars_status gtars_regionset_file_digest(const gtars_regionset_t *rs, char *out33);
+gtars_status gtars_regionset_bed_text(const gtars_regionset_t *rs, int on_host, char **out, uint64_t *len);
+gtars_status gtars_regionset_write_bed(const gtars_regionset_t *rs, const char *path, int gz);
+gtars_status gtars_regionset_sort(gtars_regionset_t *rs);
+gtars_status gtars_regionset_list_digests(const gtars_regionset_t *const *sets, uint64_t n, int what, int on_host,
+                                          uint32_t threads, char *out);
+gtars_status gtars_regionset_list_identifier(const gtars_regionset_t *const *sets, uint64_t n, int on_host,
+                                             uint32_t threads, char *out33);
+
+/* ------------------------------------------------------------------------
  * Structural operations and region-set statistics (gtars-core region_set.rs,
  * gtars-genomicdist/src/{consensus,statistics}.rs; gtars-python/src/models/
  * region_set.rs:288-531, genomic_distributions/tools.rs:157-190), on the
