@@ -13,7 +13,8 @@ reference exposes those crates through Rust / the CLI only).  ``gtars.seqstats``
 ``gtars.models`` and ``gtars.genomic_distributions``; ``gtars.signal`` likewise holds ``SignalMatrix`` and
 ``calc_summary_signal``, and ``gtars.partitions`` holds ``PartitionList``, ``calc_partitions`` and ``calc_expected_partitions``.
 ``gtars.bam`` holds ``BamFile``, ``read_bam_header`` and the BAM QC of ``gtars uniwig bamqc`` (``compute_bam_qc``, ``run_bam_qc``,
-``write_bam_qc_tsv``).  ``gtars.vrs`` holds the reference's four functions (``vrs_digest``, ``vrs_id``, ``normalize_allele``,
+``write_bam_qc_tsv``) and, this library's own, ``BamFile.fragments`` / ``bam_to_fragments``.
+``gtars.vrs`` holds the reference's four functions (``vrs_digest``, ``vrs_id``, ``normalize_allele``,
 ``location_digest``) and the batch calls on top of the device kernels (``normalize_alleles``, ``vrs_ids``, ``compute_vrs_ids``);
 its ``hgvs`` sub-module (``gtars.vrs.hgvs``, also ``gtars.hgvs``) holds the reference's HGVS parser classes, ``parse_hgvs``,
 ``HgvsError`` and ``hgvs_to_vrs_id`` over an assembly and a transcript store, and, additive, the batch bridge on the device

@@ -350,6 +350,20 @@ _HOST_SIG = {
     "gtars_bam_decode": (C.c_int, [vp, u64, u64, u64, u32, pp, pu64]),
     "gtars_bam_qc": (C.c_int, [vp, u64, u32, vp]),
     "gtars_bam_last_stages": (None, [vp]),
+    "gtars_bam_frag_params_default": (None, [vp]),
+    "gtars_bam_fragments": (C.c_int, [vp, vp, u64, u32, pp]),
+    "gtars_bam_frags_len": (u64, [vp]),
+    "gtars_bam_frags_ref": (vp, [vp]),
+    "gtars_bam_frags_start": (vp, [vp]),
+    "gtars_bam_frags_end": (vp, [vp]),
+    "gtars_bam_frags_barcode": (vp, [vp]),
+    "gtars_bam_frags_count": (vp, [vp]),
+    "gtars_bam_frags_n_barcodes": (u64, [vp]),
+    "gtars_bam_frags_barcode_name": (vp, [vp, u64, pu64]),
+    "gtars_bam_frags_stats": (None, [vp, vp]),
+    "gtars_bam_frags_write": (C.c_int, [vp, vp, cstr]),
+    "gtars_bam_frags_free": (None, [vp]),
+    "gtars_fragments_write_text": (C.c_int, [cstr, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64]),
     "gtars_sha512t24u": (C.c_int, [vp, u64, vp]),
     "gtars_vrs_location_digest": (C.c_int, [cstr, u64, u64, vp]),
     "gtars_vrs_allele_digest": (C.c_int, [cstr, u64, u64, vp, u64, vp]),

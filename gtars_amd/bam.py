@@ -3,8 +3,10 @@
 ``BamFile`` opens a coordinate-sorted BAM through the library's own BGZF reader: the block table, the header, the
 inflated bytes (host threads) and the records' columns (decoded on the device).  ``compute_bam_qc`` is the reference's
 library-complexity QC -- NRF, PBC1, PBC2, duplicate and mitochondrial rate -- computed on the device from the decoded
-records; ``run_bam_qc`` / ``write_bam_qc_tsv`` write the reference's TSV.  No ``.bai`` is needed or read.  Without a
-device the calls that decode records raise NoDeviceError: there is no host fallback.
+records; ``run_bam_qc`` / ``write_bam_qc_tsv`` write the reference's TSV.  ``BamFile.fragments`` / ``bam_to_fragments`` (K26,
+this library's own) turn a paired-end BAM into the deduplicated fragments of a 10x-style fragment file -- filters, barcode tag,
+Tn5 shift, sort and dedup on the device.  No ``.bai`` is needed or read.  Without a device the calls that decode records
+raise NoDeviceError: there is no host fallback.
 """
 from __future__ import annotations
 
@@ -137,6 +139,21 @@ class BamFile:
         check(lib.gtars_bam_qc(self._h, max_window_bytes or 0, threads, C.byref(r)))
         return BamQcResult(*(getattr(r, k) for k, _ in _QcResult._fields_))
 
+    def fragments(self, barcode_tag: Optional[str] = "CB", min_mapq: int = 30, max_fragment_length: int = 2000,
+                  shift: Tuple[int, int] = (4, -5), require_flags: int = 0x3, exclude_flags: int = 0xB0C, sample: str = "bulk",
+                  threads: int = 0, max_window_bytes: Optional[int] = None) -> "BamFragments":
+        """The deduplicated fragments of a coordinate-sorted paired-end BAM (K26): the leftmost mate of
+        every pair that passes the filters gives (start, end) = (pos + shift[0], pos + tlen + shift[1]), clamped to the
+        reference; equal (reference, start, end, barcode) tuples collapse into one row with their multiplicity as count.
+        barcode_tag=None: no tag is read and every pair carries `sample`."""
+        p = _frag_params(barcode_tag, min_mapq, max_fragment_length, shift, require_flags, exclude_flags, sample)
+        h = C.c_void_p()
+        check(lib.gtars_bam_fragments(self._h, C.byref(p), max_window_bytes or 0, threads, C.byref(h)))
+        try:
+            return BamFragments._take(h, self.references)
+        finally:
+            lib.gtars_bam_frags_free(h)
+
 
 def read_bam_header(path: str) -> List[str]:
     """reading.rs:279-319: the reference names, in header order"""
@@ -151,8 +168,108 @@ def compute_bam_qc(path: str, threads: int = 1, max_window_bytes: Optional[int] 
         return b.qc(threads, max_window_bytes)
 
 
+FRAG_STATS = ("records", "unplaced", "flag", "mapq", "mate_ref", "not_leftmost", "too_long", "no_barcode", "empty", "kept_pairs", "fragments",
+              "barcodes")
+
+
+class _FragParams(C.Structure):
+    _fields_ = [("barcode_tag", C.c_char * 2), ("use_barcode_tag", C.c_int32), ("sample", C.c_char_p), ("min_mapq", C.c_int32),
+                ("max_fragment_length", C.c_int64), ("shift_left", C.c_int32), ("shift_right", C.c_int32), ("require_flags", C.c_uint32),
+                ("exclude_flags", C.c_uint32)]
+
+
+def _frag_params(barcode_tag, min_mapq, max_fragment_length, shift, require_flags, exclude_flags, sample) -> _FragParams:
+    """the parameter block of gtars_bam_fragments; ValueError for what the call refuses, before any device work"""
+    p = _FragParams()
+    if barcode_tag is not None:
+        tag = barcode_tag.encode() if isinstance(barcode_tag, str) else bytes(barcode_tag)
+        if len(tag) != 2 or 0 in tag:
+            raise ValueError(f"barcode_tag must be two bytes, not {barcode_tag!r}")
+        p.barcode_tag, p.use_barcode_tag = tag, 1
+    else:
+        if not isinstance(sample, str) or not sample or any(c.isspace() for c in sample):
+            raise ValueError(f"sample must not be empty and must hold no white space, not {sample!r}")
+        p.use_barcode_tag = 0
+    p.sample = (sample if isinstance(sample, str) else "").encode()
+    if min_mapq < 0:
+        raise ValueError("min_mapq must not be negative")
+    if max_fragment_length < 1:
+        raise ValueError("max_fragment_length must be at least 1")
+    shift = tuple(int(s) for s in shift)
+    if len(shift) != 2 or any(abs(s) >= 1 << 31 for s in shift):
+        raise ValueError("shift must be two 32-bit integers")
+    if not 0 <= require_flags <= 0xFFFF or not 0 <= exclude_flags <= 0xFFFF:
+        raise ValueError("require_flags and exclude_flags are 16-bit flag masks")
+    p.min_mapq, p.max_fragment_length = min(int(min_mapq), 256), min(int(max_fragment_length), (1 << 62))
+    p.shift_left, p.shift_right = shift
+    p.require_flags, p.exclude_flags = int(require_flags), int(exclude_flags)
+    return p
+
+
+def _frag_stats(h) -> Dict[str, int]:
+    out = (C.c_uint64 * len(FRAG_STATS))()
+    lib.gtars_bam_frags_stats(h, C.cast(out, C.c_void_p))
+    return {k: int(out[i]) for i, k in enumerate(FRAG_STATS)}
+
+
+class BamFragments:
+    """The rows of BamFile.fragments in (ref, start, end, barcode) order: numpy columns ``ref`` (int32, the header's reference
+    ids), ``start``, ``end``, ``barcode`` (ids into ``barcodes``) and ``count`` (uint32); ``barcodes`` in id order (the byte
+    order of the distinct barcodes); ``references`` as (name, length); ``stats``."""
+
+    def __init__(self, ref, start, end, barcode, count, barcodes: List[str], references: List[Tuple[str, int]], stats: Dict[str, int]):
+        self.ref, self.start, self.end, self.barcode, self.count = ref, start, end, barcode, count
+        self.barcodes, self.references, self.stats = barcodes, references, stats
+
+    @classmethod
+    def _take(cls, h, references) -> "BamFragments":
+        n = int(lib.gtars_bam_frags_len(h))
+
+        def col(fn, ctype, dtype):
+            p = fn(h)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(n,)).copy() if n and p else np.zeros(0, dtype)
+
+        names = []
+        for i in range(int(lib.gtars_bam_frags_n_barcodes(h))):
+            ln = C.c_uint64()
+            names.append(C.string_at(lib.gtars_bam_frags_barcode_name(h, i, C.byref(ln)), ln.value).decode("utf-8", "replace"))
+        return cls(col(lib.gtars_bam_frags_ref, C.c_int32, np.int32), col(lib.gtars_bam_frags_start, C.c_uint32, np.uint32),
+                   col(lib.gtars_bam_frags_end, C.c_uint32, np.uint32), col(lib.gtars_bam_frags_barcode, C.c_uint32, np.uint32),
+                   col(lib.gtars_bam_frags_count, C.c_uint32, np.uint32), names, list(references), _frag_stats(h))
+
+    def __len__(self) -> int:
+        return len(self.ref)
+
+    def write(self, path) -> None:
+        """``chrom\\tstart\\tend\\tbarcode\\tcount`` per row; one gzip member when the path ends in ``.gz``"""
+        refs = (C.c_char_p * max(len(self.references), 1))(*[name.encode() for name, _ in self.references])
+        bcs = (C.c_char_p * max(len(self.barcodes), 1))(*[b.encode() for b in self.barcodes])
+        cols = [np.ascontiguousarray(self.ref, np.int32)] + [np.ascontiguousarray(c, np.uint32) for c in (self.start, self.end, self.barcode, self.count)]
+        check(lib.gtars_fragments_write_text(str(path).encode(), C.cast(refs, C.c_void_p), len(self.references), C.cast(bcs, C.c_void_p),
+                                             len(self.barcodes), *(C.c_void_p(c.ctypes.data) for c in cols), len(self)))
+
+
+def bam_to_fragments(bam_path: str, out_path: str, threads: int = 0, max_window_bytes: Optional[int] = None, **kw) -> Dict[str, int]:
+    """BamFile.fragments(**kw) of the file at bam_path written to out_path (the rows never become Python objects); returns the
+    statistics"""
+    names = ("barcode_tag", "min_mapq", "max_fragment_length", "shift", "require_flags", "exclude_flags", "sample")
+    dflt = dict(zip(names, ("CB", 30, 2000, (4, -5), 0x3, 0xB0C, "bulk")))
+    unknown = set(kw) - set(names)
+    if unknown:
+        raise TypeError(f"bam_to_fragments: unexpected arguments {sorted(unknown)}")
+    p = _frag_params(*(kw.get(k, dflt[k]) for k in names))
+    with BamFile(bam_path) as b:
+        h = C.c_void_p()
+        check(lib.gtars_bam_fragments(b._h, C.byref(p), max_window_bytes or 0, threads, C.byref(h)))
+        try:
+            check(lib.gtars_bam_frags_write(h, b._h, str(out_path).encode()))
+            return _frag_stats(h)
+        finally:
+            lib.gtars_bam_frags_free(h)
+
+
 def last_stages() -> Dict[str, float]:
-    """where the calling thread's last compute_bam_qc / columns() spent its host time"""
+    """where the calling thread's last compute_bam_qc / columns() / fragments() spent its host time"""
     out = (C.c_double * 6)()
     lib.gtars_bam_last_stages(C.cast(out, C.c_void_p))
     return {"open_s": out[0], "inflate_s": out[1], "walk_s": out[2], "windows": int(out[3]), "records": int(out[4]), "call_s": out[5]}

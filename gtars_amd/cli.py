@@ -19,6 +19,10 @@
       filling, any step).  Input from a file or stdin, output to PREFIX_{start,end,core}.wig|bedgraph or stdout.
   python -m gtars_amd uniwig bamqc --input X.bam --output Y.tsv [--threads N]
       gtars-cli/src/uniwig/cli.rs, gtars-uniwig/src/bamqc.rs: the library-complexity QC of a coordinate-sorted BAM as a TSV.
+  python -m gtars_amd bam fragments --bam X.bam --output Y.tsv[.gz] [--barcode-tag CB | --no-barcode NAME] [--min-mapq N]
+                                    [--max-length N] [--shift A,B]
+      this library's own: the deduplicated fragments of a coordinate-sorted paired-end BAM as a
+      10x-style fragment file; prints the statistics as key<TAB>value lines.
 
 Same rules as the reference: fields are split on TAB only, coordinates must parse as u32 (``+5`` is accepted, blanks and
 signs are not), every line counts (no header skipping in overlaprs).  The whole query file is ONE batch on the device.
@@ -232,8 +236,43 @@ def bamqc_parser() -> argparse.ArgumentParser:
     return q
 
 
+def bam_fragments_parser() -> argparse.ArgumentParser:
+    q = argparse.ArgumentParser(prog="python -m gtars_amd bam fragments",
+                                description="Deduplicated fragments (chrom, start, end, barcode, count) of a coordinate-sorted paired-end BAM file")
+    q.add_argument("--bam", required=True, help="Path to the BAM file")
+    q.add_argument("--output", "-o", required=True, help="Path of the fragment file to write (.gz: one gzip member)")
+    g = q.add_mutually_exclusive_group()
+    g.add_argument("--barcode-tag", default="CB", help="Aux tag (type Z) that holds the cell barcode (default CB)")
+    g.add_argument("--no-barcode", metavar="NAME", help="Read no tag: every pair belongs to the sample NAME")
+    q.add_argument("--min-mapq", type=int, default=30)
+    q.add_argument("--max-length", type=int, default=2000, help="Longest template length kept")
+    q.add_argument("--shift", default="4,-5", help="Tn5 shift of the two ends, A,B (default 4,-5)")
+    q.add_argument("--threads", "-t", type=int, default=0, help="Host threads that inflate (0: the library's budget)")
+    return q
+
+
+def run_bam_fragments(a, out: TextIO = None) -> int:
+    from .bam import bam_to_fragments
+
+    out = sys.stdout if out is None else out
+    try:
+        shift = tuple(int(x) for x in a.shift.split(","))
+        if len(shift) != 2:
+            raise ValueError
+    except ValueError:
+        sys.stderr.write(f"bam fragments: --shift takes two integers A,B, not {a.shift!r}\n")
+        return 2
+    kw = dict(barcode_tag=None, sample=a.no_barcode) if a.no_barcode is not None else dict(barcode_tag=a.barcode_tag)
+    stats = bam_to_fragments(a.bam, a.output, threads=a.threads, min_mapq=a.min_mapq, max_fragment_length=a.max_length, shift=shift, **kw)
+    for k, v in stats.items():
+        out.write(f"{k}\t{v}\n")
+    return 0
+
+
 def main(argv: Sequence[str] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
+    if argv[:2] == ["bam", "fragments"]:
+        return run_bam_fragments(bam_fragments_parser().parse_args(argv[2:]))
     # `uniwig bamqc` is a command of its own under uniwig: uniwig's own options are all required, so it cannot be one of them
     if argv[:2] == ["uniwig", "bamqc"]:
         a = bamqc_parser().parse_args(argv[2:])

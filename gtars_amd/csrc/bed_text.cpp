@@ -305,6 +305,25 @@ gtars_status gzip_of(const std::string &text, std::string &out) {
 
 }  // namespace
 
+namespace gtars {
+
+gtars_status write_text_file(const std::string &text, const char *path, bool gz) {
+    std::string packed;
+    if (gz)
+        if (const gtars_status e = gzip_of(text, packed)) return e;
+    const std::string &bytes = gz ? packed : text;
+    std::error_code ec;
+    const std::filesystem::path parent = std::filesystem::path(path).parent_path();
+    if (!parent.empty()) std::filesystem::create_directories(parent, ec);
+    FILE *f = fopen(path, "wb");
+    if (!f) return fail(GTARS_ERR_IO, std::string("cannot create ") + path);
+    const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (fclose(f) != 0 || !ok) return fail(GTARS_ERR_IO, std::string("cannot write ") + path);
+    return GTARS_OK;
+}
+
+}  // namespace gtars
+
 extern "C" {
 
 gtars_status gtars_regionset_identifier(const gtars_regionset_t *rs, char *out33) {
@@ -332,19 +351,9 @@ gtars_status gtars_regionset_bed_text(const gtars_regionset_t *rs, int on_host, 
 gtars_status gtars_regionset_write_bed(const gtars_regionset_t *rs, const char *path, int gz) {
     return guarded([&]() -> gtars_status {
         if (!rs || !path) return fail(GTARS_ERR_INVALID_ARG, "NULL argument");
-        std::string text, packed;
+        std::string text;
         if (const gtars_status e = text_of(rs, gtars_regionset_len(rs) < gtars::bed_text_device_rows(), text)) return e;
-        if (gz)
-            if (const gtars_status e = gzip_of(text, packed)) return e;
-        const std::string &bytes = gz ? packed : text;
-        std::error_code ec;
-        const std::filesystem::path parent = std::filesystem::path(path).parent_path();
-        if (!parent.empty()) std::filesystem::create_directories(parent, ec);
-        FILE *f = fopen(path, "wb");
-        if (!f) return fail(GTARS_ERR_IO, std::string("cannot create ") + path);
-        const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
-        if (fclose(f) != 0 || !ok) return fail(GTARS_ERR_IO, std::string("cannot write ") + path);
-        return GTARS_OK;
+        return gtars::write_text_file(text, path, gz != 0);
     });
 }
 

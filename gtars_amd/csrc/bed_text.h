@@ -27,6 +27,10 @@ struct BedCols {
     const uint8_t *rest = nullptr, *has_rest = nullptr;
 };
 
+// `text` to the file at `path` (its directory is created): as it is, or as one gzip member at the best compression level --
+// what to_bed / to_bed_gz write, and K26's fragment files
+gtars_status write_text_file(const std::string &text, const char *path, bool gz);
+
 constexpr int BED_WHAT_TEXT = 2;  // (behind GTARS_BED_IDENTIFIER = 0 and GTARS_BED_FILE_DIGEST = 1 of gtars_amd.h)
 
 // the switches of K25

@@ -19,6 +19,15 @@ inline unsigned grid_for(u64 n, u32 per = 256, u32 cap = 1u << 16) {
     return (unsigned)std::min<u64>(want, cap);
 }
 
+// One launch of a grid-stride kernel of 256-lane workgroups over n elements, on the geometry above, with the launch's error
+// checked: what `hipLaunchKernelGGL(k, dim3(grid_for(n)), dim3(256), 0, st, ...); GT_HIP(hipGetLastError());` spells out.
+template <class K, class... A>
+inline gtars_status launch_over(hipStream_t st, u64 n, K kernel, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(256), 0, st, args...);
+    GT_HIP(hipGetLastError());
+    return GTARS_OK;
+}
+
 // first position p in [lo, hi) with x[p] >= key (first_gt: > key), hi if none; x ascends.  P: any indexable, global or LDS
 // (their sibling last_le -- the row of an element in a scanned offset table -- is in byte_csr.h: host programs compile it too)
 template <class P>

@@ -839,9 +839,54 @@ gtars_status gtars_bam_record_offsets(const gtars_bam_t *b, const void *data, ui
 gtars_status gtars_bam_decode(const gtars_bam_t *b, uint64_t first, uint64_t count, uint64_t max_window_bytes,
                               uint32_t threads, int32_t **cols, uint64_t *n);
 gtars_status gtars_bam_qc(const gtars_bam_t *b, uint64_t max_window_bytes, uint32_t threads, gtars_bam_qc_result *out);
-/* the calling thread's last gtars_bam_qc / gtars_bam_decode: seconds of open (read + block table + header), inflate,
- * record walk; windows; records; seconds of the whole call */
+/* the calling thread's last gtars_bam_qc / gtars_bam_decode / gtars_bam_fragments: seconds of open (read + block table +
+ * header), inflate, record walk; windows; records; seconds of the whole call */
 void gtars_bam_last_stages(double *out6);
+
+/* BAM to fragments (K26; DESIGN.md section 3 K26 states the rule -- it is this library's, no reference pins it).  A
+ * coordinate-sorted paired-end BAM becomes the deduplicated fragments of a 10x-style fragment file: the leftmost mate of a
+ * proper pair makes the fragment (pos + shift_left, pos + tlen + shift_right), clamped to the reference; equal (reference,
+ * start, end, barcode) tuples collapse into one row whose count is their multiplicity.  The records are filtered, their aux
+ * tags walked, and the rows sorted and collapsed on the device. */
+typedef struct gtars_bam_frags gtars_bam_frags_t;
+typedef struct {
+    char barcode_tag[2];     /* the aux tag (type Z) that holds the cell barcode */
+    int32_t use_barcode_tag; /* 0: no tag is read, every pair belongs to `sample` */
+    const char *sample;      /* read when use_barcode_tag == 0: not empty, no white space */
+    int32_t min_mapq;        /* >= 0 */
+    int64_t max_fragment_length; /* >= 1 */
+    int32_t shift_left, shift_right;
+    uint32_t require_flags, exclude_flags;
+} gtars_bam_frag_params;
+/* barcode_tag "CB", min_mapq 30, max_fragment_length 2000, shift (4, -5), require 0x3, exclude 0xB0C, sample "bulk" */
+void gtars_bam_frag_params_default(gtars_bam_frag_params *p);
+/* records, then the reasons a record gives no fragment in the order they are tested (unplaced, flag, mapq, mate_ref,
+ * not_leftmost, too_long, no_barcode, empty), kept_pairs, fragments (rows), barcodes: records = the reasons + kept_pairs,
+ * the sum of the count column = kept_pairs */
+#define GTARS_BAM_FRAG_N_STATS 12
+/* Malformed aux data in a record that reaches the barcode step is GTARS_ERR_PARSE with the record range of its window.
+ * More than 2^32 - 2 kept pairs are refused.  *out: gtars_bam_frags_free. */
+gtars_status gtars_bam_fragments(const gtars_bam_t *b, const gtars_bam_frag_params *params, uint64_t max_window_bytes,
+                                 uint32_t threads, gtars_bam_frags_t **out);
+uint64_t gtars_bam_frags_len(const gtars_bam_frags_t *f);
+/* the columns, borrowed: refID, start, end, barcode id and count of every row, in (refID, start, end, barcode) order */
+const int32_t *gtars_bam_frags_ref(const gtars_bam_frags_t *f);
+const uint32_t *gtars_bam_frags_start(const gtars_bam_frags_t *f);
+const uint32_t *gtars_bam_frags_end(const gtars_bam_frags_t *f);
+const uint32_t *gtars_bam_frags_barcode(const gtars_bam_frags_t *f);
+const uint32_t *gtars_bam_frags_count(const gtars_bam_frags_t *f);
+/* the distinct barcodes in id order (their byte order, a prefix before the longer string); *len: bytes without the NUL */
+uint64_t gtars_bam_frags_n_barcodes(const gtars_bam_frags_t *f);
+const char *gtars_bam_frags_barcode_name(const gtars_bam_frags_t *f, uint64_t i, uint64_t *len);
+void gtars_bam_frags_stats(const gtars_bam_frags_t *f, uint64_t *out12);
+/* `chrom \t start \t end \t barcode \t count \n` per row, chrom from the header of `b`; one gzip member when the path ends
+ * in ".gz".  No row: an empty file. */
+gtars_status gtars_bam_frags_write(const gtars_bam_frags_t *f, const gtars_bam_t *b, const char *path);
+void gtars_bam_frags_free(gtars_bam_frags_t *f);
+/* the same writer over the caller's host columns and name tables (host code, no device) */
+gtars_status gtars_fragments_write_text(const char *path, const char *const *ref_names, uint32_t n_ref, const char *const *barcodes,
+                                        uint64_t n_barcodes, const int32_t *ref, const uint32_t *start, const uint32_t *end,
+                                        const uint32_t *barcode, const uint32_t *count, uint64_t n);
 
 /* ------------------------------------------------------------------------
  * VRS allele identifiers  (K18; gtars-vrs/src/normalize.rs:362-441, digest.rs:52-86, vcf_core.rs:35-189, vcf.rs:56-73;
